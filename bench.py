@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- rendered Mpix/s, forward+backward, 1920x1080, 1 M Gaussians (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,19 +10,27 @@ step drives it (reference gsplat/gsmodel.py:6-93): ``GSFunction`` forward + back
 parameter-gradient floats per Gaussian.  The default ``--mode fused`` evaluates it with the fused kernels
 (one preprocess kernel that also bins, sort, draw; draw-backward, one Jacobian-free chain-rule kernel);
 ``--mode ops`` is the reference's seven-op structure (six ops with calc_J=True, splat, splatB, chain rule) --
-its time is also reported as ``ops_ms_per_step`` of the default run.  The step validates its patch count the
+its time is also reported as ``ops_ms_per_step`` of a ``--full`` run.  The step validates its patch count the
 way ``Trainer.step`` does (``fused.deferred()`` + ``commit()``): nothing is skipped inside the timed region.
 With N > 1 every rank renders its own camera view of the same scene (one view per GPU, weak scaling) and the
 step ends with an RCCL all-reduce of the parameter gradients (236 MB at 1 M Gaussians); `value` is the
 whole-job rate: N * W*H / t_step.
 
 Order of a run: ``--ramp-steps`` (default 400, ~0.4 s) untimed steps that take the GPU off its idle clocks, the W warm-up
-steps, an untimed pre-pass with every launch bracketed by HIP events (per-kernel table), then EXACTLY K timed
-steps between barrier + synchronize pairs -- back to back, the garbage collector parked, so that the timed
-region sees the steady state of a training run and not the clock ramp (measured: 20 steps timed cold 1.03-1.04
-ms/step, the same 20 steps after the ramp: see DESIGN 5).
+steps, then EXACTLY K timed steps between barrier + synchronize pairs -- back to back, the garbage collector parked, so
+that the timed region sees the steady state of a training run and not the clock ramp (measured: 20 steps timed cold
+1.03-1.04 ms/step, the same 20 steps after the ramp: see DESIGN 5).  ``ms_per_step`` = the timed region / K.
 
-Rank 0 prints ONE JSON line carrying, besides the contract fields,
+``--dump-outputs DIR`` writes what the last timed step handed its caller as DIR/<name>.npy (float32; a fixed, seeded
+sample of the Gaussians' rows and, above 32 MB, of the image's pixels; under 64 MB in all): ``image``, the parameter
+gradients ``grad_<param>``, ``grad_us``, ``mask`` and the sampled ``rows`` (float64).  The inputs are synthetic and
+seeded, the same on every run with the same arguments, so that two builds can be compared output for output.
+
+A plain run does only that: set up, ramp, warm up, time, dump, print the contract fields (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, with ``config``).  Everything else below runs only with
+``--full``: an untimed pre-pass with every launch bracketed by HIP events (per-kernel table) before the timed steps,
+the dominant kernel bracketed inside them, and the extra legs after them.  With ``--full`` rank 0's ONE JSON line
+carries, besides the contract fields,
   gpu_busy_ms_per_step -- sum of the HIP-event durations of all kernels of a step (untimed pre-pass), next to
                   the wall-clock ms_per_step: a ratio above 1.03 means the host, not the GPU, set the pace
                   (a warning goes to stderr);
@@ -49,6 +57,45 @@ if REPO not in sys.path:
 from tools.benchlib import (HBM_PEAK_GBS, VALU_BOUND, XGMI_LINK_GBS, algorithmic_bytes, cpu_baseline,  # noqa: E402,F401
                             epoch_pattern_leg, kernel_source_hash, parse_report, relaunch_command, scene_leg,
                             train_legs, uhd_leg)
+
+DUMP_SEED = 20240613                 # fixed: the same sample on every run and build
+DUMP_ROW_BYTES = 24 << 20            # the sampled rows of the per-Gaussian outputs (+ their indices)
+DUMP_IMAGE_BYTES = 32 << 20          # the image whole up to this size, else a sample of its pixels (+ their indices)
+
+
+def dump_outputs(out_dir, image, grads, mask, n):
+    """--dump-outputs: the arrays the timed step's caller receives -- the rendered image, the gradient of every input
+    with one (``grad_<name>``, rows = Gaussians) and the visibility mask -- as float32 ``out_dir/<name>.npy``.  Rows
+    beyond DUMP_ROW_BYTES are a seeded sample (``rows.npy``: the row indices, float64), the same one for every array
+    and every run of these arguments; an image above DUMP_IMAGE_BYTES is dumped as ``image_sample.npy`` (channels x
+    sampled pixels) with the flat pixel indices in ``image_pixels.npy``."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    per_row = {"grad_" + k: g.reshape(n, -1) for k, g in grads.items() if g is not None}
+    if mask is not None and mask.numel() == n:
+        per_row["mask"] = mask.reshape(n, 1)
+    row_bytes = 8 + 4 * sum(int(t.shape[1]) for t in per_row.values())
+    k = min(n, DUMP_ROW_BYTES // row_bytes)
+    rows = np.arange(n) if k >= n else np.sort(rng.choice(n, size=k, replace=False))
+    idx = torch.from_numpy(rows).to(image.device)
+    files = {"rows": rows.astype(np.float64)}
+    for name, t in per_row.items():
+        files[name] = t.detach().index_select(0, idx).float().cpu().numpy()
+    img = image.detach().float().cpu().numpy()
+    if img.nbytes <= DUMP_IMAGE_BYTES:
+        files["image"] = img
+    else:
+        ch = img.shape[0]
+        flat = img.reshape(ch, -1)
+        kp = DUMP_IMAGE_BYTES // (4 * ch + 8)
+        pix = np.sort(rng.choice(flat.shape[1], size=kp, replace=False))
+        files["image_pixels"] = pix.astype(np.float64)
+        files["image_sample"] = flat[:, pix]
+    total = sum(v.nbytes for v in files.values())
+    assert total <= 64 << 20, total
+    for name, v in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
 
 
 def main():
@@ -92,17 +139,27 @@ def main():
                          "right after reset_alpha (every opacity <= 0.01: nothing saturates)")
     ap.add_argument("--no-skewed", action="store_true", help="skip the extra legs on the two skewed scenes")
     ap.add_argument("--no-train", action="store_true",
-                    help="skip the training-step legs (fwd_loss_bwd, train_step, epoch_pattern) of the default run")
+                    help="skip the training-step legs (fwd_loss_bwd, train_step, epoch_pattern) of a --full run")
     ap.add_argument("--no-uhd", action="store_true", help="skip the extra 3840x2160 leg")
     ap.add_argument("--extras", action="store_true",
-                    help="also time render+loss+backward and the whole optimizer step (other dL/dimage, so their "
-                         "kernel launches would blur a rocprofv3 summary of the headline step)")
+                    help="with --full: also time render+loss+backward and the whole optimizer step (other dL/dimage, "
+                         "so their kernel launches would blur a rocprofv3 summary of the headline step)")
     ap.add_argument("--mode", default="fused", choices=["fused", "ops"],
                     help="GSFunction evaluation: fused kernels (default) or the reference's 7-op structure")
     ap.add_argument("--immediate", action="store_true",
                     help="fused mode: validate the patch count inside forward (one host wait per render) instead of "
                          "at the step's commit()")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event tables and roofline, scene "
+                         "statistics, forward-only rate, the seven-op surface, eight ring views, the skewed scenes, "
+                         "training legs, 4K, HBM / clock probes, the exchange anatomy and the CPU baseline (the --no-* "
+                         "flags and --cpu-sample thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (image, parameter gradients, mask; a fixed seeded "
+                         "sample of the Gaussians) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     cmd = relaunch_command(a.gpus, os.environ, sys.argv[1:])
     if cmd is not None:       # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU)
         sys.stdout.flush()
@@ -190,6 +247,7 @@ def main():
     deferred = a.mode == "fused" and not a.immediate and overlap is None
     ev_render, ev_done, ev_parts = [], [], []     # (ev_parts: render end, all-gather end, row kernel end)
     redone = [0]
+    last_mask = [None]      # the mask output of the step's last render (--dump-outputs)
     # V > 1: the views of a rank go round-robin to --view-streams HIP streams (dist_views.ViewStreams: a view is a
     # chain of dependent kernels, a quarter of it latency-bound; two views on two streams fill each other's gaps)
     n_lanes = min(V, max(1, a.view_streams)) if (a.mode == "fused" and V > 1) else 1
@@ -220,6 +278,7 @@ def main():
             with vs_v.lane(i) as lv:
                 image, mask = GSFunction.apply(lv[0], lv[1], lv[2], lv[3], lv[4], us_v[vs_v.lane_index(i)], c, o)
                 image.backward(dl_v)
+                last_mask[0] = mask
         vs_v.finish()
         if fx_v is not None and not (exchange and fx_v is fx):   # (the step's own sink under an exchange: finished
             fx_v.finish(params["pws"], params["shs"])            # there, it is a collective)
@@ -248,6 +307,7 @@ def main():
             image, mask = GSFunction.apply(params["pws"], params["shs"], params["alphas"], params["scales"],
                                            params["rots"], us0, c, o)
             image.backward(dl)
+            last_mask[0] = mask
         if sink is not None and not exchange:
             sink.finish(params["pws"], params["shs"])
         return image
@@ -318,7 +378,7 @@ def main():
     for _ in range(a.warmup):
         step()
     sync()
-    prof = not a.no_prof
+    prof = a.full and not a.no_prof
 
     def read_report():
         need = lib.egs_prof_report(None, 0)
@@ -358,6 +418,10 @@ def main():
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
     dt = float(dt_t.item())
     ms = dt / a.steps * 1e3
+    if a.dump_outputs and rank == 0:
+        grads = {k: params[k].grad for k in order}
+        grads["us"] = us0.grad if n_lanes == 1 else None
+        dump_outputs(a.dump_outputs, image, grads, last_mask[0], sc.n)
 
     roofline_rep = read_report() if prof else None   # only the dominant kernel, recorded over the timed region
     if prof:
@@ -366,7 +430,7 @@ def main():
     # per-rank anatomy of a step (outside the timed region): render = forward + backward kernels,
     # exchange = what the gradient all-reduce adds behind them
     exch = None
-    if exchange:
+    if exchange and a.full:
         for _ in range(5):
             step(timing=True)
         sync()
@@ -410,29 +474,31 @@ def main():
                     "ring_one_link": round(form["link_bytes_per_rank"] / (XGMI_LINK_GBS * 1e9) * 1e3, 3),
                     "direct_all_links": round(form["direct_bytes_per_link"] / (XGMI_LINK_GBS * 1e9) * 1e3, 3)}}
 
-    # realised scene statistics (bytes depend on them)
-    with torch.no_grad():
-        _, ranges, gsid = forward_only()
-        lens = (ranges[:, 1] - ranges[:, 0]).to(torch.int64)
-        P_drawn = int(gsid.shape[0]); T = int(ranges.shape[0])
-        # P of the reference's lists (every tile of every rect, getRects kernel.cu:82-122): what SURVEY 8(d)'s
-        # algorithmic-byte formulas count.  The fused path draws footprint-culled lists (P_drawn <= P).
-        P = int(render(params["pws"].detach(), params["shs"].detach(), params["alphas"].detach(),
-                       params["scales"].detach(), params["rots"].detach(), cam)[4].shape[0]) if a.mode == "fused" \
-            else P_drawn
-        max_len = int(lens.max().item())
-        pairs = int(lens.sum().item()) * 256
-        # forward-only rate (BASELINE configs[1]), untimed by the headline.  The statistics above went through host
-        # reads and a seven-op render: re-ramp the clocks first (as the headline does), then time.
-        nf = max(3, a.steps // 2)
-        for _ in range(min(max(0, a.ramp_steps), 200)):
-            forward_only()
-        torch.cuda.synchronize()
-        tf0 = time.perf_counter()
-        for _ in range(nf):
-            forward_only()
-        torch.cuda.synchronize()
-        fwd_ms = (time.perf_counter() - tf0) / nf * 1e3
+    # realised scene statistics (bytes depend on them) and the forward-only rate: --full only
+    P = P_drawn = T = max_len = pairs = fwd_ms = None
+    nf = max(3, a.steps // 2)
+    if a.full:
+        with torch.no_grad():
+            _, ranges, gsid = forward_only()
+            lens = (ranges[:, 1] - ranges[:, 0]).to(torch.int64)
+            P_drawn = int(gsid.shape[0]); T = int(ranges.shape[0])
+            # P of the reference's lists (every tile of every rect, getRects kernel.cu:82-122): what SURVEY 8(d)'s
+            # algorithmic-byte formulas count.  The fused path draws footprint-culled lists (P_drawn <= P).
+            P = int(render(params["pws"].detach(), params["shs"].detach(), params["alphas"].detach(),
+                           params["scales"].detach(), params["rots"].detach(), cam)[4].shape[0]) if a.mode == "fused" \
+                else P_drawn
+            max_len = int(lens.max().item())
+            pairs = int(lens.sum().item()) * 256
+            # forward-only rate (BASELINE configs[1]), untimed by the headline.  The statistics above went through host
+            # reads and a seven-op render: re-ramp the clocks first (as the headline does), then time.
+            for _ in range(min(max(0, a.ramp_steps), 200)):
+                forward_only()
+            torch.cuda.synchronize()
+            tf0 = time.perf_counter()
+            for _ in range(nf):
+                forward_only()
+            torch.cuda.synchronize()
+            fwd_ms = (time.perf_counter() - tf0) / nf * 1e3
     # per-kernel algorithmic rate of the headline step (each input read once, each output written once)
     for k, row in kernels.items():
         ab = algorithmic_bytes(k, sc.n, P, T, HW, a.sh_dim, (world * V) if fx is not None else 0)
@@ -443,7 +509,7 @@ def main():
     # the unmodified-caller surface: GSFunction over the seven ops (six with calc_J=True, splat, splatB and the
     # chain-rule kernel over the stored Jacobians) -- an extra, outside the timed region
     ops_ms, ops_kernels, ops_public_ms = None, None, None
-    if a.mode == "fused" and not a.no_ops and rank == 0 and world == 1:
+    if a.full and a.mode == "fused" and not a.no_ops and rank == 0 and world == 1:
         for _ in range(8):        # (the first calls allocate the Jacobian tensors and learn the patch capacity)
             render_step("ops")
         torch.cuda.synchronize()
@@ -486,7 +552,7 @@ def main():
     # BASELINE configs[3] on this one GPU: the eight ring views as ONE step (views on --view-streams streams, gradients
     # accumulated, no exchange) -- an extra, outside the timed region
     ring8 = None
-    if a.mode == "fused" and not a.no_ring8 and rank == 0 and world == 1 and V == 1 and not a.immediate:
+    if a.full and a.mode == "fused" and not a.no_ring8 and rank == 0 and world == 1 and V == 1 and not a.immediate:
         cams8 = [Camera.from_scene(c, dev) for c in S.ring_cameras(sc.cam, 8)]
         lanes8 = max(1, min(8, a.view_streams))
         vs8 = DV.ViewStreams([params[k] for k in order], lanes8)
@@ -519,7 +585,7 @@ def main():
 
     # the same step on the heavy-tailed scenes (an extra, outside the timed region)
     skewed = None
-    if (a.mode == "fused" and a.scene == "iid" and not a.no_skewed and rank == 0 and world == 1 and V == 1
+    if (a.full and a.mode == "fused" and a.scene == "iid" and not a.no_skewed and rank == 0 and world == 1 and V == 1
             and not a.immediate and prof):
         ref = {"pairs": pairs, "k_draw_us": kernels.get("k_draw", {}).get("avg_us"),
                "k_draw_bwd_us": kernels.get("k_draw_bwd", {}).get("avg_us")}
@@ -533,7 +599,7 @@ def main():
     # achievable HBM bandwidth on THIS box: a device-to-device float4 copy ("confirm on the box
     # with a device-to-device copy kernel and report both")
     peak_measured, clock_mhz = None, None
-    if rank == 0:
+    if a.full and rank == 0:
         nb = 1 << 30
         src = torch.empty(nb, dtype=torch.uint8, device=dev).fill_(1)
         dst = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -562,12 +628,12 @@ def main():
         cbh = cb.cpu().numpy()
         clock_mhz = round(float(cbh[1] - cbh[0]) / max(1.0, float(cbh[3] - cbh[2])) * 100.0, 1)
 
-    # the whole training step (outside the timed region; VERDICT r5 #3: in the DEFAULT line): render + fused HIP L1 / SSIM
+    # the whole training step (outside the timed region; VERDICT r5 #3: in the --full line): render + fused HIP L1 / SSIM
     # loss + backward, and raw parameters -> activations -> render -> loss -> backward -> Adam; --extras adds the
     # reference's structure (torch activations, torch.optim.Adam).  Then the access pattern of train.py's loop
     # (epoch_pattern) and one 4K render.
     loss_leg, train_extra, epoch_pat, uhd = None, None, None, None
-    solo = a.mode == "fused" and a.scene == "iid" and rank == 0 and world == 1 and V == 1 and not a.immediate
+    solo = a.full and a.mode == "fused" and a.scene == "iid" and rank == 0 and world == 1 and V == 1 and not a.immediate
     if solo and (a.extras or not a.no_train):
         for p in params.values():
             p.grad = None
@@ -578,7 +644,7 @@ def main():
         uhd = uhd_leg(dev, lib)
 
     roofline = None
-    src_hash = kernel_source_hash()
+    src_hash = kernel_source_hash() if a.full else None
     if prof and roofline_rep and dom in roofline_rep:
         cnt, tot = roofline_rep[dom]
         avg_s = tot / cnt * 1e-3
@@ -659,7 +725,7 @@ def main():
     cpu_sample = a.cpu_sample
     if cpu_sample < 0:
         cpu_sample = sc.n if (os.cpu_count() or 1) >= 64 else 250_000
-    if rank == 0 and world == 1 and cpu_sample > 0:
+    if a.full and rank == 0 and world == 1 and cpu_sample > 0:
         cpu = cpu_baseline(sc, min(cpu_sample, sc.n))
 
     if rank == 0:
@@ -690,22 +756,25 @@ def main():
                                         "length at first sight); backward: by the work this render measured"
                                         if fused_path.TILE_WORK_CACHE else "forward: by list length; backward: by "
                                         "the work this render measured",
-                       "patches": P, "patches_drawn": P_drawn, "tiles": T, "max_list_len": max_len,
-                       "pixel_gaussian_pairs": pairs,
                        "lists": "footprint-culled (fused path)" if (a.mode == "fused" and fused_path.CULL_LISTS)
                                 else "reference rects"},
-            "gpu_busy_ms_per_step": None if gpu_busy_ms is None else round(gpu_busy_ms, 4),
-            "wall_over_gpu_busy": None if not gpu_busy_ms else round(ms / gpu_busy_ms, 4),
             "redone_steps": redone[0],
-            "fwd_only": {"ms": round(fwd_ms, 4), "Mpix/s": round(HW / (fwd_ms * 1e-3) / 1e6, 2)},
-            "ops_ms_per_step": None if ops_ms is None else round(ops_ms, 4),
-            "ops_public_pair_ms_per_step": None if ops_public_ms is None else round(ops_public_ms, 4),
-            "ops_kernels": ops_kernels,
-            "ring_views_8": ring8, "skewed_scenes": skewed,
-            "fwd_loss_bwd": loss_leg, "train_step": train_extra, "epoch_pattern": epoch_pat, "uhd_3840x2160": uhd,
-            "exchange": exch,
-            "roofline": roofline, "cpu_baseline": cpu, "kernels": kernels, "kernel_source_hash": src_hash,
         }
+        if a.full:
+            line["config"].update({"patches": P, "patches_drawn": P_drawn, "tiles": T, "max_list_len": max_len,
+                                   "pixel_gaussian_pairs": pairs})
+            line.update({
+                "gpu_busy_ms_per_step": None if gpu_busy_ms is None else round(gpu_busy_ms, 4),
+                "wall_over_gpu_busy": None if not gpu_busy_ms else round(ms / gpu_busy_ms, 4),
+                "fwd_only": {"ms": round(fwd_ms, 4), "Mpix/s": round(HW / (fwd_ms * 1e-3) / 1e6, 2)},
+                "ops_ms_per_step": None if ops_ms is None else round(ops_ms, 4),
+                "ops_public_pair_ms_per_step": None if ops_public_ms is None else round(ops_public_ms, 4),
+                "ops_kernels": ops_kernels,
+                "ring_views_8": ring8, "skewed_scenes": skewed,
+                "fwd_loss_bwd": loss_leg, "train_step": train_extra, "epoch_pattern": epoch_pat, "uhd_3840x2160": uhd,
+                "exchange": exch,
+                "roofline": roofline, "cpu_baseline": cpu, "kernels": kernels, "kernel_source_hash": src_hash,
+            })
         if cpu:
             line["fwd_speedup_vs_cpu"] = round(line["fwd_only"]["Mpix/s"] / cpu["value"], 1)
         if gpu_busy_ms and world == 1 and ms > 1.03 * gpu_busy_ms:

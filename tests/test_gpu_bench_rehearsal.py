@@ -1,8 +1,8 @@
 """``bench.py --gpus 2`` end to end on the one-GPU box: EGS_BENCH_REHEARSAL=1 puts both ranks on cuda:0 and runs the
 collectives over gloo (RCCL refuses two ranks on one device).  No number of such a line is a measurement; what is
 pinned is that the N > 1 path of the bench -- the self-relaunch under torch.distributed.run, one ring view per rank,
-the factored SH exchange chosen by ``factored_exchange_pays``, the per-rank step anatomy, ONE JSON line from rank 0 --
-runs, in both exchange forms."""
+the factored SH exchange chosen by ``factored_exchange_pays``, the per-rank step anatomy (a ``--full`` leg), ONE JSON
+line from rank 0 -- runs, in both exchange forms."""
 import json
 import os
 import subprocess
@@ -21,7 +21,7 @@ def test_two_rank_bench_line_on_one_gpu(form):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gaussians", "30000", "--width", "320",
            "--height", "192", "--steps", "3", "--warmup", "1", "--ramp-steps", "2", "--cpu-sample", "0",
-           "--factored-sh", form]
+           "--factored-sh", form, "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -60,6 +60,13 @@ def reset_scene(fx):
     return sc, stages(gsc, sc)
 
 
+# Two splatB calls on the same kept states run the same kernels on the same data; only the order in which the float
+# atomics of a Gaussian's tiles land differs.  On this scene the largest dcinv entry (a screen-filling Gaussian, ~0.05)
+# moves by up to 1.9e-6 of itself between eight identical calls (the rebuilt path: 1.2e-6), so the bound is the
+# backward pass's run-to-run jitter bound of tests/test_gpu_determinism.py: 4e-6 of the largest entry (~30 ulps).
+JITTER = 4e-6
+
+
 def _windows(rg, gx, gy):
     """three 6 x 4-tile windows: around the longest list, in the image centre, on the ragged bottom tile row"""
     lens = rg[:, 1] - rg[:, 0]
@@ -102,7 +109,7 @@ def test_skewed_reset_splatB_gradients_vs_oracle(fx, reset_scene, how):
             again = gsc.splatB(H, W, cl[0], cl[1], cl[2], d, cl[3], cl[4], cl[5], cl[6], cl[7], dev(dl))
             assert gsc.last_splatB_info()["kept_states"]
             for x, y in zip(grads, again):
-                assert float((x - y).abs().max()) <= 2e-6 * float(x.abs().max())
+                assert float((x - y).abs().max()) <= JITTER * float(x.abs().max())
             # ... and a write through .data (no version counter moves) is SEEN: everything again from the handed tensors,
             # equal to what a splatB that keeps nothing gives for them
             us2 = g["us"].clone()
@@ -118,11 +125,11 @@ def test_skewed_reset_splatB_gradients_vs_oracle(fx, reset_scene, how):
         if how == "public_kept":
             assert info["kept_states"], info
             # the kept states survive a backward pass (it reads them): the same call again finds them and gives the same
-            # gradients (float atomics in another order: 1e-6 of the maximum)
+            # gradients (float atomics in another order: JITTER)
             again = gsc.splatB(H, W, g["us"], g["cinv"], g["alphas"], d, g["col"], contrib, tau, ranges, gsid, dev(dl))
             assert gsc.last_splatB_info()["kept_states"]
             for x, y in zip(grads, again):
-                assert float((x - y).abs().max()) <= 2e-6 * float(x.abs().max())
+                assert float((x - y).abs().max()) <= JITTER * float(x.abs().max())
             # alphas as [N,1] -- what GSFunction hands both calls (gsmodel.py:36, 67): splatB normalises it to [N] before it
             # forms its signature, and so must the entry (round 6: through GSFunction nothing ever matched)
             a1 = g["alphas"].reshape(-1, 1)

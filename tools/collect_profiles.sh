@@ -11,15 +11,15 @@ T="timeout 240"
 # ONLY_COUNTERS=1: just the counter passes at the end (pmc_traffic.json), e.g. after tools/profile_step.py changed
 if [ -z "$ONLY_COUNTERS" ]; then
 # the default bench line (CPU baseline, seven-op figure, eight ring views, the two skewed scenes) and the driver's flags
-$T python $R/bench.py > $O/bench.json 2> $O/bench.err
-$T python $R/bench.py --steps 20 --warmup 5 --cpu-sample 0 > $O/bench_20_5.json 2>> $O/bench.err
+$T python $R/bench.py --full > $O/bench.json 2> $O/bench.err
+$T python $R/bench.py --full --steps 20 --warmup 5 --cpu-sample 0 > $O/bench_20_5.json 2>> $O/bench.err
 # the headline command under rocprofv3 kernel trace + stats; the same on the heavy-tailed scene after reset_alpha
-$T rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $R/bench.py --cpu-sample 0 --no-ops --no-ring8 --no-skewed > $O/bench_under_rocprof.json 2>/tmp/ks.err
+$T rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $R/bench.py --full --cpu-sample 0 --no-ops --no-ring8 --no-skewed > $O/bench_under_rocprof.json 2>/tmp/ks.err
 find /tmp/ks -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
-$T rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kr -- python $R/bench.py --scene skewed_reset --steps 20 --cpu-sample 0 --no-ops --no-ring8 > $O/bench_skewed_reset_under_rocprof.json 2>/tmp/kr.err
+$T rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kr -- python $R/bench.py --full --scene skewed_reset --steps 20 --cpu-sample 0 --no-ops --no-ring8 > $O/bench_skewed_reset_under_rocprof.json 2>/tmp/kr.err
 find /tmp/kr -name "*kernel_stats.csv" -exec cp {} $O/skewed_reset_kernel_stats.csv \;
-$T python $R/bench.py --scene skewed --steps 20 --cpu-sample 0 --no-ops --no-ring8 > $O/bench_skewed.json 2>> $O/bench.err
-EGS_SEGMENTS=0 $T python $R/bench.py --scene skewed_reset --steps 10 --cpu-sample 0 --no-ops --no-ring8 > $O/bench_skewed_reset_unsplit.json 2>> $O/bench.err
+$T python $R/bench.py --full --scene skewed --steps 20 --cpu-sample 0 --no-ops --no-ring8 > $O/bench_skewed.json 2>> $O/bench.err
+EGS_SEGMENTS=0 $T python $R/bench.py --full --scene skewed_reset --steps 10 --cpu-sample 0 --no-ops --no-ring8 > $O/bench_skewed_reset_unsplit.json 2>> $O/bench.err
 # one step as a timeline (no event brackets), after 150+ steps: steady-state clocks
 $T rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -- python $R/tools/profile_step.py --steps 160 > /tmp/tr.log 2>&1
 python $R/tools/trace_timeline.py /tmp/tr > $O/step_timeline.txt

@@ -3,14 +3,14 @@
 # && make -C ab/old/easygaussiansplatting_amd/csrc ; ab/ is git-ignored but travels with gpurun) against the working tree.
 #   gpurun --timeout 600 -- 'timeout 500 bash tools/lab/ab_reset.sh'
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out/ab
+O=$R/ab/out; mkdir -p $O
 for i in 1 2 3; do
   for w in old new; do
     D=$R; [ $w = old ] && D=$R/ab/old
-    (cd $D && timeout 120 python bench.py --scene skewed_reset --steps 30 --cpu-sample 0 --no-ops --no-ring8 2>/dev/null | tail -1 > $R/gpurun_out/ab/${w}_$i.json)
+    (cd $D && timeout 120 python bench.py --full --scene skewed_reset --steps 30 --cpu-sample 0 --no-ops --no-ring8 2>/dev/null | tail -1 > $O/${w}_$i.json)
     python - <<PY
 import json
-d=json.loads(open("$R/gpurun_out/ab/${w}_$i.json").read())
+d=json.loads(open("$O/${w}_$i.json").read())
 k=d["kernels"]
 f=sum(k[n]["avg_us"]*k[n]["launches_per_step"] for n in k if n.startswith("k_draw_seg") or n in ("k_seg_report",))
 pl=k["k_seg_plan"]["avg_us"]*k["k_seg_plan"]["launches_per_step"]

@@ -6,7 +6,7 @@
 # Measured (1 M / 1080p, k_draw 171 us): +4 SALU 178, +8 SALU 193; +4 VALU 173, +8 VALU 185; one LDS read less 162.
 cd $GRAFT_REPO_ROOT; O=gpurun_out/probe; mkdir -p $O; export PYTHONDONTWRITEBYTECODE=1
 cp easygaussiansplatting_amd/libegs_hip.so /tmp/libegs_base.so
-B="python bench.py --steps 100 --cpu-sample 0 --no-ops"
+B="python bench.py --full --steps 100 --cpu-sample 0 --no-ops"
 for v in ${VARIANTS:-base salu4 valu4 salu8 valu8 base}; do
   if [ $v = base ]; then cp /tmp/libegs_base.so easygaussiansplatting_amd/libegs_hip.so; else cp tools/variants/libegs_$v.so easygaussiansplatting_amd/libegs_hip.so; fi
   $B > $O/$v.json 2> $O/$v.err

@@ -2,7 +2,7 @@
 # round 4, lab J: k_draw_bwd with the two blocks of a tile row as one straight-line body (RED = 15) against RED = 7
 mkdir -p gpurun_out/r4j; O=gpurun_out/r4j
 cp easygaussiansplatting_amd/libegs_hip.so /tmp/keep.so
-run() { env "$@" timeout 200 python bench.py --cpu-sample 0 --steps 30 --no-ops --no-ring8 2>/dev/null | tail -1 > /tmp/b.json; python - "$*" <<'PY'
+run() { env "$@" timeout 200 python bench.py --full --cpu-sample 0 --steps 30 --no-ops --no-ring8 2>/dev/null | tail -1 > /tmp/b.json; python - "$*" <<'PY'
 import json, sys
 d = json.load(open("/tmp/b.json"))
 print(sys.argv[1], "ms/step %.4f" % d["ms_per_step"], "k_draw_bwd %.1f" % d["kernels"]["k_draw_bwd"]["avg_us"], flush=True)

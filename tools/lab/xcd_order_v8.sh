@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/xcd; mkdir -p $O
 export PYTHONDONTWRITEBYTECODE=1
 for m in 1 3 1 3; do
-  EGS_TILE_ORDER_F=$m timeout 120 python $R/bench.py --views-per-rank 8 --view-streams 4 --steps 10 --warmup 3 --ramp-steps 20 --cpu-sample 0 --no-ops --no-skewed 2>/dev/null | python -c "
+  EGS_TILE_ORDER_F=$m timeout 120 python $R/bench.py --full --views-per-rank 8 --view-streams 4 --steps 10 --warmup 3 --ramp-steps 20 --cpu-sample 0 --no-ops --no-skewed 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('order_f=$m', d['ms_per_step'], {k:v['avg_us'] for k,v in d['kernels'].items() if k in ('k_draw','k_draw_bwd')})"
 done | tee $O/steps.txt
 for m in 1 3; do
