@@ -13,7 +13,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libegs_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class EgsPolicy(C.Structure):
@@ -23,6 +23,12 @@ class EgsPolicy(C.Structure):
                 ("far_cull", C.c_int32), ("maha_floor", C.c_int32), ("alpha_clamp", C.c_int32),
                 ("alpha_skip", C.c_float), ("tau_stop", C.c_float), ("depth_key", C.c_int32),
                 ("nan_maha", C.c_int32)]
+
+
+class EgsExtras(C.Structure):
+    """Mirror of `struct EgsExtras` (render extras: depth / opacity maps, background)."""
+    _fields_ = [("depths", C.c_void_p), ("depth_out", C.c_void_p), ("alpha_out", C.c_void_p),
+                ("background", C.c_float * 3), ("dloss_ddepth", C.c_void_p), ("dloss_dalpha", C.c_void_p)]
 
 
 class EgsGaussianParams(C.Structure):
@@ -39,6 +45,7 @@ class EgsAdamGroup(C.Structure):
 _P = C.c_void_p
 _PP = C.POINTER(EgsPolicy)
 _PG = C.POINTER(EgsGaussianParams)
+_PX = C.POINTER(EgsExtras)
 _f = C.c_float
 _i = C.c_int
 _i64 = C.c_int64
@@ -91,6 +98,12 @@ SIGNATURES = {
     "egs_splat_draw_rec_seg": (_i, [_i, _i64, _P, _i, _i, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P, _P,
                                     _i, _i, _P, _sz, _P, _P, _P, _P]),
     "egs_seg_rebuild_ws_bytes": (_sz, [_i64, _i, _i]),
+    "egs_splat_draw_rec_seg_ex": (_i, [_i, _i64, _P, _i, _i, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _i, _i, _P, _sz, _P, _P, _P, _P, _PX]),
+    "egs_fused_backward_ex": (_i, [_i, _i, _i64, _i, _i] + [_P] * 8 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
+                              + [_P] * 6 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX]),
+    "egs_fused_backward_raw_ex": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
+                                  + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX]),
     "egs_splat_bwd_seg": (_i, [_i, _i64, _i, _i, _P, _P, _P, _P, _P, _PP, _P, _P, _P, _P, _P, _P, _sz, _P, _P,
                                _P, _P, _P, _P, _i, _P, _sz, _i, _P, _P]),
     "egs_mailbox_peek": (_i, [_P, _i, C.POINTER(C.c_uint32)]),

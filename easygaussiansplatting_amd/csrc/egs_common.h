@@ -154,7 +154,8 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
                      bool masked_lists = false /* gsid_per_patch carries block masks (culled lists, fused path) */,
                      void* seg_ws = nullptr /* the segment workspace the forward draw filled (egs_splat_draw_rec_seg) */,
                      size_t seg_ws_bytes = 0, int rebuild = 0 /* seg_ws is fresh: rebuild the states from contrib first */,
-                     uint32_t* seg_hint = nullptr /* page-locked words that learn the longest walk */);
+                     uint32_t* seg_hint = nullptr /* page-locked words that learn the longest walk */,
+                     const EgsExtras* extras = nullptr /* render extras: the EXTRA draw kernel (unsplit lists only) */);
 
 // ---- device helpers ---------------------------------------------------------
 #ifdef __HIPCC__

@@ -732,148 +732,21 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
     float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
     float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode) {
-  // dcolor_dpws (nullable): [N][9] left by k_preprocess_fwd; with it this kernel never reads the SH coefficients
-  // mode bit 1 (EGS_BWD_FACTORED_SH): the SH gradient stays in its factored form -- eq (5) is an outer product
-  // dL/dcolour (x) basis, so dL_dsh receives the THREE floats dL/dcolour per Gaussian ([N][3], always written, never
-  // accumulated) and the rows are formed once per step, for all views, by k_sh_grad_views; dL_dsh_high is not touched
-  const int accum = mode & 1;
-  const bool factored = (mode & 2) != 0;
-  // accum: the five (six) parameter-gradient outputs already hold the gradients of EARLIER views of the step and this
-  // view's are ADDED to them (dL_du is per view and always written): a rank that renders V views per step then needs
-  // no separate accumulation kernels (torch's `.grad += new`: 976 B per Gaussian and view against 488 here)
-  constexpr int K = 3 * NC;
-  constexpr int KH = K - 3;
-  constexpr int KS = RAW ? (KH > 0 ? KH : 1) : K;   // width of the rows that go through LDS
-  __shared__ float stage[RowStage<KS>::LDS_FLOATS];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  float sh[JW ? 1 : K], gsh[K];
-  if constexpr (!JW) {
-    if constexpr (RAW) {
-      if constexpr (KH > 0) {
-        if constexpr (KH % 2 == 1) stage_span_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
-        else stage_rows_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
-      }
-      if (i < n) { sh[0] = shs[3 * (size_t)i]; sh[1] = shs[3 * (size_t)i + 1]; sh[2] = shs[3 * (size_t)i + 2]; }
-    } else {
-      if (pp.stage_in) stage_rows_in<K>(shs, n, blockIdx.x * 256, stage, sh);
-      else if (i < n) load_sh_row<K>(shs + (size_t)K * i, sh);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k) gsh[k] = 0.f;
-  f3 gcol_out = {0.f, 0.f, 0.f};
-  if (i < n) {
-    // Every input of the row is requested here, before anything is used: with the parameter loads behind the depth
-    // test, the Jacobian row at its use and the old gradients (accum) at theirs, a row went through four dependent
-    // round trips to memory (the ISA had a full wait after each group).
-    const float4 ga = gpack[3 * (size_t)i], gb = gpack[3 * (size_t)i + 1], gc = gpack[3 * (size_t)i + 2];
-    const float depth_i = depths[i];
-    const f3 pw = ld3(pws + 3 * (size_t)i);
-    float4 q = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
-    f3 s = ld3(scales + 3 * (size_t)i);
-    float W[9];
-    if constexpr (JW) load_row<9>(dcolor_dpws + 9 * (size_t)i, W);
-    float al_raw = 0.f;
-    if constexpr (RAW) al_raw = alphas[i];
-    float4 o_rot = make_float4(0.f, 0.f, 0.f, 0.f);
-    f3 o_scale = {0.f, 0.f, 0.f}, o_pw = {0.f, 0.f, 0.f};
-    float o_alpha = 0.f;
-    if (accum) {
-      o_rot = *reinterpret_cast<const float4*>(dL_drot + 4 * (size_t)i);
-      o_scale = ld3(dL_dscale + 3 * (size_t)i);
-      o_pw = ld3(dL_dpw + 3 * (size_t)i);
-      o_alpha = dL_dalpha[i];
-    }
-    const f3 gcol = {ga.y, ga.z, ga.w};
-    const float gu0 = gb.x, gu1 = gb.y;
-    const f3 gci = {gb.z, gb.w, gc.x};
-    if constexpr (RAW) {
-      const float al = act_alpha(al_raw);
-      dL_dalpha[i] = ga.x * al * (1.f - al) + o_alpha;   // sigmoid'
-    } else {
-      dL_dalpha[i] = ga.x + o_alpha;
-    }
-    dL_du[2 * (size_t)i] = gu0; dL_du[2 * (size_t)i + 1] = gu1;
-    if (pp.near_cull && depth_i < EGS_MIN_DEPTH) {  // culled: never drawn, all gradients are zero
-      if (!accum) {
-        st3(dL_dpw + 3 * (size_t)i, {0.f, 0.f, 0.f});
-        st3(dL_dscale + 3 * (size_t)i, {0.f, 0.f, 0.f});
-        st4(dL_drot + 4 * (size_t)i, {0.f, 0.f, 0.f, 0.f});
-      }
-    } else {
-      float qnorm = 1.f;
-      if constexpr (RAW) { q = act_rot(q, qnorm); s = act_scale(s); }
-      const Proj P = project_f(pw, Rcw, tcw, pp.fx, pp.fy, pp.cx, pp.cy);
-      const Cov3 c3 = cov3d_f(q, s);
-      const Cov2 c2 = cov2d_f(c3.c, P.pc, Rcw, pp.fx, pp.fy, pp.limx, pp.limy, pp.clamp_fov);
-      float ci[3];
-      const float det_inv = inv_cov2d_f(c2.c, pp.det_eps, ci);
-      float Ji[9];
-      inv_cov2d_jac(c2.c, det_inv, Ji);
-      // dL/dcov2d = dL/dcinv2d @ J  (row vector times 3x3)
-      const float g2[3] = {gci.x * Ji[0] + gci.y * Ji[3] + gci.z * Ji[6],
-                           gci.x * Ji[1] + gci.y * Ji[4] + gci.z * Ji[7],
-                           gci.x * Ji[2] + gci.y * Ji[5] + gci.z * Ji[8]};
-      float J3[18], Jp[9];
-      cov2d_jac(c2, P.pc.z, Rcw, pp.fx, pp.fy, J3, Jp);
-      float g3[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) g3[k] = g2[0] * J3[k] + g2[1] * J3[6 + k] + g2[2] * J3[12 + k];
-      q4 gq; f3 gs;
-      cov3d_vjp(c3, q, s, g3, gq, gs);
-      if constexpr (RAW) {   // through normalize: (g - q (q.g)) / |r|; through exp: g * scale
-        const float qg = q.x * gq.w + q.y * gq.x + q.z * gq.y + q.w * gq.z;
-        gq = {(gq.w - q.x * qg) / qnorm, (gq.x - q.y * qg) / qnorm, (gq.y - q.z * qg) / qnorm,
-              (gq.z - q.w * qg) / qnorm};
-        gs = {gs.x * s.x, gs.y * s.y, gs.z * s.z};
-      }
-      if (accum) {
-        gq = {gq.w + o_rot.x, gq.x + o_rot.y, gq.y + o_rot.z, gq.z + o_rot.w};
-        gs = {gs.x + o_scale.x, gs.y + o_scale.y, gs.z + o_scale.z};
-      }
-      st4(dL_drot + 4 * (size_t)i, gq);      // eq (3)
-      st3(dL_dscale + 3 * (size_t)i, gs);    // eq (4)
-      float j00, j02, j11, j12;
-      project_jac(P, pp.fx, pp.fy, j00, j02, j11, j12);
-      const f3 gpc = {gu0 * j00 + g2[0] * Jp[0] + g2[1] * Jp[3] + g2[2] * Jp[6],
-                      gu1 * j11 + g2[0] * Jp[1] + g2[1] * Jp[4] + g2[2] * Jp[7],
-                      gu0 * j02 + gu1 * j12 + g2[0] * Jp[2] + g2[1] * Jp[5] + g2[2] * Jp[8]};
-      const ShDir<NC> d = sh_basis_f<NC>(pw, twc);
-      // eq (5): dL/dsh[c, rgb] = dL/dcolor[rgb] * basis[c]
-      gcol_out = gcol;
-      if (!factored) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          gsh[3 * c] = gcol.x * d.B[c]; gsh[3 * c + 1] = gcol.y * d.B[c]; gsh[3 * c + 2] = gcol.z * d.B[c];
-        }
-      }
-      if constexpr (!JW) sh_jac_dpw<NC>(d, sh, W);
-      float* opw = dL_dpw + 3 * (size_t)i;  // eq (7)
-      const float opw_old[3] = {o_pw.x, o_pw.y, o_pw.z};
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        opw[k] = gpc.x * Rcw[k] + gpc.y * Rcw[3 + k] + gpc.z * Rcw[6 + k] + gcol.x * W[k] + gcol.y * W[3 + k] +
-                 gcol.z * W[6 + k] + opw_old[k];
-    }
-  }
-  if (factored) {   // (a kernel argument: the whole workgroup leaves here)
-    if (i < n) st3(dL_dsh + 3 * (size_t)i, gcol_out);
-    // the view's camera centre behind the [N][3] block: the row format of egs_sh_grad_views (dL_dsh_high = its address)
-    if (dL_dsh_high && blockIdx.x == 0 && threadIdx.x < 3) dL_dsh_high[threadIdx.x] = twc[threadIdx.x];
-    return;
-  }
-  if constexpr (RAW) {
-    if (i < n) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) dL_dsh[3 * (size_t)i + k] = gsh[k] + (accum ? dL_dsh[3 * (size_t)i + k] : 0.f);
-    }
-    if constexpr (KH > 0) {
-      if constexpr (KH % 2 == 1) stage_span_out<KH>(gsh + 3, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
-      else stage_rows_out<KH>(gsh + 3, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
-    }
-  } else {
-    stage_rows_out<K>(gsh, dL_dsh, n, blockIdx.x * 256, stage, accum != 0);
-  }
+  constexpr bool EXTRA = false;
+#include "egs_preprocess_bwd.inc"
+}
+// the EXTRA flavour (render extras): gpack[i][9] holds dL/dz of the Gaussian's camera-space depth
+template <int NC, bool RAW, bool JW>
+__global__ __launch_bounds__(256) void k_preprocess_bwd_extra(
+    int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
+    const float* __restrict__ scales, const float* __restrict__ shs, const float* __restrict__ shs_high,
+    const float* __restrict__ alphas, const float* __restrict__ Rcw,
+    const float* __restrict__ tcw, const float* __restrict__ twc, const float* __restrict__ depths,
+    const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
+    float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
+    float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode) {
+  constexpr bool EXTRA = true;
+#include "egs_preprocess_bwd.inc"
 }
 
 // The SH gradient of a step from its FACTORED form (dist_views.FactoredShGrad).  For one view dL/dsh[c][rgb] is the
@@ -1171,7 +1044,9 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
                                float* dloss_dshs, float* dloss_dshs_high, float* dloss_dalphas, float* dloss_dscales,
                                float* dloss_drots, float* dloss_dus, const int32_t* tile_order,
                                float* grad_records, const float* dcolor_dpws, int phase, int row_begin, int row_count,
-                               void* seg_ws, size_t seg_ws_bytes, void* stream) {
+                               void* seg_ws, size_t seg_ws_bytes, void* stream, const EgsExtras* extras = nullptr) {
+  // extras (nullable): the render had depth / opacity / background (egs_splat_draw_rec_seg_ex); the draw pass takes
+  // their upstream gradients and leaves dL/dz in gpack[i][9], the chain rule adds it to dL/dpw (k_preprocess_bwd_extra)
   // phase 0: everything; 1: only the draw pass (-> packed gradient records in ws); 2: only the per-Gaussian
   // chain rule, for rows [row_begin, row_begin + row_count) -- a data-parallel caller launches the rows in a
   // few chunks and starts exchanging a chunk's gradients while the next one is computed (dist_views)
@@ -1199,7 +1074,7 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
   if (phase != 2) {
     int rc = splat_bwd_packed(n, patches, width, height, us, cinv2ds, alphas, colors, areas, pol, contrib, final_tau,
                               patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes, &gpack, stream, rec,
-                              tile_order, grad_records, keep_order, masked, seg_ws, seg_ws_bytes);
+                              tile_order, grad_records, keep_order, masked, seg_ws, seg_ws_bytes, 0, nullptr, extras);
     if (rc) return rc;
     if (phase == 1) return 0;
   }
@@ -1220,7 +1095,11 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
       accum
 #define EGS_PREB(NC, RAW)                                                                                         \
   do {                                                                                                            \
-    if (dcolor_dpws) EGS_LAUNCH("k_preprocess_bwd", (k_preprocess_bwd<NC, RAW, true>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
+    if (extras && dcolor_dpws)                                                                                    \
+      EGS_LAUNCH("k_preprocess_bwd_extra", (k_preprocess_bwd_extra<NC, RAW, true>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
+    else if (extras)                                                                                              \
+      EGS_LAUNCH("k_preprocess_bwd_extra", (k_preprocess_bwd_extra<NC, RAW, false>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
+    else if (dcolor_dpws) EGS_LAUNCH("k_preprocess_bwd", (k_preprocess_bwd<NC, RAW, true>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
     else EGS_LAUNCH("k_preprocess_bwd", (k_preprocess_bwd<NC, RAW, false>), g, b, s, EGS_PREB_ARGS(NC, RAW));     \
   } while (0)
   switch (sh_dim * 2 + (raw ? 1 : 0)) {
@@ -1278,6 +1157,51 @@ extern "C" int egs_fused_backward_raw(int n, int sh_dim, int64_t patches, int wi
                              dloss_dpws, dloss_dlow_shs, dloss_dhigh_shs, dloss_dalphas_raw, dloss_dscales_raw,
                              dloss_drots_raw, dloss_dus, tile_order, grad_records, dcolor_dpws, phase, row_begin,
                              row_count, seg_ws, seg_ws_bytes, stream);
+}
+
+// egs_fused_backward(_raw) of a render with extras (egs_splat_draw_rec_seg_ex): the same arguments and the same EgsExtras
+// (depths, background; dloss_ddepth / dloss_dalpha nullable); extras == NULL is the plain call
+extern "C" int egs_fused_backward_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                                     const float* rots, const float* scales, const float* shs, const float* alphas,
+                                     const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx,
+                                     float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
+                                     const float* colors, const int32_t* areas, const void* rec, const float* depths,
+                                     const int32_t* contrib, const float* final_tau,
+                                     const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
+                                     const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
+                                     float* dloss_dshs, float* dloss_dalphas, float* dloss_dscales,
+                                     float* dloss_drots, float* dloss_dus, const int32_t* tile_order,
+                                     float* grad_records, const float* dcolor_dpws, int phase, int row_begin,
+                                     int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
+                                     const EgsExtras* extras) {
+  return fused_backward_impl(false, n, sh_dim, patches, width, height, pws, rots, scales, shs, nullptr, alphas, Rcw,
+                             tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths, contrib,
+                             final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes, dloss_dpws,
+                             dloss_dshs, nullptr, dloss_dalphas, dloss_dscales, dloss_drots, dloss_dus, tile_order,
+                             grad_records, dcolor_dpws, phase, row_begin, row_count, seg_ws, seg_ws_bytes, stream,
+                             extras);
+}
+
+extern "C" int egs_fused_backward_raw_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                                         const float* rots_raw, const float* scales_raw, const float* low_shs,
+                                         const float* high_shs, const float* alphas_raw, const float* Rcw,
+                                         const float* tcw, const float* twc, float fx, float fy, float cx, float cy,
+                                         const EgsPolicy* pol, const float* us, const float* cinv2ds,
+                                         const float* colors, const int32_t* areas, const void* rec,
+                                         const float* depths, const int32_t* contrib, const float* final_tau,
+                                         const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
+                                         const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
+                                         float* dloss_dlow_shs, float* dloss_dhigh_shs, float* dloss_dalphas_raw,
+                                         float* dloss_dscales_raw, float* dloss_drots_raw, float* dloss_dus,
+                                         const int32_t* tile_order, float* grad_records, const float* dcolor_dpws,
+                                         int phase, int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes,
+                                         void* stream, const EgsExtras* extras) {
+  return fused_backward_impl(true, n, sh_dim, patches, width, height, pws, rots_raw, scales_raw, low_shs, high_shs,
+                             alphas_raw, Rcw, tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths,
+                             contrib, final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes,
+                             dloss_dpws, dloss_dlow_shs, dloss_dhigh_shs, dloss_dalphas_raw, dloss_dscales_raw,
+                             dloss_drots_raw, dloss_dus, tile_order, grad_records, dcolor_dpws, phase, row_begin,
+                             row_count, seg_ws, seg_ws_bytes, stream, extras);
 }
 
 extern "C" int egs_sh_grad_views(int n, int sh_dim, int views, const float* pws, const float* rows,

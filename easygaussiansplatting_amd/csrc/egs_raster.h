@@ -96,6 +96,22 @@ struct DrawParams {
   int masked;
 };
 DrawParams make_draw_params(int W, int H, const EgsPolicy* pol, bool backward = false);
+// the EXTRA flavour of the two draw kernels (render extras, egs_hip.h EgsExtras): a kernel argument of its own, so that
+// DrawParams and the plain instances stay as they are
+struct DrawExtras {
+  const float* depths;     // [N] camera-space z of every Gaussian
+  float* depth_out;        // forward, nullable [H][W]: sum w z
+  float* alpha_out;        // forward, nullable [H][W]: sum w = 1 - T_final (0 on empty tiles)
+  const float* dl_depth;   // backward, nullable [H][W]: dL/ddepth (NULL: 0)
+  const float* dl_alpha;   // backward, nullable [H][W]: dL/dalpha (NULL: 0)
+  float bg[3];             // image += T_final * bg
+};
+int launch_draw_extra(const DrawParams& dp, const EgsPolicy* pol, int32_t* ranges, const int32_t* gsid,
+                      const float4* rec, float* image, int32_t* contrib, float* final_tau, const DrawExtras& ex,
+                      hipStream_t s);
+int launch_draw_bwd_extra(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
+                          const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg,
+                          float* gpack, const DrawExtras& ex, hipStream_t s);
 int draw_grid(const DrawParams& p);
 // capacity of a dispatch-order buffer (the per-XCD modes pad every class to the largest one)
 int tile_order_len(int gx, int gy);

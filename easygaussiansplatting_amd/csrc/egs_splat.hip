@@ -4,6 +4,7 @@
 #include "egs_raster.h"
 
 #include <algorithm>
+#include <cstring>
 
 namespace egs {
 
@@ -44,7 +45,7 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
                      const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
                      float** gpack_out, void* stream, const void* rec_in, const int32_t* tile_order,
                      float* grad_records, bool keep_forward_order, bool masked_lists, void* seg_ws,
-                     size_t seg_ws_bytes, int rebuild, uint32_t* seg_hint) {
+                     size_t seg_ws_bytes, int rebuild, uint32_t* seg_hint, const EgsExtras* extras) {
   // rebuild != 0 (with seg_ws of egs_seg_rebuild_ws_bytes): no forward pass left its segment states here -- the public
   // splatB is handed tensors only -- so they are REBUILT first: every tile's walk from `contrib`, then the forward
   // segment launches over [0, walk) with their pixels going to scratch.  seg_hint (nullable): the page-locked words
@@ -58,6 +59,7 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
   if (!grad_records) EGS_HIP(hipMemsetAsync(gpack, 0, (size_t)n * 48, s));
   if (patches == 0) return 0;
   EGS_CHECK_ARG(contrib && final_tau && patch_range_per_tile && gsid_per_patch && dloss_dgammas);
+  EGS_CHECK_ARG(!extras || (extras->depths && !seg_ws));   // (render extras: the unsplit kernels only)
   EGS_CHECK_ARG(rec_in || (us && cinv2ds && alphas && colors && (areas || pol->footprint != 1)));
   EGS_CHECK_ARG(rec_in || (us && alphas && colors && (pol->footprint == 0 || areas)));
   DrawParams dp = make_draw_params(width, height, pol, true);
@@ -135,6 +137,15 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
                                       walk ? seg_hint : nullptr);
     if (rc) return rc;
   }
+  if (extras) {
+    DrawExtras ex = {};
+    ex.depths = extras->depths;
+    ex.dl_depth = extras->dloss_ddepth;
+    ex.dl_alpha = extras->dloss_dalpha;
+    for (int c = 0; c < 3; ++c) ex.bg[c] = extras->background[c];
+    return launch_draw_bwd_extra(dp, pol, patch_range_per_tile, gsid_per_patch, rec, final_tau, contrib, dloss_dgammas,
+                                 gpack, ex, s);
+  }
   return launch_draw_bwd(dp, pol, patch_range_per_tile, gsid_per_patch, rec, final_tau, contrib, dloss_dgammas, gpack, s);
 }
 }  // namespace egs
@@ -153,7 +164,9 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
                            void* stream, const uint32_t* patches_dev = nullptr, int32_t* tile_order = nullptr,
                            float* grad_records = nullptr, const int32_t* prev_tile_work = nullptr,
                            int order_ready = 0, int flags = 0, int32_t* gsid_plain = nullptr, void* seg_ws = nullptr,
-                           size_t seg_ws_bytes = 0, uint32_t* seg_hint = nullptr, int32_t* walk_word = nullptr) {
+                           size_t seg_ws_bytes = 0, uint32_t* seg_hint = nullptr, int32_t* walk_word = nullptr,
+                           const EgsExtras* extras = nullptr) {
+  // extras (nullable, unsplit lists only): also depth / opacity maps and a background (k_draw_extra)
   // walk_word (nullable, with seg_hint): the caller's PERSISTENT device word (one per problem size and stream, -1 before
   // its first use) in which this render's draw items gather its longest walk; the range kernel of this call first
   // publishes what the previous render left there into seg_hint[1]
@@ -174,6 +187,7 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
   // the device (the host has not seen it yet)
   EGS_CHECK_ARG(n >= 0 && patches >= 0 && patches < (int64_t)0x7FFFFFFF && width > 0 && height > 0 && pol);
   EGS_CHECK_ARG(image && contrib && final_tau && patch_range_per_tile);
+  EGS_CHECK_ARG(!extras || ((extras->depths || n == 0) && !seg_ws));
   hipStream_t s = (hipStream_t)stream;
   DrawParams dp = make_draw_params(width, height, pol);
   const bool masked = (flags & (EGS_DRAW_CULLED_LISTS | EGS_DRAW_MASKED_LISTS)) && pol->footprint == 0 &&
@@ -187,6 +201,15 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
     EGS_HIP(hipMemsetAsync(image, 0, 12 * hw, s));
     EGS_HIP(hipMemsetAsync(contrib, 0, 4 * hw, s));
     EGS_HIP(hipMemsetAsync(final_tau, 0, 4 * hw, s));
+    if (extras) {   // T = 1 everywhere: the background, no depth, no opacity
+      for (int c = 0; c < 3; ++c) {
+        uint32_t bits;
+        memcpy(&bits, &extras->background[c], 4);
+        EGS_HIP(hipMemsetD32Async((hipDeviceptr_t)(image + c * hw), (int)bits, hw, s));
+      }
+      if (extras->depth_out) EGS_HIP(hipMemsetAsync(extras->depth_out, 0, 4 * hw, s));
+      if (extras->alpha_out) EGS_HIP(hipMemsetAsync(extras->alpha_out, 0, 4 * hw, s));
+    }
     if (tile_order) {
       // the caller keeps [order | work] between renders and will trust it next time (order_ready): it must hold
       // a valid permutation and the work of THIS render (none) whatever happened here
@@ -275,6 +298,14 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
     dp.zero_buf = (float4*)grad_records;
     dp.zero_n4 = (uint32_t)(3 * (size_t)n);
     dp.zero_per = (dp.zero_n4 + (uint32_t)draw_grid(dp) - 1) / (uint32_t)draw_grid(dp);
+  }
+  if (extras) {
+    DrawExtras ex = {};
+    ex.depths = extras->depths;
+    ex.depth_out = extras->depth_out;
+    ex.alpha_out = extras->alpha_out;
+    for (int c = 0; c < 3; ++c) ex.bg[c] = extras->background[c];
+    return launch_draw_extra(dp, pol, patch_range_per_tile, gsid_per_patch, rec, image, contrib, final_tau, ex, s);
   }
   return launch_draw(dp, pol, patch_range_per_tile, gsid_per_patch, rec, image, contrib, final_tau, s);
 }
@@ -378,6 +409,23 @@ extern "C" int egs_splat_draw_rec_seg(int n, int64_t patches, const uint32_t* to
                          ws_draw_bytes, (const float4*)rec, image, contrib, final_tau, patch_range_per_tile,
                          gsid_per_patch, stream, total_patches, tile_order, grad_records, prev_tile_work, order_ready,
                          flags, gsid_plain, seg_ws, seg_ws_bytes, seg_hint, walk_word);
+}
+
+// egs_splat_draw_rec_seg of a render with extras (EgsExtras: depth / opacity maps, background); extras == NULL is the
+// plain call.  With extras the lists are never split: seg_ws must be NULL.
+extern "C" int egs_splat_draw_rec_seg_ex(int n, int64_t patches, const uint32_t* total_patches, int width, int height,
+                                         const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
+                                         size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
+                                         int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order,
+                                         float* grad_records, const int32_t* prev_tile_work, int order_ready, int flags,
+                                         void* seg_ws, size_t seg_ws_bytes, uint32_t* seg_hint, int32_t* walk_word,
+                                         int32_t* gsid_plain, void* stream, const EgsExtras* extras) {
+  EGS_CHECK_ARG((rec || n == 0) && (!total_patches || patches > 0));
+  EGS_CHECK_ARG(!gsid_plain || ((((uintptr_t)gsid_plain | (uintptr_t)gsid_per_patch) & 15) == 0));
+  return splat_draw_impl(n, patches, width, height, nullptr, nullptr, nullptr, nullptr, nullptr, pol, ws_bin, ws_draw,
+                         ws_draw_bytes, (const float4*)rec, image, contrib, final_tau, patch_range_per_tile,
+                         gsid_per_patch, stream, total_patches, tile_order, grad_records, prev_tile_work, order_ready,
+                         flags, gsid_plain, seg_ws, seg_ws_bytes, seg_hint, walk_word, extras);
 }
 
 extern "C" size_t egs_splat_bwd_ws_bytes(int n) {

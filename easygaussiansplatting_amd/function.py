@@ -15,6 +15,7 @@ Identical inputs ``(pws, shs, alphas[N,1], scales, rots, us, cam)``, outputs
 from __future__ import annotations
 
 import dataclasses
+import math
 
 import torch
 
@@ -52,12 +53,59 @@ class RenderOptions:
     accumulate: bool = False        # backward ADDS this view's gradients to the leaves' .grad inside the chain-rule kernel
     sh_sink: object = None          # dist_views.FactoredShGrad: the SH gradient of this view stays dL/dcolour [N,3]
     exchange: object = None         # dist_views.ChunkedExchange: all-reduce the gradient chunks from inside backward
+    # render extras (fused path only): ``apply`` then returns image, mask, then depth [1,H,W] if requested, then alpha
+    # [1,H,W] if requested.  depth = sum w_i z_i (camera-space z, not normalised: depth / alpha.clamp_min(eps) is the
+    # expected depth), alpha = sum w_i = 1 - T_final; both differentiable.
+    depth: bool = False             # also return the accumulated depth map
+    alpha: bool = False             # also return the accumulated opacity map
+    background: tuple = None        # (r, g, b) floats: the image gets T_final * bg added (not differentiable)
 
     def __post_init__(self):
         if self.mode not in ("fused", "ops"):
             raise ValueError("RenderOptions.mode must be 'fused' or 'ops', got %r" % (self.mode,))
         if self.sh_sink is not None and self.exchange is not None:
             raise ValueError("RenderOptions: sh_sink and exchange exclude each other")
+        if self.background is not None:
+            try:
+                bg = tuple(float(v) for v in self.background)
+            except (TypeError, ValueError):
+                bg = None
+            if bg is None or len(bg) != 3 or not all(math.isfinite(v) for v in bg) or \
+                    isinstance(self.background, (str, bytes)):
+                raise ValueError("RenderOptions.background must be three finite floats, got %r" % (self.background,))
+            object.__setattr__(self, "background", bg)
+        if self.mode == "ops" and self.has_extras():
+            raise ValueError("RenderOptions: depth / alpha / background need mode='fused' (the seven-op structure mirrors "
+                             "the reference, which renders the image only)")
+
+    def has_extras(self):
+        return bool(self.depth) or bool(self.alpha) or self.background is not None
+
+    def extras(self):
+        """-> fused.Extras of this call, or None without extras."""
+        return _fused.Extras(bool(self.depth), bool(self.alpha), self.background) if self.has_extras() else None
+
+
+def _extra_outputs(ctx, image, mask, depth, alpha):
+    """(image, mask[, depth][, alpha]) of a fused render with extras (ctx.extras)"""
+    out = [image, mask]
+    if ctx.extras.depth:
+        out.append(depth)
+    if ctx.extras.alpha:
+        out.append(alpha)
+    return tuple(out)
+
+
+def _extra_grads(ctx, dloss_dgammas, rest):
+    """-> (dL/dimage, dL/ddepth, dL/dalpha) from the grad outputs behind the mask's; dL/dimage is zeros when only the
+    maps took part in the loss, None when nothing did"""
+    rest = list(rest)
+    dd = rest.pop(0) if ctx.extras.depth else None
+    da = rest.pop(0) if ctx.extras.alpha else None
+    if dloss_dgammas is None and (dd is not None or da is not None):
+        ref = dd if dd is not None else da
+        dloss_dgammas = torch.zeros((3, ctx.cam.height, ctx.cam.width), dtype=torch.float32, device=ref.device)
+    return dloss_dgammas, dd, da
 
 
 class GSFunction(torch.autograd.Function):
@@ -76,12 +124,19 @@ class GSFunction(torch.autograd.Function):
         use_records = GSFunction.ops_use_records if opts is None else opts.ops_use_records
         # the mask output never carries a gradient: do not let autograd zero-fill one per step
         ctx.set_materialize_grads(False)
+        ctx.extras = None if opts is None else opts.extras()
         if ctx.mode == "fused":
-            image, mask, state = _fused.forward(pws, shs, alphas, scales, rots, cam, need_grad=True)
+            if ctx.extras is not None:
+                image, mask, state, depth, alpha = _fused.forward(pws, shs, alphas, scales, rots, cam, need_grad=True,
+                                                                  extras=ctx.extras)
+            else:
+                image, mask, state = _fused.forward(pws, shs, alphas, scales, rots, cam, need_grad=True)
             ctx.cam = cam
             ctx.state = state
             ctx.save_for_backward(pws, shs, alphas, scales, rots)
             ctx.mark_non_differentiable(mask)
+            if ctx.extras is not None:
+                return _extra_outputs(ctx, image, mask, depth, alpha)
             return image, mask
         # forward.md steps 1-5 == gsmodel.py:21-39
         us, pcs, depths, du_dpcs = gsc.project(pws, cam.Rcw, cam.tcw, cam.fx, cam.fy, cam.cx, cam.cy, True)
@@ -110,9 +165,12 @@ class GSFunction(torch.autograd.Function):
         return image, mask
 
     @staticmethod
-    def backward(ctx, dloss_dgammas, _):
+    def backward(ctx, dloss_dgammas, _, *rest):
         cam = ctx.cam
         pad = (None,) * (ctx.n_inputs - 6)      # cam (and the options)
+        dd = da = None
+        if ctx.extras is not None:
+            dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
         if dloss_dgammas is None:  # the image did not take part in the loss
             return (None,) * ctx.n_inputs
         if ctx.mode == "fused":
@@ -125,7 +183,8 @@ class GSFunction(torch.autograd.Function):
             acc = _fused.accumulation_targets(leaves, ctx, 5, None if o is None else (o.accumulate, o.exchange))
             dpws, dshs, dalphas, dscales, drots, dus = _fused.backward(
                 pws, shs, alphas, scales, rots, cam, ctx.state, dloss_dgammas.contiguous(), accumulate=acc,
-                sh_sink=sink, exchange=(_fused.DEFAULT if o is None else o.exchange))
+                sh_sink=sink, exchange=(_fused.DEFAULT if o is None else o.exchange),
+                dloss_ddepth=None if dd is None else dd.contiguous(), dloss_dalpha=None if da is None else da.contiguous())
             if acc is not None:      # added to the leaves' .grad inside the kernel: nothing for autograd to accumulate
                 return (None, None, None, None, None, dus) + pad
             return (dpws, dshs, dalphas, dscales, drots, dus) + pad
@@ -154,16 +213,23 @@ class GSRawFunction(torch.autograd.Function):
         ctx.opts = opts            # (``mode`` does not apply: this node IS the fused path)
         ctx.n_inputs = 9     # (as GSFunction: the maximal tuple)
         ctx.set_materialize_grads(False)
-        image, mask, state = _fused.forward(pws, low_shs, alphas_raw, scales_raw, rots_raw, cam, high_shs=high_shs,
-                                            need_grad=True)
+        ctx.extras = None if opts is None else opts.extras()
+        res = _fused.forward(pws, low_shs, alphas_raw, scales_raw, rots_raw, cam, high_shs=high_shs, need_grad=True,
+                             extras=ctx.extras)
+        image, mask, state = res[:3]
         ctx.cam = cam
         ctx.state = state
         ctx.save_for_backward(pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw)
         ctx.mark_non_differentiable(mask)
+        if ctx.extras is not None:
+            return _extra_outputs(ctx, image, mask, res[3], res[4])
         return image, mask
 
     @staticmethod
-    def backward(ctx, dloss_dgammas, _):
+    def backward(ctx, dloss_dgammas, _, *rest):
+        dd = da = None
+        if ctx.extras is not None:
+            dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
         if dloss_dgammas is None:
             return (None,) * ctx.n_inputs
         pad = (None,) * (ctx.n_inputs - 7)
@@ -175,7 +241,8 @@ class GSRawFunction(torch.autograd.Function):
         acc = _fused.accumulation_targets(leaves, ctx, 6, None if o is None else (o.accumulate, o.exchange))
         dpws, dlow, dhigh, dalphas, dscales, drots, dus = _fused.backward(
             pws, low_shs, alphas_raw, scales_raw, rots_raw, ctx.cam, ctx.state, dloss_dgammas.contiguous(),
-            high_shs=high_shs, accumulate=acc, sh_sink=sink, exchange=(_fused.DEFAULT if o is None else o.exchange))
+            high_shs=high_shs, accumulate=acc, sh_sink=sink, exchange=(_fused.DEFAULT if o is None else o.exchange),
+            dloss_ddepth=None if dd is None else dd.contiguous(), dloss_dalpha=None if da is None else da.contiguous())
         if acc is not None:
             return (None, None, None, None, None, None, dus) + pad
         return (dpws, dlow, dhigh, dalphas, dscales, drots, dus) + pad

@@ -57,7 +57,7 @@ class FusedState:
     patch count has not been validated yet (deferred validation, see ``deferred``)."""
     __slots__ = ("us", "depths", "cinv2ds", "colors", "areas", "rec", "contrib", "final_tau", "ranges", "gsid",
                  "order", "order_by_work", "gpack", "dcw", "culled", "width", "height", "ticket", "_patches", "_keep",
-                 "seg")
+                 "seg", "extras")
 
     def patch_count(self) -> int:
         """P of this render (waits for its read-back if it has not been looked at yet)."""
@@ -75,6 +75,28 @@ class FusedState:
         """The 4-bit mask of 8x8 pixel blocks per list entry (bit k = block (k & 1, k >> 1)); 15 for unculled lists."""
         g = self.gsid[:self.patch_count()]
         return ((g >> 28) & 15) if self.culled else torch.full_like(g, 15)
+
+
+class Extras(collections.namedtuple("Extras", ("depth", "alpha", "background"))):
+    """Render extras of ``forward`` (include/egs_hip.h EgsExtras): ``depth`` / ``alpha`` request the maps
+    depth = sum w_i z_i (camera-space z, NOT normalised: depth / alpha.clamp_min(eps) is the expected depth) and
+    alpha = sum w_i = 1 - T_final; ``background`` (r, g, b) floats or None adds T_final * bg to the image.  A render
+    with extras takes the unsplit draw kernels (never the segment path)."""
+    __slots__ = ()
+
+    def background_rgb(self):
+        return (0.0, 0.0, 0.0) if self.background is None else tuple(float(v) for v in self.background)
+
+
+def _egs_extras(depths, bg, depth_out=None, alpha_out=None, dloss_ddepth=None, dloss_dalpha=None):
+    ex = _lib.EgsExtras()
+    ex.depths = depths.data_ptr() if depths is not None else None
+    ex.depth_out = depth_out.data_ptr() if depth_out is not None else None
+    ex.alpha_out = alpha_out.data_ptr() if alpha_out is not None else None
+    ex.background[:] = bg
+    ex.dloss_ddepth = dloss_ddepth.data_ptr() if dloss_ddepth is not None else None
+    ex.dloss_dalpha = dloss_dalpha.data_ptr() if dloss_dalpha is not None else None
+    return ex
 
 
 class _Ticket:
@@ -341,8 +363,9 @@ def _split_sh(low_shs, high_shs, n):
     return low, high, K
 
 
-def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False):
-    """-> (image[3,H,W], mask[N] bool, state).  ``cam`` carries Rcw/tcw/twc device
+def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False, extras=None):
+    """-> (image[3,H,W], mask[N] bool, state); with ``extras`` (``Extras``) -> (image, mask, state, depth, alpha), the
+    two maps float32 [1,H,W] or None where not requested.  ``cam`` carries Rcw/tcw/twc device
     tensors and fx, fy, cx, cy, width, height (reference gausplat_dataset.py:14-26).
     ``need_grad``: a backward pass will follow (the draw kernel then also zeroes its gradient records).
     With ``high_shs`` the inputs are the RAW training tensors (``shs`` = low_shs, ``alphas`` =
@@ -372,7 +395,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False)
     f32, i32 = torch.float32, torch.int32
     S = FusedState()
     S.width, S.height = W, H
-    S.ticket, S._patches, S._keep, S.seg = None, None, None, None
+    S.ticket, S._patches, S._keep, S.seg, S.extras = None, None, None, None, None
     # the draw kernels (forward and backward) work from the packed records alone: us / cinv2ds / colors /
     # areas are not materialised
     S.us = S.cinv2ds = S.colors = S.areas = None
@@ -392,6 +415,21 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False)
                                 _ptr(S.colors), _ptr(S.areas), _ptr(S.rec), _ptr(mask), _ptr(S.dcw),
                                 1 if S.culled else 0, hint, _ptr(ws_bin), ws_bin_bytes, _ptr(total), host_slot[0], st)
     image = torch.empty((3, H, W), dtype=f32, device=dev)       # fully written by the draw stage
+    depth_map = alpha_map = None
+    ex = None           # EgsExtras of the draw stage (render extras), None: the plain entry point
+    if extras is not None:
+        S.extras = extras
+        if extras.depth:
+            depth_map = torch.empty((1, H, W), dtype=f32, device=dev)
+        if extras.alpha:
+            alpha_map = torch.empty((1, H, W), dtype=f32, device=dev)
+        ex = _egs_extras(S.depths, extras.background_rgb(), depth_map, alpha_map)
+    done = (lambda: (image, mask, S)) if extras is None else (lambda: (image, mask, S, depth_map, alpha_map))
+
+    def draw_rec(*args):
+        if ex is None:
+            return lib.egs_splat_draw_rec_seg(*args)
+        return lib.egs_splat_draw_rec_seg_ex(*args, C.byref(ex))
     S.contrib = torch.empty((H, W), dtype=i32, device=dev)
     S.final_tau = torch.empty((H, W), dtype=f32, device=dev)
     S.ranges = torch.empty((_tiles(W, H), 2), dtype=i32, device=dev)
@@ -412,7 +450,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False)
         if use_seg:
             S.seg = torch.empty(lib.egs_seg_ws_bytes(max(patches, 1), W, H), dtype=torch.uint8, device=dev)
         # (seg_ws NULL: the unsplit kernels; the hint slot still learns how far this camera's tiles are walked)
-        _lib.check(lib.egs_splat_draw_rec_seg(n, patches, None, W, H, _ptr(S.rec), pol, _ptr(ws_bin), _ptr(ws_draw),
+        _lib.check(draw_rec(n, patches, None, W, H, _ptr(S.rec), pol, _ptr(ws_bin), _ptr(ws_draw),
                                               ws_draw.numel(), _ptr(image), _ptr(S.contrib), _ptr(S.final_tau),
                                               _ptr(S.ranges), _ptr(S.gsid), _ptr(S.order), _ptr(S.gpack), prev_work,
                                               order_ready, draw_flags, _ptr(S.seg),
@@ -439,6 +477,8 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False)
     prev_work, order_ready = None, 0
     cache_entry = None        # registered only AFTER the draw stage that writes the order buffer was enqueued
     use_seg, seg_hint = _seg_decision(ctx, lib, key, pol_) if n > 0 else (False, None)
+    if extras is not None:    # the extras exist on the unsplit kernels only (the hint slot still learns from the render)
+        use_seg = False
     walk_word = _walk_word(ctx, key, dev, st, seg_hint is not None)
     walk_known = False        # the camera was rendered before: its walk lengths are on record
     if TILE_WORK_CACHE and n > 0:
@@ -504,7 +544,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False)
 
     if cap == 0 or n == 0:
         render_exact()                               # first render of this size
-        return image, mask, S
+        return done()
     # The draw stage is enqueued AHEAD of the read-back: buffers sized by the largest patch count seen so
     # far, the kernels take the real count from device memory, and {P, max depth key} travel to a page-locked
     # mailbox slot by a copy enqueued between the two stages (egs_mailbox_post).  The GPU never waits for the
@@ -537,7 +577,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False)
         ws_draw = torch.empty(lib.egs_splat_draw_ws_bytes(n, cap, W, H), dtype=torch.uint8, device=dev)
         if use_seg:
             S.seg = torch.empty(lib.egs_seg_ws_bytes(cap, W, H), dtype=torch.uint8, device=dev)
-        _lib.check(lib.egs_splat_draw_rec_seg(n, cap, _ptr(total), W, H, _ptr(S.rec), pol, _ptr(ws_bin),
+        _lib.check(draw_rec(n, cap, _ptr(total), W, H, _ptr(S.rec), pol, _ptr(ws_bin),
                                               _ptr(ws_draw), ws_draw.numel(), _ptr(image), _ptr(S.contrib),
                                               _ptr(S.final_tau), _ptr(S.ranges), _ptr(gsid_full), _ptr(S.order),
                                               _ptr(S.gpack), prev_work, order_ready, draw_flags, _ptr(S.seg),
@@ -566,7 +606,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False)
         for old in waiting:
             if old is not t and not _settle(old, False):
                 break
-        return image, mask, S
+        return done()
     t.collected = True                                # validated right here: never reported by commit()
     _settle(t, True)
     if t.status == _Ticket.FAILED:
@@ -576,7 +616,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False)
             render_exact(redo=True)
         else:                                         # more patches than ever before: redo the draw stage
             draw_exact(t.patches, redo=True)
-    return image, mask, S
+    return done()
 
 
 _pad_index = {}    # (device, N, slice widths) -> positions of the alignment words of a flat gradient buffer
@@ -665,7 +705,7 @@ def accumulation_targets(leaves, node_ctx=None, count=None, explicit=None):
 
 
 def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, high_shs=None, accumulate=None,
-             sh_sink=None, exchange=DEFAULT):
+             sh_sink=None, exchange=DEFAULT, dloss_ddepth=None, dloss_dalpha=None):
     """-> (dloss_dpws[N,3], dloss_dshs[N,K], dloss_dalphas[N,1], dloss_dscales[N,3],
            dloss_drots[N,4], dloss_dus[N,2])  -- the gradient tuple of gsmodel.py:87-93.
     With ``high_shs`` (raw tensors, see ``forward``): -> (dpws, dlow_shs[N,3], dhigh_shs[N,K-3],
@@ -674,7 +714,9 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     view's gradients are ADDED to them by the kernel and the same tensors are returned.
     ``sh_sink`` (``dist_views.FactoredShGrad``): the SH gradient of this view is left there as dL/dcolour [N,3]
     (``EGS_BWD_FACTORED_SH``); the SH entries of the return tuple are None, ``accumulate`` holds the other four
-    tensors only, and the flat buffer is the 11 floats per Gaussian of pws, alphas, scales, rots."""
+    tensors only, and the flat buffer is the 11 floats per Gaussian of pws, alphas, scales, rots.
+    A render with extras (``forward(..., extras=...)``): ``dloss_ddepth`` / ``dloss_dalpha`` [1,H,W] or None (0); the
+    background of the render is part of the gradient whatever they are."""
     raw = high_shs is not None
     pws = _chk(pws, "pws", torch.float32, (None, 3))
     n = pws.shape[0]
@@ -688,6 +730,14 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     rots = _chk(rots, "rots", torch.float32, (n, 4))
     W, H = S.width, S.height
     dl = _chk(dloss_dgammas, "dloss_dgammas", torch.float32, (3, H, W))
+    rx = getattr(S, "extras", None)
+    ex = None
+    if rx is not None:
+        dd = _chk(dloss_ddepth, "dloss_ddepth", torch.float32, (1, H, W)) if dloss_ddepth is not None else None
+        da = _chk(dloss_dalpha, "dloss_dalpha", torch.float32, (1, H, W)) if dloss_dalpha is not None else None
+        ex = _egs_extras(S.depths, rx.background_rgb(), dloss_ddepth=dd, dloss_dalpha=da)
+    elif dloss_ddepth is not None or dloss_dalpha is not None:
+        raise ValueError("fused.backward: depth / alpha gradients for a render without extras")
     lib = _lib_on(pws)
     dev = pws.device
     f32 = torch.float32
@@ -740,16 +790,20 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     gpack, S.gpack = S.gpack, None      # zeroed by the forward draw kernel: good for ONE backward pass
     seg = getattr(S, "seg", None)       # the forward pass split its long lists: the backward pass walks its segments
     seg_bytes = seg.numel() if seg is not None else 0
+    # (render extras: the _ex entry points with the same arguments and the EgsExtras behind them)
+    tail = () if ex is None else (C.byref(ex),)
     if raw:
-        launch = lambda phase, b, c: _lib.check(lib.egs_fused_backward_raw(
+        fn = lib.egs_fused_backward_raw if ex is None else lib.egs_fused_backward_raw_ex
+        launch = lambda phase, b, c: _lib.check(fn(
             n, K, S.gsid.shape[0], W, H, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), _ptr(high_shs), *mid,
             _ptr(dhigh), _ptr(dalphas), _ptr(dscales), _ptr(drots), _ptr(dus), _ptr(S.order), _ptr(gpack),
-            _ptr(getattr(S, "dcw", None)), phase, b, c, _ptr(seg), seg_bytes, st))
+            _ptr(getattr(S, "dcw", None)), phase, b, c, _ptr(seg), seg_bytes, st, *tail))
     else:
-        launch = lambda phase, b, c: _lib.check(lib.egs_fused_backward(
+        fn = lib.egs_fused_backward if ex is None else lib.egs_fused_backward_ex
+        launch = lambda phase, b, c: _lib.check(fn(
             n, K, S.gsid.shape[0], W, H, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), *mid, _ptr(dalphas),
             _ptr(dscales), _ptr(drots), _ptr(dus), _ptr(S.order), _ptr(gpack), _ptr(getattr(S, "dcw", None)), phase,
-            b, c, _ptr(seg), seg_bytes, st))
+            b, c, _ptr(seg), seg_bytes, st, *tail))
     # the forward pass was dispatched by remembered work: the backward pass keeps its order (no second order kernel)
     keep = KEEP_FORWARD_ORDER if (REUSE_ORDER and getattr(S, "order_by_work", False)) else 0
     if getattr(S, "culled", False):

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define EGS_ABI_VERSION 9
+#define EGS_ABI_VERSION 10
 
 #define EGS_ERR_BAD_ARG 10001
 #define EGS_ERR_WORKSPACE 10002
@@ -364,6 +364,28 @@ int egs_splat_draw_rec_seg(int n, int64_t patches, const uint32_t* total_patches
  * every segment is walked backward by a wave of its own: on scene.skewed_scene after reset_alpha 3.4 ms of one-wave-
  * per-tile backward draw become ~1.2 ms.  seg_hint (nullable): page-locked words that learn the longest walk from
  * either path -- a host decides from them whether its next call brings a workspace. */
+/* Render extras (ABI 10): per pixel, with w_i = T_i alpha'_i the blend weight of the draw kernel (same skip / stop / clamp
+ * rules),  depth = sum w_i z_i  (z_i = depths[i], camera-space z; NOT normalised: depth / alpha is the expected depth),
+ * alpha = sum w_i = 1 - T_final  (0 on tiles without patches), and  image_c = sum w_i c_i + T_final bg_c.  final_tau keeps
+ * its reference value (0 on tiles without patches).  Forward: depth_out / alpha_out are nullable [H][W] outputs.
+ * Backward: dloss_ddepth / dloss_dalpha are nullable [H][W] upstream gradients (NULL: 0); the background is a constant.
+ * Only the unsplit draw kernels have the extras: seg_ws must be NULL. */
+typedef struct EgsExtras {
+  const float* depths;         /* [N] camera-space z per Gaussian (egs_fused_forward's `depths`) */
+  float* depth_out;            /* nullable [H][W] */
+  float* alpha_out;            /* nullable [H][W] */
+  float background[3];
+  const float* dloss_ddepth;   /* nullable [H][W] */
+  const float* dloss_dalpha;   /* nullable [H][W] */
+} EgsExtras;
+/* egs_splat_draw_rec_seg + extras (NULL: exactly the plain call) */
+int egs_splat_draw_rec_seg_ex(int n, int64_t patches, const uint32_t* total_patches /*nullable*/, int width, int height,
+                              const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
+                              size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
+                              int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order,
+                              float* grad_records, const int32_t* prev_tile_work, int order_ready, int flags,
+                              void* seg_ws /*must be NULL with extras*/, size_t seg_ws_bytes, uint32_t* seg_hint,
+                              int32_t* walk_word, int32_t* gsid_plain, void* stream, const EgsExtras* extras);
 size_t egs_seg_rebuild_ws_bytes(int64_t patch_capacity, int width, int height);
 int egs_splat_bwd_seg(int n, int64_t patches, int width, int height, const float* us, const float* cinv2ds,
                       const float* alphas, const float* colors, const void* rec /*nullable*/, const EgsPolicy* pol,
@@ -494,6 +516,32 @@ int egs_fused_backward_raw(int n, int sh_dim, int64_t patches, int width, int he
                            const int32_t* tile_order /*nullable*/, float* grad_records /*nullable*/,
                            const float* dcolor_dpws /*nullable*/, int phase, int row_begin, int row_count,
                            void* seg_ws /*nullable*/, size_t seg_ws_bytes, void* stream);
+/* egs_fused_backward / egs_fused_backward_raw of a render with extras: the EgsExtras of the forward call (depths,
+ * background) with dloss_ddepth / dloss_dalpha; dL/dz is added to dloss_dpws.  extras == NULL: the plain call. */
+int egs_fused_backward_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                          const float* rots, const float* scales, const float* shs, const float* alphas,
+                          const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx,
+                          float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
+                          const float* colors, const int32_t* areas, const void* rec, const float* depths,
+                          const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
+                          const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
+                          float* dloss_dpws, float* dloss_dshs, float* dloss_dalphas, float* dloss_dscales,
+                          float* dloss_drots, float* dloss_dus, const int32_t* tile_order, float* grad_records,
+                          const float* dcolor_dpws, int phase, int row_begin, int row_count, void* seg_ws,
+                          size_t seg_ws_bytes, void* stream, const EgsExtras* extras);
+int egs_fused_backward_raw_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                              const float* rots_raw, const float* scales_raw, const float* low_shs,
+                              const float* high_shs, const float* alphas_raw, const float* Rcw, const float* tcw,
+                              const float* twc, float fx, float fy, float cx, float cy, const EgsPolicy* pol,
+                              const float* us, const float* cinv2ds, const float* colors, const int32_t* areas,
+                              const void* rec, const float* depths, const int32_t* contrib, const float* final_tau,
+                              const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
+                              const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
+                              float* dloss_dlow_shs, float* dloss_dhigh_shs, float* dloss_dalphas_raw,
+                              float* dloss_dscales_raw, float* dloss_drots_raw, float* dloss_dus,
+                              const int32_t* tile_order, float* grad_records, const float* dcolor_dpws, int phase,
+                              int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
+                              const EgsExtras* extras);
 /* The SH-coefficient gradient of a step from the factored form EGS_BWD_FACTORED_SH leaves:
  *     dloss_dshs[i][c][rgb] (+)= scale * sum_v  rows[v][3 i + rgb] * basis_c(pws[i] - twc_v)
  * rows: `views` rows of `row_stride` floats, row v = { dL/dcolour of view v [N][3], twc_v[3], padding } -- this rank's

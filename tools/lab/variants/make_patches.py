@@ -29,14 +29,19 @@ def draw_probes(s):
     __syncthreads();  // single-wave workgroup''')
     s=rep(s,'''        const float4 Q = sA[j], P = sB[j];            // wave-uniform address: LDS broadcast
         float4 K;
-        if constexpr (BOX) K = sC[j];
+        float zj = 0.f;
+        if constexpr (BOX) { K = sC[j]; if constexpr (EXTRA) zj = sZ[j]; }
+        else if constexpr (EXTRA) { const float4 gbz = sC[j]; K = make_float4(P.w, gbz.x, gbz.y, 0.f); zj = gbz.z; }
         else { const float2 gb = *reinterpret_cast<const float2*>(&sC[j]); K = make_float4(P.w, gb.x, gb.y, 0.f); }
 ''','''#ifdef EGS_DRAW_PROBE_NOK    // LDS probe: two broadcast reads per entry instead of three (timing only: the colours are constants)
         const float4 Q = sA[j], P = sB[j], K = make_float4(0.5f, 0.25f, 0.125f, 0.f);
+        const float zj = 0.f;
 #else
         const float4 Q = sA[j], P = sB[j];            // wave-uniform address: LDS broadcast
         float4 K;
-        if constexpr (BOX) K = sC[j];
+        float zj = 0.f;
+        if constexpr (BOX) { K = sC[j]; if constexpr (EXTRA) zj = sZ[j]; }
+        else if constexpr (EXTRA) { const float4 gbz = sC[j]; K = make_float4(P.w, gbz.x, gbz.y, 0.f); zj = gbz.z; }
         else { const float2 gb = *reinterpret_cast<const float2*>(&sC[j]); K = make_float4(P.w, gb.x, gb.y, 0.f); }
 #endif
 #ifdef EGS_DRAW_DUMMY_SALU   // issue-limit probe (tools/lab/lab_issue_probe.sh): N extra scalar instructions per entry
@@ -56,7 +61,7 @@ def draw_probes(s):
 #endif
   if (p.work_out) {   // what k_draw_bwd will walk: the largest contributor index of the tile and of its blocks''')
     return s
-mkpatch('draw_issue_probes', {'egs_draw.hip': draw_probes}, '''Issue-port probes of k_draw (round 4, DESIGN 3.3 / LAB 3.3): -DEGS_DRAW_DUMMY_SALU=N / -DEGS_DRAW_DUMMY_VALU=N add N scalar /
+mkpatch('draw_issue_probes', {'egs_draw_fwd.inc': draw_probes}, '''Issue-port probes of k_draw (round 4, DESIGN 3.3 / LAB 3.3): -DEGS_DRAW_DUMMY_SALU=N / -DEGS_DRAW_DUMMY_VALU=N add N scalar /
 vector instructions per (tile, entry); -DEGS_DRAW_PROBE_NOK reads two LDS pieces per entry instead of three and blends
 constant colours (timing only, the image is not the scene's).  Apply, build a variant library, time it with
 tools/lab/lab_issue_probe.sh.  Not part of the product sources.
@@ -74,12 +79,14 @@ __device__ __forceinline__ float rows_of4(float e0, float e1, float e2, float e3
   return (e0 + e1) + (e2 + e3);
 #endif
 ''')
-    s=rep(s,'''__device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[9], int c16) {
-''','''__device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[9], int c16) {
+    s=rep(s,'''__device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c16) {
+''','''__device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c16) {
 #if EGS_PROBE_REDUCE >= 2
   return ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7])) + q[8];
 #endif
 ''')
+    return s
+def bwd_body_probes(s):
     s=rep(s,'''      if (nanfix && !BOX && !p.masked) mymask = 0xF;
       sA[lane] = A;''','''      if (nanfix && !BOX && !p.masked) mymask = 0xF;
 #if EGS_PROBE_HIT_BITS   // (measurement builds only: even this wave-uniform test cost the production kernel two spilled registers)
@@ -89,6 +96,8 @@ __device__ __forceinline__ float rows_of4(float e0, float e1, float e2, float e3
       }
 #endif
       sA[lane] = A;''')
+    return s
+def bwd_params_probes(s):
     s=rep(s,'''  p.masked = 0;
 ''','''  p.masked = 0;
   p.hit_bits = g_probe_hit_bits;
@@ -111,7 +120,8 @@ def hdr_hit(s):
   // of its tile -- what a forward pass COULD leave behind; the backward pass then drops such entries before staging them
   const uint32_t* hit_bits;
 };''')
-mkpatch('draw_bwd_probes', {'egs_draw.hip': bwd_probes, 'egs_raster.h': hdr_hit}, '''Probes of k_draw_bwd (rounds 3-4, LAB 3.4): -DEGS_PROBE_REDUCE=1|2 replaces the transposing wave reduction by plain adds
+mkpatch('draw_bwd_probes', {'egs_draw.hip': lambda s: bwd_params_probes(bwd_probes(s)), 'egs_draw_bwd.inc': bwd_body_probes,
+                           'egs_raster.h': hdr_hit}, '''Probes of k_draw_bwd (rounds 3-4, LAB 3.4): -DEGS_PROBE_REDUCE=1|2 replaces the transposing wave reduction by plain adds
 (timing only); -DEGS_PROBE_HIT_BITS=1 + egs_probe_set_hit_bits() lets the kernel drop entries a forward pass could have
 marked as hitting nothing (prices the "hit bit" proposal; tools/lab/bwd_hit_stats.py binds the symbol itself).
 Not part of the product sources.
