@@ -3,7 +3,8 @@ scomup/EasyGaussianSplatting (its CUDA extension ``gsplatcu``) and the pieces a 
 around it, on hand-written HIP kernels for gfx950 behind a C ABI (``include/egs_hip.h``).
 
     gsplatcu   the seven reference ops (project ... splat, splatB) + set_policy
-    function   GSFunction (autograd boundary of gsmodel.py), GSRawFunction (GSModel.forward in one node), render
+    function   GSFunction (autograd boundary of gsmodel.py), GSRawFunction (GSModel.forward in one node),
+               GSPoseFunction / GSRawPoseFunction (the same with camera pose gradients), render
     fused      the fused forward / backward behind GSFunction
     loss       gau_loss (0.8 L1 + 0.2 (1 - SSIM)) as HIP kernels
     optim      FusedAdam;  density  DensityControl (prune / clone / split / alpha reset on the device)

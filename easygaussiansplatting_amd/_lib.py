@@ -31,6 +31,11 @@ class EgsExtras(C.Structure):
                 ("background", C.c_float * 3), ("dloss_ddepth", C.c_void_p), ("dloss_dalpha", C.c_void_p)]
 
 
+class EgsPoseGrad(C.Structure):
+    """Mirror of `struct EgsPoseGrad` (camera pose gradients of egs_fused_backward(_raw)_pose)."""
+    _fields_ = [("dloss_dRcw", C.c_void_p), ("dloss_dtcw", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 class EgsGaussianParams(C.Structure):
     """Mirror of `struct EgsGaussianParams`: device pointers of the six training tensors (or their moments)."""
     _fields_ = [(k, C.c_void_p) for k in ("pws", "low_shs", "high_shs", "alphas_raw", "scales_raw", "rots_raw")]
@@ -46,6 +51,7 @@ _P = C.c_void_p
 _PP = C.POINTER(EgsPolicy)
 _PG = C.POINTER(EgsGaussianParams)
 _PX = C.POINTER(EgsExtras)
+_PPose = C.POINTER(EgsPoseGrad)
 _f = C.c_float
 _i = C.c_int
 _i64 = C.c_int64
@@ -104,6 +110,11 @@ SIGNATURES = {
                               + [_P] * 6 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX]),
     "egs_fused_backward_raw_ex": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
                                   + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX]),
+    "egs_pose_ws_bytes": (_sz, [_i]),
+    "egs_fused_backward_pose": (_i, [_i, _i, _i64, _i, _i] + [_P] * 8 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
+                                + [_P] * 6 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX, _PPose]),
+    "egs_fused_backward_raw_pose": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
+                                    + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX, _PPose]),
     "egs_splat_bwd_seg": (_i, [_i, _i64, _i, _i, _P, _P, _P, _P, _P, _PP, _P, _P, _P, _P, _P, _P, _sz, _P, _P,
                                _P, _P, _P, _P, _i, _P, _sz, _i, _P, _P]),
     "egs_mailbox_peek": (_i, [_P, _i, C.POINTER(C.c_uint32)]),

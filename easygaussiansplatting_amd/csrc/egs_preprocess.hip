@@ -732,7 +732,8 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
     float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
     float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode) {
-  constexpr bool EXTRA = false;
+  constexpr bool EXTRA = false, POSE = false;
+  float* const pose_ws = nullptr;   // (POSE only)
 #include "egs_preprocess_bwd.inc"
 }
 // the EXTRA flavour (render extras): gpack[i][9] holds dL/dz of the Gaussian's camera-space depth
@@ -745,8 +746,62 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_extra(
     const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
     float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
     float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode) {
-  constexpr bool EXTRA = true;
+  constexpr bool EXTRA = true, POSE = false;
+  float* const pose_ws = nullptr;   // (POSE only)
 #include "egs_preprocess_bwd.inc"
+}
+// the POSE flavour (camera pose gradient, either EXTRA): every output of the plain / extra instance, plus one partial
+// row {dL/dRcw [9], dL/dtcw [3], dL/dtwc [3], 0} per workgroup in pose_ws, summed by k_pose_reduce
+template <int NC, bool RAW, bool JW, bool EXTRA>
+__global__ __launch_bounds__(256) void k_preprocess_bwd_pose(
+    int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
+    const float* __restrict__ scales, const float* __restrict__ shs, const float* __restrict__ shs_high,
+    const float* __restrict__ alphas, const float* __restrict__ Rcw,
+    const float* __restrict__ tcw, const float* __restrict__ twc, const float* __restrict__ depths,
+    const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
+    float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
+    float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode, float* __restrict__ pose_ws) {
+  constexpr bool POSE = true;
+#include "egs_preprocess_bwd.inc"
+}
+
+// The camera pose gradient from the partial rows of k_preprocess_bwd_pose: ONE workgroup of 1024 threads, thread t sums
+// column t % 16 of rows t / 16, t / 16 + 64, ... in double (eight loads in flight, added in row order), the 64 partial
+// sums of a column are added in index order, then the camera centre twc = -Rcw^T tcw is folded back:
+// dL/dRcw[r][k] -= tcw[r] dL/dtwc[k],  dL/dtcw -= Rcw dL/dtwc.  Every sum has a fixed order: identical partial rows
+// give identical bits.
+__global__ __launch_bounds__(1024) void k_pose_reduce(int rows, const float* __restrict__ pose_ws,
+                                                      const float* __restrict__ Rcw, const float* __restrict__ tcw,
+                                                      float* __restrict__ dL_dRcw, float* __restrict__ dL_dtcw) {
+  __shared__ double part[64][17];
+  __shared__ double g[16];
+  const int t = threadIdx.x, col = t & 15;
+  double acc = 0.0;
+  int r = t >> 4;
+  for (; r + 7 * 64 < rows; r += 8 * 64) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = pose_ws[16 * (size_t)(r + 64 * j) + col];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc += (double)v[j];
+  }
+  for (; r < rows; r += 64) acc += (double)pose_ws[16 * (size_t)r + col];
+  part[t >> 4][col] = acc;
+  __syncthreads();
+  if (t < 16) {
+    double v = 0.0;
+    for (int j = 0; j < 64; ++j) v += part[j][t];
+    g[t] = v;
+  }
+  __syncthreads();
+  if (t == 0) {
+    const double* gt = g + 12;   // dL/dtwc
+    for (int i = 0; i < 3; ++i) {
+      for (int k = 0; k < 3; ++k) dL_dRcw[3 * i + k] = (float)(g[3 * i + k] - (double)tcw[i] * gt[k]);
+      dL_dtcw[i] = (float)(g[9 + i] - ((double)Rcw[3 * i] * gt[0] + (double)Rcw[3 * i + 1] * gt[1] +
+                                       (double)Rcw[3 * i + 2] * gt[2]));
+    }
+  }
 }
 
 // The SH gradient of a step from its FACTORED form (dist_views.FactoredShGrad).  For one view dL/dsh[c][rgb] is the
@@ -1033,6 +1088,9 @@ extern "C" int egs_fused_forward_raw(int n, int sh_dim, const float* pws, const 
 
 extern "C" size_t egs_fused_backward_ws_bytes(int n) { return egs_splat_bwd_ws_bytes(n); }
 
+// one partial row of 16 floats per 256-Gaussian workgroup of k_preprocess_bwd_pose
+extern "C" size_t egs_pose_ws_bytes(int n) { return align_up((size_t)div_up(n > 0 ? n : 1, 256) * 16 * sizeof(float), 256); }
+
 static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
                                const float* rots, const float* scales, const float* shs, const float* shs_high,
                                const float* alphas, const float* Rcw, const float* tcw, const float* twc, float fx,
@@ -1044,7 +1102,8 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
                                float* dloss_dshs, float* dloss_dshs_high, float* dloss_dalphas, float* dloss_dscales,
                                float* dloss_drots, float* dloss_dus, const int32_t* tile_order,
                                float* grad_records, const float* dcolor_dpws, int phase, int row_begin, int row_count,
-                               void* seg_ws, size_t seg_ws_bytes, void* stream, const EgsExtras* extras = nullptr) {
+                               void* seg_ws, size_t seg_ws_bytes, void* stream, const EgsExtras* extras = nullptr,
+                               const EgsPoseGrad* pose = nullptr) {
   // extras (nullable): the render had depth / opacity / background (egs_splat_draw_rec_seg_ex); the draw pass takes
   // their upstream gradients and leaves dL/dz in gpack[i][9], the chain rule adds it to dL/dpw (k_preprocess_bwd_extra)
   // phase 0: everything; 1: only the draw pass (-> packed gradient records in ws); 2: only the per-Gaussian
@@ -1058,6 +1117,18 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
   const bool factored = (phase & EGS_BWD_FACTORED_SH) != 0;
   phase &= ~(EGS_BWD_KEEP_FORWARD_ORDER | EGS_BWD_CULLED_LISTS | EGS_BWD_ACCUMULATE | EGS_BWD_FACTORED_SH);
   EGS_CHECK_ARG(phase >= 0 && phase <= 2);
+  // pose (nullable): the camera gradient needs every row in one launch (k_pose_reduce sums all partial rows)
+  if (pose) {
+    EGS_CHECK_ARG(phase == 0 && pose->dloss_dRcw && pose->dloss_dtcw);
+    if (pose->ws_bytes < egs_pose_ws_bytes(n) || !pose->ws) {
+      set_error(EGS_ERR_WORKSPACE, "fused_backward pose workspace too small", __FILE__, __LINE__);
+      return EGS_ERR_WORKSPACE;
+    }
+    if (n == 0) {   // nothing drawn: the pose gradient is zero
+      EGS_HIP(hipMemsetAsync(pose->dloss_dRcw, 0, 9 * sizeof(float), (hipStream_t)stream));
+      EGS_HIP(hipMemsetAsync(pose->dloss_dtcw, 0, 3 * sizeof(float), (hipStream_t)stream));
+    }
+  }
   if (phase != 2) { row_begin = 0; row_count = n; }
   EGS_CHECK_ARG(row_begin >= 0 && row_count >= 0 && row_begin + (int64_t)row_count <= n && row_begin % 256 == 0);
   EGS_CHECK_ARG(sh_dim == 3 || sh_dim == 12 || sh_dim == 27 || sh_dim == 48);
@@ -1093,9 +1164,17 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
                : ((RAW && dloss_dshs_high) ? dloss_dshs_high + kh * r0 : dloss_dshs_high), dloss_dalphas + r0,       \
       dloss_dscales + 3 * r0, dloss_drots + 4 * r0, dloss_dus + 2 * r0, dcolor_dpws ? dcolor_dpws + 9 * r0 : dcolor_dpws, \
       accum
+  float* pose_ws = pose ? (float*)pose->ws : nullptr;
+#define EGS_PREB_POSE(NC, RAW, JW, EX) \
+  EGS_LAUNCH("k_preprocess_bwd_pose", (k_preprocess_bwd_pose<NC, RAW, JW, EX>), g, b, s, EGS_PREB_ARGS(NC, RAW), pose_ws)
 #define EGS_PREB(NC, RAW)                                                                                         \
   do {                                                                                                            \
-    if (extras && dcolor_dpws)                                                                                    \
+    if (pose) {                                                                                                   \
+      if (extras && dcolor_dpws) EGS_PREB_POSE(NC, RAW, true, true);                                              \
+      else if (extras) EGS_PREB_POSE(NC, RAW, false, true);                                                       \
+      else if (dcolor_dpws) EGS_PREB_POSE(NC, RAW, true, false);                                                  \
+      else EGS_PREB_POSE(NC, RAW, false, false);                                                                  \
+    } else if (extras && dcolor_dpws)                                                                             \
       EGS_LAUNCH("k_preprocess_bwd_extra", (k_preprocess_bwd_extra<NC, RAW, true>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
     else if (extras)                                                                                              \
       EGS_LAUNCH("k_preprocess_bwd_extra", (k_preprocess_bwd_extra<NC, RAW, false>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
@@ -1113,8 +1192,14 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
     default: EGS_PREB(16, true); break;
   }
 #undef EGS_PREB
+#undef EGS_PREB_POSE
 #undef EGS_PREB_ARGS
   EGS_LAUNCH_OK();
+  if (pose) {
+    EGS_LAUNCH("k_pose_reduce", k_pose_reduce, dim3(1), dim3(1024), s, (int)g.x, pose_ws, Rcw, tcw, pose->dloss_dRcw,
+               pose->dloss_dtcw);
+    EGS_LAUNCH_OK();
+  }
   return 0;
 }
 
@@ -1202,6 +1287,53 @@ extern "C" int egs_fused_backward_raw_ex(int n, int sh_dim, int64_t patches, int
                              dloss_dpws, dloss_dlow_shs, dloss_dhigh_shs, dloss_dalphas_raw, dloss_dscales_raw,
                              dloss_drots_raw, dloss_dus, tile_order, grad_records, dcolor_dpws, phase, row_begin,
                              row_count, seg_ws, seg_ws_bytes, stream, extras);
+}
+
+// egs_fused_backward(_raw)_ex plus the camera pose gradient (include/egs_hip.h EgsPoseGrad)
+extern "C" int egs_fused_backward_pose(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                                       const float* rots, const float* scales, const float* shs, const float* alphas,
+                                       const float* Rcw, const float* tcw, const float* twc, float fx, float fy,
+                                       float cx, float cy, const EgsPolicy* pol, const float* us,
+                                       const float* cinv2ds, const float* colors, const int32_t* areas,
+                                       const void* rec, const float* depths, const int32_t* contrib,
+                                       const float* final_tau, const int32_t* patch_range_per_tile,
+                                       const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws,
+                                       size_t ws_bytes, float* dloss_dpws, float* dloss_dshs, float* dloss_dalphas,
+                                       float* dloss_dscales, float* dloss_drots, float* dloss_dus,
+                                       const int32_t* tile_order, float* grad_records, const float* dcolor_dpws,
+                                       int phase, int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes,
+                                       void* stream, const EgsExtras* extras, const EgsPoseGrad* pose) {
+  EGS_CHECK_ARG(pose);
+  return fused_backward_impl(false, n, sh_dim, patches, width, height, pws, rots, scales, shs, nullptr, alphas, Rcw,
+                             tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths, contrib,
+                             final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes, dloss_dpws,
+                             dloss_dshs, nullptr, dloss_dalphas, dloss_dscales, dloss_drots, dloss_dus, tile_order,
+                             grad_records, dcolor_dpws, phase, row_begin, row_count, seg_ws, seg_ws_bytes, stream,
+                             extras, pose);
+}
+
+extern "C" int egs_fused_backward_raw_pose(int n, int sh_dim, int64_t patches, int width, int height,
+                                           const float* pws, const float* rots_raw, const float* scales_raw,
+                                           const float* low_shs, const float* high_shs, const float* alphas_raw,
+                                           const float* Rcw, const float* tcw, const float* twc, float fx, float fy,
+                                           float cx, float cy, const EgsPolicy* pol, const float* us,
+                                           const float* cinv2ds, const float* colors, const int32_t* areas,
+                                           const void* rec, const float* depths, const int32_t* contrib,
+                                           const float* final_tau, const int32_t* patch_range_per_tile,
+                                           const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws,
+                                           size_t ws_bytes, float* dloss_dpws, float* dloss_dlow_shs,
+                                           float* dloss_dhigh_shs, float* dloss_dalphas_raw, float* dloss_dscales_raw,
+                                           float* dloss_drots_raw, float* dloss_dus, const int32_t* tile_order,
+                                           float* grad_records, const float* dcolor_dpws, int phase, int row_begin,
+                                           int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
+                                           const EgsExtras* extras, const EgsPoseGrad* pose) {
+  EGS_CHECK_ARG(pose);
+  return fused_backward_impl(true, n, sh_dim, patches, width, height, pws, rots_raw, scales_raw, low_shs, high_shs,
+                             alphas_raw, Rcw, tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths,
+                             contrib, final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes,
+                             dloss_dpws, dloss_dlow_shs, dloss_dhigh_shs, dloss_dalphas_raw, dloss_dscales_raw,
+                             dloss_drots_raw, dloss_dus, tile_order, grad_records, dcolor_dpws, phase, row_begin,
+                             row_count, seg_ws, seg_ws_bytes, stream, extras, pose);
 }
 
 extern "C" int egs_sh_grad_views(int n, int sh_dim, int views, const float* pws, const float* rows,

@@ -1,6 +1,6 @@
-// Body of the chain-rule kernels k_preprocess_bwd (EXTRA = false) and k_preprocess_bwd_extra (EXTRA = true),
-// egs_preprocess.hip.  Included inside the kernel, as egs_draw_fwd.inc: the parameters, NC, RAW, JW and EXTRA come
-// from there.
+// Body of the chain-rule kernels k_preprocess_bwd (EXTRA = false), k_preprocess_bwd_extra (EXTRA = true) and
+// k_preprocess_bwd_pose (POSE = true), egs_preprocess.hip.  Included inside the kernel, as egs_draw_fwd.inc: the
+// parameters, NC, RAW, JW, EXTRA and POSE come from there.
   // dcolor_dpws (nullable): [N][9] left by k_preprocess_fwd; with it this kernel never reads the SH coefficients
   // mode bit 1 (EGS_BWD_FACTORED_SH): the SH gradient stays in its factored form -- eq (5) is an outer product
   // dL/dcolour (x) basis, so dL_dsh receives the THREE floats dL/dcolour per Gaussian ([N][3], always written, never
@@ -31,6 +31,12 @@
 #pragma unroll
   for (int k = 0; k < K; ++k) gsh[k] = 0.f;
   f3 gcol_out = {0.f, 0.f, 0.f};
+  // POSE: this lane's share of the camera gradient, {dL/dRcw [3][3], dL/dtcw [3], dL/dtwc [3]} (DESIGN §3.8)
+  float pg[POSE ? 15 : 1];
+  if constexpr (POSE) {
+#pragma unroll
+    for (int k = 0; k < 15; ++k) pg[k] = 0.f;
+  }
   if (i < n) {
     // Every input of the row is requested here, before anything is used: with the parameter loads behind the depth
     // test, the Jacobian row at its use and the old gradients (accum) at theirs, a row went through four dependent
@@ -125,7 +131,48 @@
       for (int k = 0; k < 3; ++k)
         opw[k] = gpc.x * Rcw[k] + gpc.y * Rcw[3 + k] + gpc.z * Rcw[6 + k] + gcol.x * W[k] + gcol.y * W[3 + k] +
                  gcol.z * W[6 + k] + opw_old[k];
+      if constexpr (POSE) {
+        // p_c = Rcw pw + tcw: dL/dtcw += gpc, dL/dRcw += gpc pw^T (projection, J(p_c) of cov2d, depth)
+        const float gp[3] = {gpc.x, gpc.y, gpc.z}, pwv[3] = {pw.x, pw.y, pw.z};
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          pg[9 + r] = gp[r];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) pg[3 * r + k] = gp[r] * pwv[k];
+        }
+        // the W = Rcw factor of cov2d = (J W) Sigma (J W)^T with J held (clamped x/z, y/z as cov2d_f):
+        // dL/dM0 = 2 g2[0] v0 + g2[1] v1, dL/dM1 = g2[1] v0 + 2 g2[2] v1;  dL/dRcw += J0^T dL/dM0 + J1^T dL/dM1
+        const f3 gM0 = (2.f * g2[0]) * c2.v0 + g2[1] * c2.v1;
+        const f3 gM1 = g2[1] * c2.v0 + (2.f * g2[2]) * c2.v1;
+        const float z = P.pc.z, z2 = z * z;
+        const float a00 = pp.fx / z, a02 = -(pp.fx * c2.x) / z2, a11 = pp.fy / z, a12 = -(pp.fy * c2.y) / z2;
+        pg[0] += a00 * gM0.x; pg[1] += a00 * gM0.y; pg[2] += a00 * gM0.z;
+        pg[3] += a11 * gM1.x; pg[4] += a11 * gM1.y; pg[5] += a11 * gM1.z;
+        pg[6] += a02 * gM0.x + a12 * gM1.x; pg[7] += a02 * gM0.y + a12 * gM1.y; pg[8] += a02 * gM0.z + a12 * gM1.z;
+        // the SH colour sees pw - twc: dL/dtwc = -gcol^T dcolor/dpw
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pg[12 + k] = -(gcol.x * W[k] + gcol.y * W[3 + k] + gcol.z * W[6 + k]);
+      }
     }
+  }
+  if constexpr (POSE) {
+    // one partial row of 16 floats per workgroup: a fixed butterfly across the wave64, the 4 waves in order through
+    // LDS.  No atomics -- k_pose_reduce sums the rows in a fixed order, so the result is bitwise reproducible.
+    __shared__ float pose_part[4][16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 15; ++k) {
+      float v = pg[k];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      if (lane == 0) pose_part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16)
+      pose_ws[16 * (size_t)blockIdx.x + threadIdx.x] =
+          threadIdx.x < 15 ? ((pose_part[0][threadIdx.x] + pose_part[1][threadIdx.x]) + pose_part[2][threadIdx.x]) +
+                                 pose_part[3][threadIdx.x]
+                           : 0.f;
   }
   if (factored) {   // (a kernel argument: the whole workgroup leaves here)
     if (i < n) st3(dL_dsh + 3 * (size_t)i, gcol_out);

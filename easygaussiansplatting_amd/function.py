@@ -248,6 +248,128 @@ class GSRawFunction(torch.autograd.Function):
         return (dpws, dlow, dhigh, dalphas, dscales, drots, dus) + pad
 
 
+def camera_centre(Rcw, tcw):
+    """twc = -Rcw^T tcw on the device (no host sync): the camera centre the pose nodes render with.  ``Camera.twc`` is
+    -inv(Rcw) tcw instead; on a true rotation the two agree."""
+    return -(Rcw.t() @ tcw)
+
+
+class _PoseCamera:
+    """The camera of one pose-node call: size and intrinsics of ``cam``, extrinsics from the node's tensors"""
+
+    def __init__(self, cam, Rcw, tcw):
+        self.width, self.height = cam.width, cam.height
+        self.fx, self.fy, self.cx, self.cy = cam.fx, cam.fy, cam.cx, cam.cy
+        self.Rcw, self.tcw = Rcw, tcw
+        self.twc = camera_centre(Rcw, tcw).contiguous()
+
+
+def _pose_setup(ctx, opts, Rcw, tcw, cam, like):
+    """checks shared by the pose nodes; -> the call's _PoseCamera"""
+    if opts is not None and opts.mode == "ops":
+        raise ValueError("the pose nodes need mode='fused' (the seven-op structure mirrors the reference, which has no "
+                         "pose Jacobian)")
+    if (opts.exchange if opts is not None else _fused._exchange_hook) is not None:
+        raise ValueError("the pose nodes do not combine with a ChunkedExchange (the camera gradient needs the chain "
+                         "rule in one launch)")
+    Rcw, tcw = _fused.pose_tensors(Rcw, tcw, like)
+    ctx.opts = opts
+    ctx.set_materialize_grads(False)
+    ctx.extras = None if opts is None else opts.extras()
+    return _PoseCamera(cam, Rcw.detach(), tcw.detach())
+
+
+class GSPoseFunction(torch.autograd.Function):
+    """``GSFunction`` on the fused path with the camera pose as two more differentiable inputs:
+    ``apply(pws, shs, alphas, scales, rots, us, Rcw, tcw, cam, opts=None)``.  ``cam`` supplies only the image size and
+    the intrinsics; the extrinsics are ``Rcw`` [3,3] and ``tcw`` [3] (float32, on the device of the Gaussians), and the
+    camera centre is twc = -Rcw^T tcw (``camera_centre``; ``Camera`` uses -inv(Rcw) tcw -- equal on a true rotation,
+    and the gradient is that of the -Rcw^T tcw form).  Outputs are those of ``GSFunction`` (render extras included);
+    the backward pass also returns dL/dRcw and dL/dtcw, formed by the chain-rule kernel in the same launch.
+    ``RenderOptions(mode="ops")`` or an ``exchange`` raise ValueError."""
+
+    @staticmethod
+    def forward(ctx, pws, shs, alphas, scales, rots, us, Rcw, tcw, cam, opts=None):
+        pcam = _pose_setup(ctx, opts, Rcw, tcw, cam, pws)
+        ctx.n_inputs = 10
+        res = _fused.forward(pws, shs, alphas, scales, rots, pcam, need_grad=True, extras=ctx.extras)
+        image, mask, state = res[:3]
+        ctx.cam = pcam
+        ctx.state = state
+        ctx.save_for_backward(pws, shs, alphas, scales, rots)
+        ctx.mark_non_differentiable(mask)
+        if ctx.extras is not None:
+            return _extra_outputs(ctx, image, mask, res[3], res[4])
+        return image, mask
+
+    @staticmethod
+    def backward(ctx, dloss_dgammas, _, *rest):
+        dd = da = None
+        if ctx.extras is not None:
+            dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
+        if dloss_dgammas is None:
+            return (None,) * ctx.n_inputs
+        o = ctx.opts
+        cam = ctx.cam
+        pws, shs, alphas, scales, rots = ctx.saved_tensors
+        sink = _fused.sh_sink_for(ctx, 5, (shs,), None if o is None else (o.sh_sink, None))
+        leaves = (pws, alphas, scales, rots) if sink is not None else (pws, shs, alphas, scales, rots)
+        acc = _fused.accumulation_targets(leaves, ctx, 5, None if o is None else (o.accumulate, None))
+        dpws, dshs, dalphas, dscales, drots, dus, dR, dt = _fused.backward(
+            pws, shs, alphas, scales, rots, cam, ctx.state, dloss_dgammas.contiguous(), accumulate=acc, sh_sink=sink,
+            exchange=None, dloss_ddepth=None if dd is None else dd.contiguous(),
+            dloss_dalpha=None if da is None else da.contiguous(), pose=(cam.Rcw, cam.tcw))
+        pose = (dR if ctx.needs_input_grad[6] else None, dt if ctx.needs_input_grad[7] else None, None, None)
+        if acc is not None:
+            return (None, None, None, None, None, dus) + pose
+        return (dpws, dshs, dalphas, dscales, drots, dus) + pose
+
+
+class GSRawPoseFunction(torch.autograd.Function):
+    """``GSRawFunction`` with the camera pose as two more differentiable inputs:
+    ``apply(pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw, us, Rcw, tcw, cam, opts=None)``; ``cam``, the
+    camera centre and the options as ``GSPoseFunction``."""
+
+    @staticmethod
+    def forward(ctx, pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw, us, Rcw, tcw, cam, opts=None):
+        pcam = _pose_setup(ctx, opts, Rcw, tcw, cam, pws)
+        ctx.n_inputs = 11
+        res = _fused.forward(pws, low_shs, alphas_raw, scales_raw, rots_raw, pcam, high_shs=high_shs, need_grad=True,
+                             extras=ctx.extras)
+        image, mask, state = res[:3]
+        ctx.cam = pcam
+        ctx.state = state
+        ctx.save_for_backward(pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw)
+        ctx.mark_non_differentiable(mask)
+        if ctx.extras is not None:
+            return _extra_outputs(ctx, image, mask, res[3], res[4])
+        return image, mask
+
+    @staticmethod
+    def backward(ctx, dloss_dgammas, _, *rest):
+        dd = da = None
+        if ctx.extras is not None:
+            dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
+        if dloss_dgammas is None:
+            return (None,) * ctx.n_inputs
+        o = ctx.opts
+        cam = ctx.cam
+        pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw = ctx.saved_tensors
+        sink = _fused.sh_sink_for(ctx, 6, (low_shs, high_shs), None if o is None else (o.sh_sink, None))
+        leaves = (pws, alphas_raw, scales_raw, rots_raw) if sink is not None else \
+            (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw)
+        acc = _fused.accumulation_targets(leaves, ctx, 6, None if o is None else (o.accumulate, None))
+        dpws, dlow, dhigh, dalphas, dscales, drots, dus, dR, dt = _fused.backward(
+            pws, low_shs, alphas_raw, scales_raw, rots_raw, cam, ctx.state, dloss_dgammas.contiguous(),
+            high_shs=high_shs, accumulate=acc, sh_sink=sink, exchange=None,
+            dloss_ddepth=None if dd is None else dd.contiguous(), dloss_dalpha=None if da is None else da.contiguous(),
+            pose=(cam.Rcw, cam.tcw))
+        pose = (dR if ctx.needs_input_grad[7] else None, dt if ctx.needs_input_grad[8] else None, None, None)
+        if acc is not None:
+            return (None, None, None, None, None, None, dus) + pose
+        return (dpws, dlow, dhigh, dalphas, dscales, drots, dus) + pose
+
+
 def render(pws, shs, alphas, scales, rots, cam, calc_J=False):
     """Inference path of the reference's forward_gpu.py:47-60 (six op calls)."""
     us, pcs, depths = gsc.project(pws, cam.Rcw, cam.tcw, cam.fx, cam.fy, cam.cx, cam.cy, False)

@@ -99,6 +99,23 @@ def _egs_extras(depths, bg, depth_out=None, alpha_out=None, dloss_ddepth=None, d
     return ex
 
 
+def pose_tensors(Rcw, tcw, like):
+    """(Rcw [3,3], tcw [3]) of a pose gradient, validated: float32 tensors on the device of ``like``; -> contiguous"""
+    pair = ((Rcw, "Rcw", (3, 3)), (tcw, "tcw", (3,)))
+    for t, name, shape in pair:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("pose %s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if tuple(t.shape) != shape:
+            raise ValueError("pose %s must have shape %s, got %s" % (name, list(shape), list(t.shape)))
+        if t.dtype != torch.float32:
+            raise ValueError("pose %s must be torch.float32, got %s" % (name, t.dtype))
+    for t, name, _ in pair:
+        if not t.is_cuda or t.device != like.device:
+            raise ValueError("pose %s must live on the device of the Gaussians (%s), got %s" % (name, like.device,
+                                                                                                 t.device))
+    return Rcw.contiguous(), tcw.contiguous()
+
+
 class _Ticket:
     """One enqueue-ahead render whose {P, max depth key} read-back is still in flight."""
     __slots__ = ("ctx", "slot", "key", "cap", "hint", "state", "status", "patches", "need", "collected")
@@ -705,7 +722,7 @@ def accumulation_targets(leaves, node_ctx=None, count=None, explicit=None):
 
 
 def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, high_shs=None, accumulate=None,
-             sh_sink=None, exchange=DEFAULT, dloss_ddepth=None, dloss_dalpha=None):
+             sh_sink=None, exchange=DEFAULT, dloss_ddepth=None, dloss_dalpha=None, pose=None):
     """-> (dloss_dpws[N,3], dloss_dshs[N,K], dloss_dalphas[N,1], dloss_dscales[N,3],
            dloss_drots[N,4], dloss_dus[N,2])  -- the gradient tuple of gsmodel.py:87-93.
     With ``high_shs`` (raw tensors, see ``forward``): -> (dpws, dlow_shs[N,3], dhigh_shs[N,K-3],
@@ -716,7 +733,10 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     (``EGS_BWD_FACTORED_SH``); the SH entries of the return tuple are None, ``accumulate`` holds the other four
     tensors only, and the flat buffer is the 11 floats per Gaussian of pws, alphas, scales, rots.
     A render with extras (``forward(..., extras=...)``): ``dloss_ddepth`` / ``dloss_dalpha`` [1,H,W] or None (0); the
-    background of the render is part of the gradient whatever they are."""
+    background of the render is part of the gradient whatever they are.
+    ``pose`` = (Rcw [3,3], tcw [3]), float32 on the device: the camera of the forward call (``cam.twc`` must be
+    -Rcw^T tcw), whose gradient is also formed -> the usual tuple followed by (dloss_dRcw [3,3], dloss_dtcw [3]).  The
+    pose gradient belongs to this view: always written, never added to ``accumulate``.  Excludes ``exchange``."""
     raw = high_shs is not None
     pws = _chk(pws, "pws", torch.float32, (None, 3))
     n = pws.shape[0]
@@ -741,6 +761,19 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     lib = _lib_on(pws)
     dev = pws.device
     f32 = torch.float32
+    pg = None
+    hook = _exchange_hook if exchange is DEFAULT else exchange      # (``exchange``: the call's own ChunkedExchange or None)
+    if pose is not None:
+        if hook is not None:
+            raise ValueError("fused.backward: a pose gradient cannot go with a ChunkedExchange (the chunked chain rule "
+                             "has no single launch to reduce the camera gradient in)")
+        Rcw, tcw = pose_tensors(pose[0], pose[1], pws)
+        dRcw = torch.empty((3, 3), dtype=f32, device=dev)
+        dtcw = torch.empty((3,), dtype=f32, device=dev)
+        pose_ws = torch.empty(lib.egs_pose_ws_bytes(n), dtype=torch.uint8, device=dev)
+        pg = _lib.EgsPoseGrad(dRcw.data_ptr(), dtcw.data_ptr(), pose_ws.data_ptr(), pose_ws.numel())
+    else:
+        Rcw, tcw = cam.Rcw, cam.tcw
     # The parameter gradients are slices of ONE allocation (order: pws, shs | low, high, alphas, scales,
     # rots): a data-parallel caller exchanges all 59 floats per Gaussian with a single all-reduce of
     # ``flat_grad_buffer(params)`` instead of five or six latency-bound ones (autograd adopts the slices as
@@ -782,7 +815,7 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     dus = torch.empty((n, 2), dtype=f32, device=dev)
     ws_bytes = lib.egs_fused_backward_ws_bytes(n)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    mid = (_ptr(alphas), _ptr(cam.Rcw), _ptr(cam.tcw), _ptr(cam.twc), float(cam.fx), float(cam.fy), float(cam.cx),
+    mid = (_ptr(alphas), _ptr(Rcw), _ptr(tcw), _ptr(cam.twc), float(cam.fx), float(cam.fy), float(cam.cx),
            float(cam.cy), C.byref(_pol()), _ptr(S.us), _ptr(S.cinv2ds), _ptr(S.colors), _ptr(S.areas), _ptr(S.rec),
            _ptr(S.depths), _ptr(S.contrib), _ptr(S.final_tau), _ptr(S.ranges), _ptr(S.gsid), _ptr(dl), _ptr(ws),
            ws_bytes, _ptr(dpws), _ptr(dshs))
@@ -792,14 +825,20 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     seg_bytes = seg.numel() if seg is not None else 0
     # (render extras: the _ex entry points with the same arguments and the EgsExtras behind them)
     tail = () if ex is None else (C.byref(ex),)
+    if pg is not None:      # (pose: the _pose entry points, EgsExtras nullable, then the EgsPoseGrad)
+        tail = (None if ex is None else C.byref(ex), C.byref(pg))
     if raw:
         fn = lib.egs_fused_backward_raw if ex is None else lib.egs_fused_backward_raw_ex
+        if pg is not None:
+            fn = lib.egs_fused_backward_raw_pose
         launch = lambda phase, b, c: _lib.check(fn(
             n, K, S.gsid.shape[0], W, H, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), _ptr(high_shs), *mid,
             _ptr(dhigh), _ptr(dalphas), _ptr(dscales), _ptr(drots), _ptr(dus), _ptr(S.order), _ptr(gpack),
             _ptr(getattr(S, "dcw", None)), phase, b, c, _ptr(seg), seg_bytes, st, *tail))
     else:
         fn = lib.egs_fused_backward if ex is None else lib.egs_fused_backward_ex
+        if pg is not None:
+            fn = lib.egs_fused_backward_pose
         launch = lambda phase, b, c: _lib.check(fn(
             n, K, S.gsid.shape[0], W, H, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), *mid, _ptr(dalphas),
             _ptr(dscales), _ptr(drots), _ptr(dus), _ptr(S.order), _ptr(gpack), _ptr(getattr(S, "dcw", None)), phase,
@@ -812,7 +851,6 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
         keep |= ACCUMULATE            # the outputs hold earlier views' gradients: add to them
     if sh_sink is not None:
         keep |= FACTORED_SH
-    hook = _exchange_hook if exchange is DEFAULT else exchange      # (``exchange``: the call's own ChunkedExchange or None)
     if hook is not None and sh_sink is not None:
         raise RuntimeError("fused.backward: sh_sink and an attached ChunkedExchange exclude each other")
     chunks = hook.chunks if hook is not None else 1
@@ -833,8 +871,10 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
             c = min(rows, n - b)
             launch(2 | (keep & (ACCUMULATE | FACTORED_SH)), b, c)
             hook.on_chunk([p[b:b + c] for p in parts])
+    tail = () if pg is None else (dRcw, dtcw)
     if sh_sink is not None:
-        return (dpws, None, None, dalphas, dscales, drots, dus) if raw else (dpws, None, dalphas, dscales, drots, dus)
+        return ((dpws, None, None, dalphas, dscales, drots, dus) if raw else (dpws, None, dalphas, dscales, drots, dus)) \
+            + tail
     if raw:
-        return dpws, dshs, dhigh, dalphas, dscales, drots, dus
-    return dpws, dshs, dalphas, dscales, drots, dus
+        return (dpws, dshs, dhigh, dalphas, dscales, drots, dus) + tail
+    return (dpws, dshs, dalphas, dscales, drots, dus) + tail

@@ -542,6 +542,45 @@ int egs_fused_backward_raw_ex(int n, int sh_dim, int64_t patches, int width, int
                               const int32_t* tile_order, float* grad_records, const float* dcolor_dpws, int phase,
                               int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
                               const EgsExtras* extras);
+/* Camera pose gradients.  egs_fused_backward(_raw)_pose take the arguments of their _ex counterpart (extras nullable),
+ * write every output of it, and also dL/dRcw [3][3] (row-major) and dL/dtcw [3] of this view -- always written, never
+ * added to, whatever EGS_BWD_ACCUMULATE says of the per-Gaussian outputs.  The camera centre is treated as
+ * twc = -Rcw^T tcw (the rotation convention; equal to -inv(Rcw) tcw on a true rotation): the caller passes that twc,
+ * and its gradient is folded into dL/dRcw and dL/dtcw.  Near-culled Gaussians contribute nothing.  The base phase must
+ * be 0 (EGS_ERR_BAD_ARG otherwise); ws of fewer than egs_pose_ws_bytes(n) bytes gives EGS_ERR_WORKSPACE.  The result
+ * is bitwise reproducible: one partial row per workgroup of the chain-rule kernel, summed in a fixed order in double. */
+typedef struct EgsPoseGrad {
+  float* dloss_dRcw;   /* [3][3] */
+  float* dloss_dtcw;   /* [3] */
+  void* ws;            /* egs_pose_ws_bytes(n) bytes of device memory */
+  size_t ws_bytes;
+} EgsPoseGrad;
+size_t egs_pose_ws_bytes(int n);
+int egs_fused_backward_pose(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                            const float* rots, const float* scales, const float* shs, const float* alphas,
+                            const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx,
+                            float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
+                            const float* colors, const int32_t* areas, const void* rec, const float* depths,
+                            const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
+                            const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
+                            float* dloss_dpws, float* dloss_dshs, float* dloss_dalphas, float* dloss_dscales,
+                            float* dloss_drots, float* dloss_dus, const int32_t* tile_order, float* grad_records,
+                            const float* dcolor_dpws, int phase, int row_begin, int row_count, void* seg_ws,
+                            size_t seg_ws_bytes, void* stream, const EgsExtras* extras /*nullable*/,
+                            const EgsPoseGrad* pose);
+int egs_fused_backward_raw_pose(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                                const float* rots_raw, const float* scales_raw, const float* low_shs,
+                                const float* high_shs, const float* alphas_raw, const float* Rcw, const float* tcw,
+                                const float* twc, float fx, float fy, float cx, float cy, const EgsPolicy* pol,
+                                const float* us, const float* cinv2ds, const float* colors, const int32_t* areas,
+                                const void* rec, const float* depths, const int32_t* contrib, const float* final_tau,
+                                const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
+                                const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
+                                float* dloss_dlow_shs, float* dloss_dhigh_shs, float* dloss_dalphas_raw,
+                                float* dloss_dscales_raw, float* dloss_drots_raw, float* dloss_dus,
+                                const int32_t* tile_order, float* grad_records, const float* dcolor_dpws, int phase,
+                                int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
+                                const EgsExtras* extras /*nullable*/, const EgsPoseGrad* pose);
 /* The SH-coefficient gradient of a step from the factored form EGS_BWD_FACTORED_SH leaves:
  *     dloss_dshs[i][c][rgb] (+)= scale * sum_v  rows[v][3 i + rgb] * basis_c(pws[i] - twc_v)
  * rows: `views` rows of `row_stride` floats, row v = { dL/dcolour of view v [N][3], twc_v[3], padding } -- this rank's
