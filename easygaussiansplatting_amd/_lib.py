@@ -97,6 +97,10 @@ SIGNATURES = {
     "egs_fused_forward": (_i, [_i, _i] + [_P] * 8 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8 + [_i, _i, _P, _sz, _P, _P, _P]),
     "egs_fused_forward_raw": (_i, [_i, _i] + [_P] * 9 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8
                               + [_i, _i, _P, _sz, _P, _P, _P]),
+    "egs_fused_forward_aa": (_i, [_i, _i] + [_P] * 8 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8
+                             + [_i, _i, _P, _sz, _P, _P, _P]),
+    "egs_fused_forward_raw_aa": (_i, [_i, _i] + [_P] * 9 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8
+                                 + [_i, _i, _P, _sz, _P, _P, _P]),
     "egs_fused_backward_raw": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
                                + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P]),
     "egs_seg_ws_bytes": (_sz, [_i64, _i, _i]),
@@ -149,6 +153,7 @@ SIGNATURES = {
     "egs_nn_sqdist_ws_bytes": (_sz, [_i]),
     "egs_nn_sqdist": (_i, [_i, _P, _P, _sz, _P, _P]),
     "egs_viewer_prep": (_i, [_i, _i, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _f, _f, _P, _P, _P]),
+    "egs_viewer_prep_aa": (_i, [_i, _i, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _f, _f, _P, _P, _P]),
     "egs_prof_enable": (_i, [_i]),
     "egs_prof_set_filter": (None, [C.c_char_p]),
     "egs_prof_reset": (None, []),

@@ -197,6 +197,31 @@ __device__ __forceinline__ void inv_cov2d_jac(const float* c2, float det_inv, fl
   J[6] = -a * c * d2 + det_inv; J[7] = 2 * a * b * d2; J[8] = -a * a * d2;
 }
 
+// ---- anti-aliased rendering: opacity compensation of the 2D filter ----------------------
+// c2 = the dilated cov2d (a, b, c) incl. the +0.3; comp = sqrt(det(Sigma) / det(Sigma + 0.3 I)), Sigma = c2 - 0.3 I.
+// det(Sigma) <= 0 or a comp that is not finite (a NaN cov2d): comp = 0 and no gradient.
+__device__ __forceinline__ float aa_comp_f(const float* c2) {
+  const float a = c2[0], b = c2[1], c = c2[2];
+  const float det0 = (a - 0.3f) * (c - 0.3f) - b * b, det1 = a * c - b * b;
+  const float comp = sqrtf(det0 / det1);
+  return (det0 > 0.f && isfinite(comp)) ? comp : 0.f;
+}
+// comp, and gc2 += g dcomp/dc2 (b as the one off-diagonal entry, the convention of inv_cov2d_jac / cov2d_jac):
+// r = det0 / det1, dr/da = ((c - h) - r c) / det1, dr/dc = ((a - h) - r a) / det1, dr/db = 2 b (r - 1) / det1,
+// dcomp = dr / (2 comp)
+__device__ __forceinline__ float aa_comp_vjp(const float* c2, float g, float* gc2) {
+  const float a = c2[0], b = c2[1], c = c2[2];
+  const float det0 = (a - 0.3f) * (c - 0.3f) - b * b, det1 = a * c - b * b;
+  const float inv1 = 1.f / det1, r = det0 * inv1;
+  const float comp = sqrtf(r);
+  if (!(det0 > 0.f && isfinite(comp))) return 0.f;
+  const float k = g * inv1 / (2.f * comp);
+  gc2[0] += k * ((c - 0.3f) - r * c);
+  gc2[1] += k * (2.f * b * (r - 1.f));
+  gc2[2] += k * ((a - 0.3f) - r * a);
+  return comp;
+}
+
 // ---- sh2color: F.4 and its Jacobians                    (reference kernel.cu:619-807)
 // constants: reference common.cuh:28-43 == gsplat/sh_coef.py:5-23
 #define SH_C0_0 0.28209479177387814f

@@ -589,133 +589,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
                                                         float4* __restrict__ rec, BinParams bp, BinCountOut bo,
                                                         uint8_t* __restrict__ visible,
                                                         float* __restrict__ dcolor_dpws) {
-  // dcolor_dpws (nullable, [N][9]): dcolor/dpw of every Gaussian, for the backward pass -- the ONLY thing that pass
-  // needs the SH coefficients for (eq (7): dL/dpw += dL/dcolor . dcolor/dpw; dL/dsh needs the basis alone).  36 B
-  // written here save the 4K-byte SH row re-read there (192 B at SH degree 3).
-  constexpr int K = 3 * NC;
-  constexpr int KH = K - 3;   // width of high_shs
-  constexpr int STAGE_FLOATS = (RAW && KH > 0 && RowStage<KH>::LDS_FLOATS > RowStage<12>::LDS_FLOATS)
-                                   ? RowStage<KH>::LDS_FLOATS : RowStage<12>::LDS_FLOATS;
-  __shared__ float stage[STAGE_FLOATS];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (bo.cr)     // the superblock sums of the depth sort that follows must start from zero
-    for (uint32_t z = (uint32_t)i; z < bo.sort_sup_words; z += gridDim.x * 256u) bo.sort_sup[z] = 0u;
-  uint32_t dkey = 0u;
-  float sh[K];
-  if constexpr (RAW) {   // 180-B high_shs rows cannot be dwordx4-loaded per lane: the workgroup's span through LDS
-    if constexpr (KH > 0) {
-      if constexpr (KH % 2 == 1) stage_span_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
-      else stage_rows_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
-    }
-  }
-  float4 r[3] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-  float jw[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  uint4 crec = make_uint4(0u, 0u, 0u, 0u);
-  if (i < n) {
-    const f3 pw = ld3(pws + 3 * (size_t)i);
-#if EGS_PRE_EARLY_LOADS
-    // (requested with the position, not after the colour: one dependent round trip less per row)
-    float4 q_in = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
-    f3 sc_in = ld3(scales + 3 * (size_t)i);
-    const float alpha_in = (rec || bo.br) ? alphas[i] : 0.f;
-#endif
-    float col[3];
-    {  // colour has no depth test in the reference (kernel.cu:619-725)
-      if constexpr (RAW) {
-        sh[0] = shs[3 * (size_t)i]; sh[1] = shs[3 * (size_t)i + 1]; sh[2] = shs[3 * (size_t)i + 2];
-      } else {  // direct dwordx4 row loads: staging them through LDS measured 10 % slower here
-        load_sh_row<K>(shs + (size_t)K * i, sh);
-      }
-      const ShDir<NC> d = sh_basis_f<NC>(pw, twc);
-#if EGS_SH_FUSED_JAC_PRE
-      if constexpr (JW) sh_color_and_jac_dpw<NC>(d, sh, col, jw);
-      else sh_color_f<NC>(d, sh, col);
-      if (colors) st3(colors + 3 * (size_t)i, {col[0], col[1], col[2]});
-#else
-      sh_color_f<NC>(d, sh, col);
-      if (colors) st3(colors + 3 * (size_t)i, {col[0], col[1], col[2]});
-      if constexpr (JW) sh_jac_dpw<NC>(d, sh, jw);
-#endif
-    }
-    const Proj P = project_f(pw, Rcw, tcw, pp.fx, pp.fy, pp.cx, pp.cy);
-    float u0 = 0.f, u1 = 0.f, depth = EGS_BAD_MARKER, ci[3] = {0.f, 0.f, 0.f};
-    int rx = 0, ry = 0;
-    if (!(pp.near_cull && P.pc.z < EGS_MIN_DEPTH)) {
-      u0 = P.u0; u1 = P.u1; depth = P.pc.z;
-#if EGS_PRE_EARLY_LOADS
-      float4 q = q_in;
-      f3 sc = sc_in;
-#else
-      float4 q = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
-      f3 sc = ld3(scales + 3 * (size_t)i);
-#endif
-      if constexpr (RAW) { float nrm; q = act_rot(q, nrm); sc = act_scale(sc); }
-      const Cov3 c3 = cov3d_f(q, sc);
-      const Cov2 c2 = cov2d_f(c3.c, P.pc, Rcw, pp.fx, pp.fy, pp.limx, pp.limy, pp.clamp_fov);
-      const float det_inv = inv_cov2d_f(c2.c, pp.det_eps, ci);
-      if (pp.nan_cull && isnan(det_inv)) {
-        depth = EGS_BAD_MARKER; ci[0] = 0.f; ci[1] = 0.f; ci[2] = 0.f;
-      } else {
-        radius_f(c2.c, pp.radius_mode, rx, ry);
-      }
-    }
-#if EGS_PRE_EARLY_LOADS
-    const float alpha_act = (rec || bo.br) ? (RAW ? act_alpha(alpha_in) : alpha_in) : 0.f;
-#else
-    const float alpha_act = (rec || bo.br) ? (RAW ? act_alpha(alphas[i]) : alphas[i]) : 0.f;
-#endif
-    if (bo.br) {  // getRects + depth key of the binning stage, straight from registers (no k_bin_count pass)
-      uint4 rect;
-      bool cull;
-      const uint32_t cnt = bin_count_one(bp, u0, u1, (float)rx, (float)ry, depth, rect, dkey, cull);
-      if (cull) { depth = EGS_BAD_MARKER; rx = 0; ry = 0; }  // in-place contract of splat (kernel.cu:114-119)
-      bo.ids[i] = (uint32_t)i;
-      // the footprint record of the binning stage and the number of tiles the Gaussian is emitted for: its rect
-      // (the reference's lists) or, bp.cull_lists, the tiles its footprint alpha' >= alpha_skip can reach
-      const BinRec brec = make_binrec(u0, u1, ci[0], ci[1], ci[2], alpha_act, pp.alpha_skip, bp.cull_lists != 0,
-                                      rect, cnt);
-      if (cnt) {
-        const uint32_t w = brec.wh & 0xFFFFu, h = brec.wh >> 16;
-        if (w <= 4u && h <= 4u) {          // the blocks the footprint reaches, as a bitmap: emission is bit arithmetic
-          const unsigned long long bits = foot_bitmap(brec);
-          crec = make_uint4(brec.xy, brec.wh, (uint32_t)bits, (uint32_t)(bits >> 32));
-        } else {                           // a bigger rect
-          const bool walk = brec.m < __int_as_float(0x7f800000);
-          if (walk && w <= 8u && h <= 8u) {   // its TILES as a bitmap; k_bin_emit evaluates the slabs of one tile
-            const unsigned long long bits = foot_tilemap(brec);
-            crec = make_uint4(brec.xy, brec.wh | EGS_CR_TILEMAP, (uint32_t)bits, (uint32_t)(bits >> 32));
-          } else {                            // counted here, walked row by row by k_bin_emit
-            crec = make_uint4(brec.xy, brec.wh | EGS_CR_BIG, walk ? foot_count(brec) : cnt, walk ? 1u : 0u);
-          }
-          if (walk) {
-            float4* o = reinterpret_cast<float4*>(bo.br + i);
-            o[0] = make_float4(brec.ux, brec.uy, brec.A, brec.Bh);
-            o[1] = make_float4(brec.C, brec.m, __uint_as_float(brec.xy), __uint_as_float(brec.wh));
-          }
-        }
-      }
-      bo.dkeys[i] = dkey;
-    }
-    // us / cinv2ds / colors / areas are only needed by callers that go on with the seven-op surface; the
-    // fused path draws from the packed records alone and passes NULL (40 B/Gaussian less to write)
-    if (us) { us[2 * (size_t)i] = u0; us[2 * (size_t)i + 1] = u1; }
-    depths[i] = depth;
-    if (visible) visible[i] = depth > 0.2f;  // the mask GSFunction returns (gsmodel.py:50)
-    if (cinv2ds) st3(cinv2ds + 3 * (size_t)i, {ci[0], ci[1], ci[2]});
-    if (areas) { areas[2 * (size_t)i] = rx; areas[2 * (size_t)i + 1] = ry; }
-    // the packed 2D record of the draw kernels, straight from registers (no k_pack_records pass)
-    if (rec)
-      make_record(u0, u1, ci[0], ci[1], ci[2], alpha_act, col[0], col[1], col[2], rx, ry,
-                  pp.W, pp.H, pp.footprint, pp.alpha_skip, r);
-  }
-  if (bo.br) {
-    __syncthreads();   // (RAW: every wave is done with the rows staged in)
-    block_max_key(dkey, bo.maxkey, reinterpret_cast<uint32_t*>(stage));
-    if (i < n) bo.cr[i] = crec;     // (16 B per lane, consecutive lanes: full lines)
-  }
-  // 48-B records leave as full lines (lane-strided 16-B pieces cost 3x the write requests)
-  if (rec) stage_rows_out<12>(reinterpret_cast<const float*>(r), reinterpret_cast<float*>(rec), n, blockIdx.x * 256, stage);
-  if constexpr (JW) rows_out<9>(jw, dcolor_dpws, n, blockIdx.x * 256, stage);
+  constexpr bool AA = false;
+#include "egs_preprocess_fwd.inc"
+}
+// the AA flavour (anti-aliased rendering): every Gaussian is binned and drawn with opacity alpha comp
+template <int NC, bool RAW, bool JW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (JW ? EGS_PRE_JW_WAVES : 8), 8))) void k_preprocess_fwd_aa(int n, PreParams pp, const float* __restrict__ pws,
+                                                        const float* __restrict__ rots,
+                                                        const float* __restrict__ scales,
+                                                        const float* __restrict__ shs,
+                                                        const float* __restrict__ shs_high,
+                                                        const float* __restrict__ alphas,
+                                                        const float* __restrict__ Rcw,
+                                                        const float* __restrict__ tcw,
+                                                        const float* __restrict__ twc,
+                                                        float* __restrict__ us, float* __restrict__ depths,
+                                                        float* __restrict__ cinv2ds,
+                                                        float* __restrict__ colors,
+                                                        int32_t* __restrict__ areas,
+                                                        float4* __restrict__ rec, BinParams bp, BinCountOut bo,
+                                                        uint8_t* __restrict__ visible,
+                                                        float* __restrict__ dcolor_dpws) {
+  constexpr bool AA = true;
+#include "egs_preprocess_fwd.inc"
 }
 
 // backward.md eq (3)(4)(5)(7) == gsmodel.py:71-85 with every Jacobian re-derived in
@@ -732,7 +628,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
     float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
     float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode) {
-  constexpr bool EXTRA = false, POSE = false;
+  constexpr bool EXTRA = false, POSE = false, AA = false;
   float* const pose_ws = nullptr;   // (POSE only)
 #include "egs_preprocess_bwd.inc"
 }
@@ -746,7 +642,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_extra(
     const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
     float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
     float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode) {
-  constexpr bool EXTRA = true, POSE = false;
+  constexpr bool EXTRA = true, POSE = false, AA = false;
   float* const pose_ws = nullptr;   // (POSE only)
 #include "egs_preprocess_bwd.inc"
 }
@@ -761,7 +657,21 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd_pose(
     const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
     float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
     float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode, float* __restrict__ pose_ws) {
-  constexpr bool POSE = true;
+  constexpr bool POSE = true, AA = false;
+#include "egs_preprocess_bwd.inc"
+}
+// the AA flavour of all three (anti-aliased rendering): the records were drawn with opacity alpha comp;
+// reads alphas[i] also without RAW (4 B per Gaussian).  pose_ws: POSE only
+template <int NC, bool RAW, bool JW, bool EXTRA, bool POSE>
+__global__ __launch_bounds__(256) void k_preprocess_bwd_aa(
+    int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
+    const float* __restrict__ scales, const float* __restrict__ shs, const float* __restrict__ shs_high,
+    const float* __restrict__ alphas, const float* __restrict__ Rcw,
+    const float* __restrict__ tcw, const float* __restrict__ twc, const float* __restrict__ depths,
+    const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
+    float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
+    float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode, float* __restrict__ pose_ws) {
+  constexpr bool AA = true;
 #include "egs_preprocess_bwd.inc"
 }
 
@@ -997,7 +907,7 @@ static PreParams make_pre_params(const EgsPolicy* pol, float fx, float fy, float
   return pp;
 }
 
-static int fused_forward_impl(bool raw, int n, int sh_dim, const float* pws, const float* rots, const float* scales,
+static int fused_forward_impl(bool raw, bool aa, int n, int sh_dim, const float* pws, const float* rots, const float* scales,
                               const float* shs, const float* shs_high, const float* alphas, const float* Rcw,
                               const float* tcw, const float* twc, float fx, float fy, float cx, float cy, int width,
                               int height, const EgsPolicy* pol, float* us, float* depths, float* cinv2ds,
@@ -1018,6 +928,7 @@ static int fused_forward_impl(bool raw, int n, int sh_dim, const float* pws, con
   EGS_CHECK_ARG(pws && rots && scales && shs && Rcw && tcw && twc && depths);
   EGS_CHECK_ARG(rec || (us && cinv2ds && colors && areas));   // something must carry the 2D Gaussians on
   EGS_CHECK_ARG(!rec || alphas);
+  EGS_CHECK_ARG(!aa || rec);   // the compensated opacity only exists inside the records
   EGS_CHECK_ARG(ws_bin);
   EGS_CHECK_ARG(((uintptr_t)rots & 15) == 0);
   if (raw) EGS_CHECK_ARG(sh_dim == 3 || (shs_high && ((uintptr_t)shs_high & 15) == 0));
@@ -1032,16 +943,15 @@ static int fused_forward_impl(bool raw, int n, int sh_dim, const float* pws, con
   dim3 g(div_up(n, 256)), b(256);
   // EGS_PRE_LDS_PAD (bytes of dynamic LDS, experiment knob): caps the resident workgroups per CU of this kernel
   static const size_t lds_pad = [] { const char* e = getenv("EGS_PRE_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }();
+#define EGS_PRE_K(KERN, NC, RAW, JW)                                                                            \
+  EGS_LAUNCH_LDS(#KERN, (KERN<NC, RAW, JW>), g, b, lds_pad, s, n, pp, pws, rots, scales, shs, shs_high, alphas, Rcw, \
+                 tcw, twc, us, depths, cinv2ds, colors, areas, (float4*)rec, bp, bo, visible, dcolor_dpws)
 #define EGS_PRE(NC, RAW)                                                                                        \
   do {                                                                                                          \
-    if (dcolor_dpws)                                                                                            \
-      EGS_LAUNCH_LDS("k_preprocess_fwd", (k_preprocess_fwd<NC, RAW, true>), g, b, lds_pad, s, n, pp, pws, rots, scales, shs, \
-                 shs_high, alphas, Rcw, tcw, twc, us, depths, cinv2ds, colors, areas, (float4*)rec, bp, bo,     \
-                 visible, dcolor_dpws);                                                                         \
-    else                                                                                                        \
-      EGS_LAUNCH_LDS("k_preprocess_fwd", (k_preprocess_fwd<NC, RAW, false>), g, b, lds_pad, s, n, pp, pws, rots, scales, shs, \
-                 shs_high, alphas, Rcw, tcw, twc, us, depths, cinv2ds, colors, areas, (float4*)rec, bp, bo,     \
-                 visible, dcolor_dpws);                                                                         \
+    if (aa && dcolor_dpws) EGS_PRE_K(k_preprocess_fwd_aa, NC, RAW, true);                                      \
+    else if (aa) EGS_PRE_K(k_preprocess_fwd_aa, NC, RAW, false);                                               \
+    else if (dcolor_dpws) EGS_PRE_K(k_preprocess_fwd, NC, RAW, true);                                          \
+    else EGS_PRE_K(k_preprocess_fwd, NC, RAW, false);                                                          \
   } while (0)
   switch (sh_dim * 2 + (raw ? 1 : 0)) {
     case 6: EGS_PRE(1, false); break;
@@ -1054,6 +964,7 @@ static int fused_forward_impl(bool raw, int n, int sh_dim, const float* pws, con
     default: EGS_PRE(16, true); break;
   }
 #undef EGS_PRE
+#undef EGS_PRE_K
   EGS_LAUNCH_OK();
   // the kernel above already did getRects + depth keys (k_bin_count of egs_splat_bin)
   return splat_bin_after_count(n, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, stream, host_totals);
@@ -1066,8 +977,8 @@ extern "C" int egs_fused_forward(int n, int sh_dim, const float* pws, const floa
                                  int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws, int cull_lists,
                                  int key_bits_hint, void* ws_bin, size_t ws_bin_bytes, uint32_t* total_patches,
                                  uint32_t* host_totals, void* stream) {
-  return fused_forward_impl(false, n, sh_dim, pws, rots, scales, shs, nullptr, alphas, Rcw, tcw, twc, fx, fy, cx, cy,
-                            width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible, dcolor_dpws,
+  return fused_forward_impl(false, false, n, sh_dim, pws, rots, scales, shs, nullptr, alphas, Rcw, tcw, twc, fx, fy, cx,
+                            cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible, dcolor_dpws,
                             cull_lists, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, host_totals, stream);
 }
 
@@ -1080,8 +991,38 @@ extern "C" int egs_fused_forward_raw(int n, int sh_dim, const float* pws, const 
                                      int cull_lists, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
                                      uint32_t* total_patches, uint32_t* host_totals, void* stream) {
   EGS_CHECK_ARG(n == 0 || (rec && alphas_raw));  // the activated alpha only exists inside the records
-  return fused_forward_impl(true, n, sh_dim, pws, rots_raw, scales_raw, low_shs, high_shs, alphas_raw, Rcw, tcw, twc,
-                            fx, fy, cx, cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible,
+  return fused_forward_impl(true, false, n, sh_dim, pws, rots_raw, scales_raw, low_shs, high_shs, alphas_raw, Rcw, tcw,
+                            twc, fx, fy, cx, cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible,
+                            dcolor_dpws, cull_lists, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, host_totals,
+                            stream);
+}
+
+// anti-aliased rendering (include/egs_hip.h): egs_fused_forward(_raw) with the opacity compensation of the 2D filter;
+// the same arguments, `rec` required
+extern "C" int egs_fused_forward_aa(int n, int sh_dim, const float* pws, const float* rots, const float* scales,
+                                    const float* shs, const float* alphas, const float* Rcw, const float* tcw,
+                                    const float* twc, float fx, float fy, float cx, float cy, int width, int height,
+                                    const EgsPolicy* pol, float* us, float* depths, float* cinv2ds, float* colors,
+                                    int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws, int cull_lists,
+                                    int key_bits_hint, void* ws_bin, size_t ws_bin_bytes, uint32_t* total_patches,
+                                    uint32_t* host_totals, void* stream) {
+  EGS_CHECK_ARG(rec);
+  return fused_forward_impl(false, true, n, sh_dim, pws, rots, scales, shs, nullptr, alphas, Rcw, tcw, twc, fx, fy, cx,
+                            cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible, dcolor_dpws,
+                            cull_lists, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, host_totals, stream);
+}
+
+extern "C" int egs_fused_forward_raw_aa(int n, int sh_dim, const float* pws, const float* rots_raw,
+                                        const float* scales_raw, const float* low_shs, const float* high_shs,
+                                        const float* alphas_raw, const float* Rcw, const float* tcw, const float* twc,
+                                        float fx, float fy, float cx, float cy, int width, int height,
+                                        const EgsPolicy* pol, float* us, float* depths, float* cinv2ds, float* colors,
+                                        int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws,
+                                        int cull_lists, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
+                                        uint32_t* total_patches, uint32_t* host_totals, void* stream) {
+  EGS_CHECK_ARG(rec && (n == 0 || alphas_raw));
+  return fused_forward_impl(true, true, n, sh_dim, pws, rots_raw, scales_raw, low_shs, high_shs, alphas_raw, Rcw, tcw,
+                            twc, fx, fy, cx, cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible,
                             dcolor_dpws, cull_lists, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, host_totals,
                             stream);
 }
@@ -1115,7 +1056,10 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
   // kernel `mode`: bit 0 accumulate, bit 1 factored SH gradient (dloss_dshs = dL/dcolour [N][3])
   const int accum = ((phase & EGS_BWD_ACCUMULATE) ? 1 : 0) | ((phase & EGS_BWD_FACTORED_SH) ? 2 : 0);
   const bool factored = (phase & EGS_BWD_FACTORED_SH) != 0;
-  phase &= ~(EGS_BWD_KEEP_FORWARD_ORDER | EGS_BWD_CULLED_LISTS | EGS_BWD_ACCUMULATE | EGS_BWD_FACTORED_SH);
+  // the render was anti-aliased (egs_fused_forward(_raw)_aa): the chain rule takes the AA instances
+  const bool aa = (phase & EGS_BWD_ANTIALIASED) != 0;
+  phase &= ~(EGS_BWD_KEEP_FORWARD_ORDER | EGS_BWD_CULLED_LISTS | EGS_BWD_ACCUMULATE | EGS_BWD_FACTORED_SH |
+             EGS_BWD_ANTIALIASED);
   EGS_CHECK_ARG(phase >= 0 && phase <= 2);
   // pose (nullable): the camera gradient needs every row in one launch (k_pose_reduce sums all partial rows)
   if (pose) {
@@ -1167,9 +1111,21 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
   float* pose_ws = pose ? (float*)pose->ws : nullptr;
 #define EGS_PREB_POSE(NC, RAW, JW, EX) \
   EGS_LAUNCH("k_preprocess_bwd_pose", (k_preprocess_bwd_pose<NC, RAW, JW, EX>), g, b, s, EGS_PREB_ARGS(NC, RAW), pose_ws)
+#define EGS_PREB_AA(NC, RAW, JW, EX, PO) \
+  EGS_LAUNCH("k_preprocess_bwd_aa", (k_preprocess_bwd_aa<NC, RAW, JW, EX, PO>), g, b, s, EGS_PREB_ARGS(NC, RAW), pose_ws)
+#define EGS_PREB_AA_JW(NC, RAW, EX, PO)                                                                           \
+  do {                                                                                                            \
+    if (dcolor_dpws) EGS_PREB_AA(NC, RAW, true, EX, PO);                                                          \
+    else EGS_PREB_AA(NC, RAW, false, EX, PO);                                                                     \
+  } while (0)
 #define EGS_PREB(NC, RAW)                                                                                         \
   do {                                                                                                            \
-    if (pose) {                                                                                                   \
+    if (aa) {                                                                                                     \
+      if (pose && extras) EGS_PREB_AA_JW(NC, RAW, true, true);                                                    \
+      else if (pose) EGS_PREB_AA_JW(NC, RAW, false, true);                                                        \
+      else if (extras) EGS_PREB_AA_JW(NC, RAW, true, false);                                                      \
+      else EGS_PREB_AA_JW(NC, RAW, false, false);                                                                 \
+    } else if (pose) {                                                                                            \
       if (extras && dcolor_dpws) EGS_PREB_POSE(NC, RAW, true, true);                                              \
       else if (extras) EGS_PREB_POSE(NC, RAW, false, true);                                                       \
       else if (dcolor_dpws) EGS_PREB_POSE(NC, RAW, true, false);                                                  \
@@ -1192,6 +1148,8 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
     default: EGS_PREB(16, true); break;
   }
 #undef EGS_PREB
+#undef EGS_PREB_AA_JW
+#undef EGS_PREB_AA
 #undef EGS_PREB_POSE
 #undef EGS_PREB_ARGS
   EGS_LAUNCH_OK();

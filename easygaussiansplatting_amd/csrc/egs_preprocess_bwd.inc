@@ -1,6 +1,9 @@
-// Body of the chain-rule kernels k_preprocess_bwd (EXTRA = false), k_preprocess_bwd_extra (EXTRA = true) and
-// k_preprocess_bwd_pose (POSE = true), egs_preprocess.hip.  Included inside the kernel, as egs_draw_fwd.inc: the
-// parameters, NC, RAW, JW, EXTRA and POSE come from there.
+// Body of the chain-rule kernels k_preprocess_bwd (EXTRA = false), k_preprocess_bwd_extra (EXTRA = true),
+// k_preprocess_bwd_pose (POSE = true) and k_preprocess_bwd_aa (AA = true, either EXTRA, either POSE),
+// egs_preprocess.hip.  Included inside the kernel, as egs_draw_fwd.inc: the parameters, NC, RAW, JW, EXTRA, POSE and AA
+// come from there.
+  // AA (anti-aliased rendering, DESIGN §3.9): the forward drew opacity alpha comp, so ga.x = dL/d(alpha comp):
+  // dL/dalpha = ga.x comp and dL/dcov2d gains ga.x alpha dcomp/dcov2d before it feeds J3, Jp and the pose W term
   // dcolor_dpws (nullable): [N][9] left by k_preprocess_fwd; with it this kernel never reads the SH coefficients
   // mode bit 1 (EGS_BWD_FACTORED_SH): the SH gradient stays in its factored form -- eq (5) is an outer product
   // dL/dcolour (x) basis, so dL_dsh receives the THREE floats dL/dcolour per Gaussian ([N][3], always written, never
@@ -48,8 +51,8 @@
     f3 s = ld3(scales + 3 * (size_t)i);
     float W[9];
     if constexpr (JW) load_row<9>(dcolor_dpws + 9 * (size_t)i, W);
-    float al_raw = 0.f;
-    if constexpr (RAW) al_raw = alphas[i];
+    float al_raw = 0.f;   // (AA without RAW: the activated alpha)
+    if constexpr (RAW || AA) al_raw = alphas[i];
     float4 o_rot = make_float4(0.f, 0.f, 0.f, 0.f);
     f3 o_scale = {0.f, 0.f, 0.f}, o_pw = {0.f, 0.f, 0.f};
     float o_alpha = 0.f;
@@ -62,7 +65,9 @@
     const f3 gcol = {ga.y, ga.z, ga.w};
     const float gu0 = gb.x, gu1 = gb.y;
     const f3 gci = {gb.z, gb.w, gc.x};
-    if constexpr (RAW) {
+    if constexpr (AA) {
+      // (stored below, once comp is known; culled: comp = 0)
+    } else if constexpr (RAW) {
       const float al = act_alpha(al_raw);
       dL_dalpha[i] = ga.x * al * (1.f - al) + o_alpha;   // sigmoid'
     } else {
@@ -70,6 +75,7 @@
     }
     dL_du[2 * (size_t)i] = gu0; dL_du[2 * (size_t)i + 1] = gu1;
     if (pp.near_cull && depth_i < EGS_MIN_DEPTH) {  // culled: never drawn, all gradients are zero
+      if constexpr (AA) dL_dalpha[i] = o_alpha;
       if (!accum) {
         st3(dL_dpw + 3 * (size_t)i, {0.f, 0.f, 0.f});
         st3(dL_dscale + 3 * (size_t)i, {0.f, 0.f, 0.f});
@@ -86,9 +92,15 @@
       float Ji[9];
       inv_cov2d_jac(c2.c, det_inv, Ji);
       // dL/dcov2d = dL/dcinv2d @ J  (row vector times 3x3)
-      const float g2[3] = {gci.x * Ji[0] + gci.y * Ji[3] + gci.z * Ji[6],
-                           gci.x * Ji[1] + gci.y * Ji[4] + gci.z * Ji[7],
-                           gci.x * Ji[2] + gci.y * Ji[5] + gci.z * Ji[8]};
+      float g2[3] = {gci.x * Ji[0] + gci.y * Ji[3] + gci.z * Ji[6],
+                     gci.x * Ji[1] + gci.y * Ji[4] + gci.z * Ji[7],
+                     gci.x * Ji[2] + gci.y * Ji[5] + gci.z * Ji[8]};
+      if constexpr (AA) {
+        const float al = RAW ? act_alpha(al_raw) : al_raw;
+        const float comp = aa_comp_vjp(c2.c, ga.x * al, g2);   // g2 += ga.x alpha dcomp/dcov2d
+        const float gal = ga.x * comp;
+        dL_dalpha[i] = (RAW ? gal * al * (1.f - al) : gal) + o_alpha;
+      }
       float J3[18], Jp[9];
       cov2d_jac(c2, P.pc.z, Rcw, pp.fx, pp.fy, J3, Jp);
       float g3[6];

@@ -59,6 +59,9 @@ class RenderOptions:
     depth: bool = False             # also return the accumulated depth map
     alpha: bool = False             # also return the accumulated opacity map
     background: tuple = None        # (r, g, b) floats: the image gets T_final * bg added (not differentiable)
+    # anti-aliased rendering (fused path only): the Mip-Splatting 2D filter -- the +0.3 px^2 dilation stays
+    # and every Gaussian is drawn with opacity alpha sqrt(det(Sigma) / det(Sigma + 0.3 I)); differentiable
+    antialiased: bool = False
 
     def __post_init__(self):
         if self.mode not in ("fused", "ops"):
@@ -74,6 +77,12 @@ class RenderOptions:
                     isinstance(self.background, (str, bytes)):
                 raise ValueError("RenderOptions.background must be three finite floats, got %r" % (self.background,))
             object.__setattr__(self, "background", bg)
+        if not isinstance(self.antialiased, (bool, int)) or self.antialiased not in (0, 1):
+            raise ValueError("RenderOptions.antialiased must be a bool, got %r" % (self.antialiased,))
+        object.__setattr__(self, "antialiased", bool(self.antialiased))
+        if self.mode == "ops" and self.antialiased:
+            raise ValueError("RenderOptions: antialiased needs mode='fused' (the seven-op structure mirrors the reference, "
+                             "which has no opacity compensation)")
         if self.mode == "ops" and self.has_extras():
             raise ValueError("RenderOptions: depth / alpha / background need mode='fused' (the seven-op structure mirrors "
                              "the reference, which renders the image only)")
@@ -126,11 +135,12 @@ class GSFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.extras = None if opts is None else opts.extras()
         if ctx.mode == "fused":
+            aa = opts is not None and opts.antialiased
             if ctx.extras is not None:
                 image, mask, state, depth, alpha = _fused.forward(pws, shs, alphas, scales, rots, cam, need_grad=True,
-                                                                  extras=ctx.extras)
+                                                                  extras=ctx.extras, antialiased=aa)
             else:
-                image, mask, state = _fused.forward(pws, shs, alphas, scales, rots, cam, need_grad=True)
+                image, mask, state = _fused.forward(pws, shs, alphas, scales, rots, cam, need_grad=True, antialiased=aa)
             ctx.cam = cam
             ctx.state = state
             ctx.save_for_backward(pws, shs, alphas, scales, rots)
@@ -215,7 +225,7 @@ class GSRawFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.extras = None if opts is None else opts.extras()
         res = _fused.forward(pws, low_shs, alphas_raw, scales_raw, rots_raw, cam, high_shs=high_shs, need_grad=True,
-                             extras=ctx.extras)
+                             extras=ctx.extras, antialiased=opts is not None and opts.antialiased)
         image, mask, state = res[:3]
         ctx.cam = cam
         ctx.state = state
@@ -292,7 +302,8 @@ class GSPoseFunction(torch.autograd.Function):
     def forward(ctx, pws, shs, alphas, scales, rots, us, Rcw, tcw, cam, opts=None):
         pcam = _pose_setup(ctx, opts, Rcw, tcw, cam, pws)
         ctx.n_inputs = 10
-        res = _fused.forward(pws, shs, alphas, scales, rots, pcam, need_grad=True, extras=ctx.extras)
+        res = _fused.forward(pws, shs, alphas, scales, rots, pcam, need_grad=True, extras=ctx.extras,
+                             antialiased=opts is not None and opts.antialiased)
         image, mask, state = res[:3]
         ctx.cam = pcam
         ctx.state = state
@@ -335,7 +346,7 @@ class GSRawPoseFunction(torch.autograd.Function):
         pcam = _pose_setup(ctx, opts, Rcw, tcw, cam, pws)
         ctx.n_inputs = 11
         res = _fused.forward(pws, low_shs, alphas_raw, scales_raw, rots_raw, pcam, high_shs=high_shs, need_grad=True,
-                             extras=ctx.extras)
+                             extras=ctx.extras, antialiased=opts is not None and opts.antialiased)
         image, mask, state = res[:3]
         ctx.cam = pcam
         ctx.state = state

@@ -47,6 +47,7 @@ SEG_SPECULATE = os.environ.get("EGS_SEG_SPECULATE", "auto")
 CULLED_LISTS = 32         # include/egs_hip.h EGS_BWD_CULLED_LISTS
 ACCUMULATE = 64           # include/egs_hip.h EGS_BWD_ACCUMULATE
 FACTORED_SH = 128         # include/egs_hip.h EGS_BWD_FACTORED_SH
+ANTIALIASED = 256         # include/egs_hip.h EGS_BWD_ANTIALIASED
 GSID_MASK = 0x0FFFFFFF    # csrc/egs_common.h EGS_GSID_MASK
 MAILBOX_SLOTS = 64
 HINT_SLOTS = 16           # problem sizes that keep a hint slot (longest list / longest walk of their recent renders)
@@ -57,7 +58,7 @@ class FusedState:
     patch count has not been validated yet (deferred validation, see ``deferred``)."""
     __slots__ = ("us", "depths", "cinv2ds", "colors", "areas", "rec", "contrib", "final_tau", "ranges", "gsid",
                  "order", "order_by_work", "gpack", "dcw", "culled", "width", "height", "ticket", "_patches", "_keep",
-                 "seg", "extras")
+                 "seg", "extras", "antialiased")
 
     def patch_count(self) -> int:
         """P of this render (waits for its read-back if it has not been looked at yet)."""
@@ -380,14 +381,17 @@ def _split_sh(low_shs, high_shs, n):
     return low, high, K
 
 
-def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False, extras=None):
+def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False, extras=None, antialiased=False):
     """-> (image[3,H,W], mask[N] bool, state); with ``extras`` (``Extras``) -> (image, mask, state, depth, alpha), the
     two maps float32 [1,H,W] or None where not requested.  ``cam`` carries Rcw/tcw/twc device
     tensors and fx, fy, cx, cy, width, height (reference gausplat_dataset.py:14-26).
     ``need_grad``: a backward pass will follow (the draw kernel then also zeroes its gradient records).
     With ``high_shs`` the inputs are the RAW training tensors (``shs`` = low_shs, ``alphas`` =
     alphas_raw, ``scales`` = scales_raw, ``rots`` = rots_raw) and the activations of
-    gsplat/utils.py:121-150 run inside the kernel (egs_fused_forward_raw)."""
+    gsplat/utils.py:121-150 run inside the kernel (egs_fused_forward_raw).
+    ``antialiased``: the opacity compensation of the 2D filter (egs_fused_forward(_raw)_aa) -- every
+    Gaussian is binned and drawn with opacity alpha sqrt(det(Sigma) / det(Sigma + 0.3 I)); the state records it and
+    ``backward`` follows."""
     raw = high_shs is not None
     pws = _chk(pws, "pws", torch.float32, (None, 3))
     n = pws.shape[0]
@@ -413,6 +417,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
     S = FusedState()
     S.width, S.height = W, H
     S.ticket, S._patches, S._keep, S.seg, S.extras = None, None, None, None, None
+    S.antialiased = bool(antialiased)
     # the draw kernels (forward and backward) work from the packed records alone: us / cinv2ds / colors /
     # areas are not materialised
     S.us = S.cinv2ds = S.colors = S.areas = None
@@ -475,10 +480,12 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
                                               None if (redo and walk_word is not None) else seg_hint, _ptr(walk_word), None, st))
 
     if raw:
-        enqueue_bin = lambda hint, total: _lib.check(lib.egs_fused_forward_raw(
+        fwd = lib.egs_fused_forward_raw_aa if S.antialiased else lib.egs_fused_forward_raw
+        enqueue_bin = lambda hint, total: _lib.check(fwd(
             n, K, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), _ptr(high_shs), *tail(hint, total)))
     else:
-        enqueue_bin = lambda hint, total: _lib.check(lib.egs_fused_forward(
+        fwd = lib.egs_fused_forward_aa if S.antialiased else lib.egs_fused_forward
+        enqueue_bin = lambda hint, total: _lib.check(fwd(
             n, K, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), *tail(hint, total)))
 
     ctx = _ctx(dev)
@@ -736,7 +743,8 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     background of the render is part of the gradient whatever they are.
     ``pose`` = (Rcw [3,3], tcw [3]), float32 on the device: the camera of the forward call (``cam.twc`` must be
     -Rcw^T tcw), whose gradient is also formed -> the usual tuple followed by (dloss_dRcw [3,3], dloss_dtcw [3]).  The
-    pose gradient belongs to this view: always written, never added to ``accumulate``.  Excludes ``exchange``."""
+    pose gradient belongs to this view: always written, never added to ``accumulate``.  Excludes ``exchange``.
+    An anti-aliased render (``forward(..., antialiased=True)``, recorded in ``S``) takes the AA chain rule."""
     raw = high_shs is not None
     pws = _chk(pws, "pws", torch.float32, (None, 3))
     n = pws.shape[0]
@@ -851,6 +859,8 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
         keep |= ACCUMULATE            # the outputs hold earlier views' gradients: add to them
     if sh_sink is not None:
         keep |= FACTORED_SH
+    if getattr(S, "antialiased", False):
+        keep |= ANTIALIASED           # (from the forward's state: the backward pass can never mismatch it)
     if hook is not None and sh_sink is not None:
         raise RuntimeError("fused.backward: sh_sink and an attached ChunkedExchange exclude each other")
     chunks = hook.chunks if hook is not None else 1
@@ -869,7 +879,7 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
         launch(1 | keep, 0, 0)
         for b in range(0, n, rows):
             c = min(rows, n - b)
-            launch(2 | (keep & (ACCUMULATE | FACTORED_SH)), b, c)
+            launch(2 | (keep & (ACCUMULATE | FACTORED_SH | ANTIALIASED)), b, c)
             hook.on_chunk([p[b:b + c] for p in parts])
     tail = () if pg is None else (dRcw, dtcw)
     if sh_sink is not None:

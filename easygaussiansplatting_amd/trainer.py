@@ -76,13 +76,17 @@ def make_optimizer(p, fused=True):
 class Trainer:
     def __init__(self, scene, cameras: Sequence, gt_images: Sequence[torch.Tensor], max_steps: int,
                  scene_size: float = 1.0, device="cuda", fused_adam: bool = True, seed: int = 0,
-                 fused_activations: bool = True, view_streams: int = 4, factored_sh: bool = True, mode: str = "fused"):
+                 fused_activations: bool = True, view_streams: int = 4, factored_sh: bool = True, mode: str = "fused",
+                 antialiased: bool = False):
         self.device = device
         # how THIS trainer's renders are evaluated (function.RenderOptions.mode; "ops" needs fused_activations=False):
         # carried by every call, never by a process-wide switch -- two trainers in one process may differ
         self.mode = mode
         if mode != "fused" and fused_activations:
             raise ValueError("Trainer(mode=%r) needs fused_activations=False (GSRawFunction is the fused path)" % (mode,))
+        # anti-aliased training (RenderOptions.antialiased; fused path only): every render of a step
+        self.antialiased = bool(antialiased)
+        RenderOptions(mode=mode, antialiased=self.antialiased)        # (raises ValueError for mode="ops")
         # a rank's views of a step go round-robin to this many HIP streams (dist_views.ViewStreams); 1 = one after
         # the other on the caller's stream
         self.view_streams = max(1, int(view_streams))
@@ -197,7 +201,7 @@ class Trainer:
             fx = self._fx
         # every render of the step carries its own options (no process-wide switch): gradients of further views are
         # added inside the chain-rule kernel, the SH gradient goes to this trainer's own FactoredShGrad
-        opts = RenderOptions(mode=self.mode, accumulate=True, sh_sink=fx)
+        opts = RenderOptions(mode=self.mode, accumulate=True, sh_sink=fx, antialiased=self.antialiased)
         if fx is not None:     # (rows allocated here, on the caller's stream, before the views fork onto their lanes)
             fx.begin_step(self.params["pws"].shape[0], self.params["pws"].device)
         with _fused.deferred() as d:

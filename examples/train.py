@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=100)
     ap.add_argument("--resize", type=float, default=1.0)
     ap.add_argument("--out", default="data")
+    ap.add_argument("--antialiased", action="store_true",
+                    help="anti-aliased rendering: opacity compensation of the 2D filter (DESIGN §3.9)")
     a = ap.parse_args()
 
     import torch
@@ -44,7 +46,7 @@ def main():
                     None)
     views_per_step = world
     steps = (len(ds) // views_per_step) * a.epochs
-    tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size)
+    tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size, antialiased=a.antialiased)
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]

@@ -464,6 +464,11 @@ size_t egs_fused_backward_ws_bytes(int n);
  * a data-parallel host all-gathers 12 bytes per Gaussian and VIEW instead of all-reducing 4 sh_dim per Gaussian
  * (192 of the 236 bytes of SURVEY 8e's exchange at degree 3). */
 #define EGS_BWD_FACTORED_SH 128
+/* OR-ed into `phase` of every egs_fused_backward* entry point (plain, _raw, _ex, _raw_ex, _pose, _raw_pose): the render
+ * was anti-aliased (egs_fused_forward(_raw)_aa), so the draw pass's dL/dalpha is that of the compensated opacity
+ * alpha comp; the chain rule applies dL/dalpha = g comp and adds g alpha dcomp/dcov2d to dL/dcov2d, and with it to the
+ * scale, rotation, position and pose gradients.  Without it a backward pass of an anti-aliased render is wrong. */
+#define EGS_BWD_ANTIALIASED 256
 #define EGS_DRAW_CULLED_LISTS 1
 /* flags of egs_splat_draw_rec* / egs_splat_bwd_rec_lists: the lists are the REFERENCE's complete lists (every tile of
  * every rect, kernel.cu:46-80) whose values carry the same 4-bit block masks above the Gaussian index -- what
@@ -516,6 +521,25 @@ int egs_fused_backward_raw(int n, int sh_dim, int64_t patches, int width, int he
                            const int32_t* tile_order /*nullable*/, float* grad_records /*nullable*/,
                            const float* dcolor_dpws /*nullable*/, int phase, int row_begin, int row_count,
                            void* seg_ws /*nullable*/, size_t seg_ws_bytes, void* stream);
+/* Anti-aliased rendering (the 2D filter of Mip-Splatting): egs_fused_forward(_raw) with every Gaussian binned and
+ * drawn with opacity alpha comp, comp = sqrt(det(Sigma) / det(Sigma + 0.3 I)), Sigma the 2D covariance before the +0.3
+ * dilation (which, like the radius, stays); comp = 0 when det(Sigma) <= 0 or comp is not finite.  The same arguments as
+ * the plain pair; `rec` is required (EGS_ERR_BAD_ARG otherwise).  The backward pass of such a render passes
+ * EGS_BWD_ANTIALIASED in `phase`. */
+int egs_fused_forward_aa(int n, int sh_dim, const float* pws, const float* rots, const float* scales,
+                         const float* shs, const float* alphas, const float* Rcw, const float* tcw, const float* twc,
+                         float fx, float fy, float cx, float cy, int width, int height, const EgsPolicy* pol,
+                         float* us, float* depths, float* cinv2ds, float* colors, int32_t* areas, void* rec,
+                         uint8_t* visible, float* dcolor_dpws /*nullable*/, int cull_lists, int key_bits_hint,
+                         void* ws_bin, size_t ws_bin_bytes, uint32_t* total_patches, uint32_t* host_totals,
+                         void* stream);
+int egs_fused_forward_raw_aa(int n, int sh_dim, const float* pws, const float* rots_raw, const float* scales_raw,
+                             const float* low_shs, const float* high_shs, const float* alphas_raw, const float* Rcw,
+                             const float* tcw, const float* twc, float fx, float fy, float cx, float cy, int width,
+                             int height, const EgsPolicy* pol, float* us, float* depths, float* cinv2ds,
+                             float* colors, int32_t* areas, void* rec, uint8_t* visible,
+                             float* dcolor_dpws /*nullable*/, int cull_lists, int key_bits_hint, void* ws_bin,
+                             size_t ws_bin_bytes, uint32_t* total_patches, uint32_t* host_totals, void* stream);
 /* egs_fused_backward / egs_fused_backward_raw of a render with extras: the EgsExtras of the forward call (depths,
  * background) with dloss_ddepth / dloss_dalpha; dL/dz is added to dloss_dpws.  extras == NULL: the plain call. */
 int egs_fused_backward_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
@@ -688,6 +712,11 @@ int egs_nn_sqdist(int n, const float* points, void* ws, size_t ws_bytes, float* 
 int egs_viewer_prep(int n, int sh_dim, const float* gs_data, const float* view_matrix,
                     const float* projection_matrix, float focal_x, float focal_y, float* gs_prep, float* depth,
                     void* stream);
+/* egs_viewer_prep for a model trained anti-aliased: the same arguments; the alpha column is alpha comp, comp the opacity
+ * compensation of egs_fused_forward_aa formed from the viewer's (unclamped) 2D covariance. */
+int egs_viewer_prep_aa(int n, int sh_dim, const float* gs_data, const float* view_matrix,
+                       const float* projection_matrix, float focal_x, float focal_y, float* gs_prep, float* depth,
+                       void* stream);
 
 /* ---- per-kernel timing with HIP events on the launch stream ---------------
  * bench.py's `roofline` leg: when enabled, every kernel launch of this library
