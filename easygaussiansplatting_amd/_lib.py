@@ -13,7 +13,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libegs_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class EgsPolicy(C.Structure):
@@ -32,7 +32,7 @@ class EgsExtras(C.Structure):
 
 
 class EgsPoseGrad(C.Structure):
-    """Mirror of `struct EgsPoseGrad` (camera pose gradients of egs_fused_backward(_raw)_pose)."""
+    """Mirror of `struct EgsPoseGrad` (camera pose gradients of egs_fused_backward)."""
     _fields_ = [("dloss_dRcw", C.c_void_p), ("dloss_dtcw", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
@@ -94,31 +94,13 @@ SIGNATURES = {
     "egs_exclusive_scan_u32": (_i, [_i64, _P, _P, _P, _P, _P, _sz, _P]),
     "egs_words_differ": (_i, [_P, _P, _i64, _P, _P]),
     "egs_chain_rule": (_i, [_i, _i] + [_P] * 16 + [_P]),
-    "egs_fused_forward": (_i, [_i, _i] + [_P] * 8 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8 + [_i, _i, _P, _sz, _P, _P, _P]),
-    "egs_fused_forward_raw": (_i, [_i, _i] + [_P] * 9 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8
-                              + [_i, _i, _P, _sz, _P, _P, _P]),
-    "egs_fused_forward_aa": (_i, [_i, _i] + [_P] * 8 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8
-                             + [_i, _i, _P, _sz, _P, _P, _P]),
-    "egs_fused_forward_raw_aa": (_i, [_i, _i] + [_P] * 9 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8
-                                 + [_i, _i, _P, _sz, _P, _P, _P]),
-    "egs_fused_backward_raw": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
-                               + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P]),
+    "egs_fused_forward": (_i, [_i, _i] + [_P] * 9 + [_f] * 4 + [_i, _i, _PP] + [_P] * 8 + [_i, _i, _P, _sz, _P, _P, _P]),
     "egs_seg_ws_bytes": (_sz, [_i64, _i, _i]),
     "egs_seg_config": (_i, [_i, _i, C.POINTER(C.c_int)]),
     "egs_splat_draw_rec_seg": (_i, [_i, _i64, _P, _i, _i, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P, _P,
-                                    _i, _i, _P, _sz, _P, _P, _P, _P]),
+                                    _i, _i, _P, _sz, _P, _P, _P, _P, _PX]),
     "egs_seg_rebuild_ws_bytes": (_sz, [_i64, _i, _i]),
-    "egs_splat_draw_rec_seg_ex": (_i, [_i, _i64, _P, _i, _i, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P, _P,
-                                       _i, _i, _P, _sz, _P, _P, _P, _P, _PX]),
-    "egs_fused_backward_ex": (_i, [_i, _i, _i64, _i, _i] + [_P] * 8 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
-                              + [_P] * 6 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX]),
-    "egs_fused_backward_raw_ex": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
-                                  + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX]),
     "egs_pose_ws_bytes": (_sz, [_i]),
-    "egs_fused_backward_pose": (_i, [_i, _i, _i64, _i, _i] + [_P] * 8 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
-                                + [_P] * 6 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX, _PPose]),
-    "egs_fused_backward_raw_pose": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
-                                    + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX, _PPose]),
     "egs_splat_bwd_seg": (_i, [_i, _i64, _i, _i, _P, _P, _P, _P, _P, _PP, _P, _P, _P, _P, _P, _P, _sz, _P, _P,
                                _P, _P, _P, _P, _i, _P, _sz, _i, _P, _P]),
     "egs_mailbox_peek": (_i, [_P, _i, C.POINTER(C.c_uint32)]),
@@ -137,8 +119,8 @@ SIGNATURES = {
     "egs_mailbox_arm": (_i, [_P, _i, _P]),
     "egs_mailbox_fetch": (_i, [_P, _i, _i, C.POINTER(C.c_uint32)]),
     "egs_fused_backward_ws_bytes": (_sz, [_i]),
-    "egs_fused_backward": (_i, [_i, _i, _i64, _i, _i] + [_P] * 8 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
-                           + [_P] * 6 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P]),
+    "egs_fused_backward": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
+                           + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX, _PPose]),
     "egs_gau_loss_ws_bytes": (_sz, [_i, _i]),
     "egs_gau_loss": (_i, [_i, _i, _P, _P, _f, _f, _P, _sz, _P, _P, _P]),
     "egs_density_accumulate": (_i, [_i, _P, _P, _i, _P, _P, _P]),
@@ -152,8 +134,7 @@ SIGNATURES = {
                                   C.c_double, C.c_double, C.c_double, _P]),
     "egs_nn_sqdist_ws_bytes": (_sz, [_i]),
     "egs_nn_sqdist": (_i, [_i, _P, _P, _sz, _P, _P]),
-    "egs_viewer_prep": (_i, [_i, _i, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _f, _f, _P, _P, _P]),
-    "egs_viewer_prep_aa": (_i, [_i, _i, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _f, _f, _P, _P, _P]),
+    "egs_viewer_prep": (_i, [_i, _i, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _f, _f, _P, _P, _i, _P]),
     "egs_prof_enable": (_i, [_i]),
     "egs_prof_set_filter": (None, [C.c_char_p]),
     "egs_prof_reset": (None, []),

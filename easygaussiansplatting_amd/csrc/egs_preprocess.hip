@@ -907,13 +907,20 @@ static PreParams make_pre_params(const EgsPolicy* pol, float fx, float fy, float
   return pp;
 }
 
-static int fused_forward_impl(bool raw, bool aa, int n, int sh_dim, const float* pws, const float* rots, const float* scales,
-                              const float* shs, const float* shs_high, const float* alphas, const float* Rcw,
-                              const float* tcw, const float* twc, float fx, float fy, float cx, float cy, int width,
-                              int height, const EgsPolicy* pol, float* us, float* depths, float* cinv2ds,
-                              float* colors, int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws,
-                              int cull_lists, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
-                              uint32_t* total_patches, uint32_t* host_totals, void* stream) {
+extern "C" int egs_fused_forward(int n, int sh_dim, const float* pws, const float* rots, const float* scales,
+                                 const float* shs, const float* shs_high, const float* alphas, const float* Rcw,
+                                 const float* tcw, const float* twc, float fx, float fy, float cx, float cy, int width,
+                                 int height, const EgsPolicy* pol, float* us, float* depths, float* cinv2ds,
+                                 float* colors, int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws,
+                                 int flags, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
+                                 uint32_t* total_patches, uint32_t* host_totals, void* stream) {
+  EGS_CHECK_ARG((flags & ~(EGS_FUSED_CULLED_LISTS | EGS_FUSED_ANTIALIASED | EGS_FUSED_RAW)) == 0);
+  const bool cull_lists = (flags & EGS_FUSED_CULLED_LISTS) != 0;
+  const bool aa = (flags & EGS_FUSED_ANTIALIASED) != 0;
+  const bool raw = (flags & EGS_FUSED_RAW) != 0;
+  EGS_CHECK_ARG(!aa || rec);   // the compensated opacity only exists inside the records
+  EGS_CHECK_ARG(!raw || n == 0 || (rec && alphas));   // so does the activated alpha
+  EGS_CHECK_ARG(raw || !shs_high);
   EGS_CHECK_ARG(n >= 0 && pol && width > 0 && height > 0 && total_patches);
   EGS_CHECK_ARG(!cull_lists || (rec && n < (1 << EGS_GSID_BITS)));   // culled lists are drawn from the records only
   EGS_CHECK_ARG(((uintptr_t)dcolor_dpws & 15) == 0);
@@ -928,7 +935,6 @@ static int fused_forward_impl(bool raw, bool aa, int n, int sh_dim, const float*
   EGS_CHECK_ARG(pws && rots && scales && shs && Rcw && tcw && twc && depths);
   EGS_CHECK_ARG(rec || (us && cinv2ds && colors && areas));   // something must carry the 2D Gaussians on
   EGS_CHECK_ARG(!rec || alphas);
-  EGS_CHECK_ARG(!aa || rec);   // the compensated opacity only exists inside the records
   EGS_CHECK_ARG(ws_bin);
   EGS_CHECK_ARG(((uintptr_t)rots & 15) == 0);
   if (raw) EGS_CHECK_ARG(sh_dim == 3 || (shs_high && ((uintptr_t)shs_high & 15) == 0));
@@ -938,7 +944,7 @@ static int fused_forward_impl(bool raw, bool aa, int n, int sh_dim, const float*
     set_error(EGS_ERR_WORKSPACE, "bin workspace too small", __FILE__, __LINE__);
     return EGS_ERR_WORKSPACE;
   }
-  const BinParams bp = make_bin_params(width, height, pol, cull_lists != 0);
+  const BinParams bp = make_bin_params(width, height, pol, cull_lists);
   const PreParams pp = make_pre_params(pol, fx, fy, cx, cy, width, height);
   dim3 g(div_up(n, 256)), b(256);
   // EGS_PRE_LDS_PAD (bytes of dynamic LDS, experiment knob): caps the resident workgroups per CU of this kernel
@@ -970,97 +976,43 @@ static int fused_forward_impl(bool raw, bool aa, int n, int sh_dim, const float*
   return splat_bin_after_count(n, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, stream, host_totals);
 }
 
-extern "C" int egs_fused_forward(int n, int sh_dim, const float* pws, const float* rots, const float* scales,
-                                 const float* shs, const float* alphas, const float* Rcw, const float* tcw,
-                                 const float* twc, float fx, float fy, float cx, float cy, int width, int height,
-                                 const EgsPolicy* pol, float* us, float* depths, float* cinv2ds, float* colors,
-                                 int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws, int cull_lists,
-                                 int key_bits_hint, void* ws_bin, size_t ws_bin_bytes, uint32_t* total_patches,
-                                 uint32_t* host_totals, void* stream) {
-  return fused_forward_impl(false, false, n, sh_dim, pws, rots, scales, shs, nullptr, alphas, Rcw, tcw, twc, fx, fy, cx,
-                            cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible, dcolor_dpws,
-                            cull_lists, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, host_totals, stream);
-}
-
-extern "C" int egs_fused_forward_raw(int n, int sh_dim, const float* pws, const float* rots_raw,
-                                     const float* scales_raw, const float* low_shs, const float* high_shs,
-                                     const float* alphas_raw, const float* Rcw, const float* tcw, const float* twc,
-                                     float fx, float fy, float cx, float cy, int width, int height,
-                                     const EgsPolicy* pol, float* us, float* depths, float* cinv2ds, float* colors,
-                                     int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws,
-                                     int cull_lists, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
-                                     uint32_t* total_patches, uint32_t* host_totals, void* stream) {
-  EGS_CHECK_ARG(n == 0 || (rec && alphas_raw));  // the activated alpha only exists inside the records
-  return fused_forward_impl(true, false, n, sh_dim, pws, rots_raw, scales_raw, low_shs, high_shs, alphas_raw, Rcw, tcw,
-                            twc, fx, fy, cx, cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible,
-                            dcolor_dpws, cull_lists, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, host_totals,
-                            stream);
-}
-
-// anti-aliased rendering (include/egs_hip.h): egs_fused_forward(_raw) with the opacity compensation of the 2D filter;
-// the same arguments, `rec` required
-extern "C" int egs_fused_forward_aa(int n, int sh_dim, const float* pws, const float* rots, const float* scales,
-                                    const float* shs, const float* alphas, const float* Rcw, const float* tcw,
-                                    const float* twc, float fx, float fy, float cx, float cy, int width, int height,
-                                    const EgsPolicy* pol, float* us, float* depths, float* cinv2ds, float* colors,
-                                    int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws, int cull_lists,
-                                    int key_bits_hint, void* ws_bin, size_t ws_bin_bytes, uint32_t* total_patches,
-                                    uint32_t* host_totals, void* stream) {
-  EGS_CHECK_ARG(rec);
-  return fused_forward_impl(false, true, n, sh_dim, pws, rots, scales, shs, nullptr, alphas, Rcw, tcw, twc, fx, fy, cx,
-                            cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible, dcolor_dpws,
-                            cull_lists, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, host_totals, stream);
-}
-
-extern "C" int egs_fused_forward_raw_aa(int n, int sh_dim, const float* pws, const float* rots_raw,
-                                        const float* scales_raw, const float* low_shs, const float* high_shs,
-                                        const float* alphas_raw, const float* Rcw, const float* tcw, const float* twc,
-                                        float fx, float fy, float cx, float cy, int width, int height,
-                                        const EgsPolicy* pol, float* us, float* depths, float* cinv2ds, float* colors,
-                                        int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws,
-                                        int cull_lists, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
-                                        uint32_t* total_patches, uint32_t* host_totals, void* stream) {
-  EGS_CHECK_ARG(rec && (n == 0 || alphas_raw));
-  return fused_forward_impl(true, true, n, sh_dim, pws, rots_raw, scales_raw, low_shs, high_shs, alphas_raw, Rcw, tcw,
-                            twc, fx, fy, cx, cy, width, height, pol, us, depths, cinv2ds, colors, areas, rec, visible,
-                            dcolor_dpws, cull_lists, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, host_totals,
-                            stream);
-}
-
 extern "C" size_t egs_fused_backward_ws_bytes(int n) { return egs_splat_bwd_ws_bytes(n); }
 
 // one partial row of 16 floats per 256-Gaussian workgroup of k_preprocess_bwd_pose
 extern "C" size_t egs_pose_ws_bytes(int n) { return align_up((size_t)div_up(n > 0 ? n : 1, 256) * 16 * sizeof(float), 256); }
 
-static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                               const float* rots, const float* scales, const float* shs, const float* shs_high,
-                               const float* alphas, const float* Rcw, const float* tcw, const float* twc, float fx,
-                               float fy, float cx, float cy, const EgsPolicy* pol, const float* us,
-                               const float* cinv2ds, const float* colors, const int32_t* areas, const void* rec,
-                               const float* depths, const int32_t* contrib, const float* final_tau,
-                               const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
-                               const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
-                               float* dloss_dshs, float* dloss_dshs_high, float* dloss_dalphas, float* dloss_dscales,
-                               float* dloss_drots, float* dloss_dus, const int32_t* tile_order,
-                               float* grad_records, const float* dcolor_dpws, int phase, int row_begin, int row_count,
-                               void* seg_ws, size_t seg_ws_bytes, void* stream, const EgsExtras* extras = nullptr,
-                               const EgsPoseGrad* pose = nullptr) {
-  // extras (nullable): the render had depth / opacity / background (egs_splat_draw_rec_seg_ex); the draw pass takes
-  // their upstream gradients and leaves dL/dz in gpack[i][9], the chain rule adds it to dL/dpw (k_preprocess_bwd_extra)
+extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                                  const float* rots, const float* scales, const float* shs, const float* shs_high,
+                                  const float* alphas, const float* Rcw, const float* tcw, const float* twc, float fx,
+                                  float fy, float cx, float cy, const EgsPolicy* pol, const float* us,
+                                  const float* cinv2ds, const float* colors, const int32_t* areas, const void* rec,
+                                  const float* depths, const int32_t* contrib, const float* final_tau,
+                                  const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
+                                  const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
+                                  float* dloss_dshs, float* dloss_dshs_high, float* dloss_dalphas,
+                                  float* dloss_dscales, float* dloss_drots, float* dloss_dus,
+                                  const int32_t* tile_order, float* grad_records, const float* dcolor_dpws, int phase,
+                                  int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
+                                  const EgsExtras* extras, const EgsPoseGrad* pose) {
+  // extras (nullable): the render had depth / opacity / background (egs_splat_draw_rec_seg with extras); the draw pass
+  // takes their upstream gradients and leaves dL/dz in gpack[i][9], the chain rule adds it to dL/dpw
+  // (k_preprocess_bwd_extra)
   // phase 0: everything; 1: only the draw pass (-> packed gradient records in ws); 2: only the per-Gaussian
   // chain rule, for rows [row_begin, row_begin + row_count) -- a data-parallel caller launches the rows in a
   // few chunks and starts exchanging a chunk's gradients while the next one is computed (dist_views)
   EGS_CHECK_ARG(n >= 0 && pol && width > 0 && height > 0 && patches >= 0);
   const bool keep_order = (phase & EGS_BWD_KEEP_FORWARD_ORDER) != 0;
-  const bool masked = (phase & EGS_BWD_CULLED_LISTS) != 0;
+  const bool masked = (phase & EGS_FUSED_CULLED_LISTS) != 0;
   // kernel `mode`: bit 0 accumulate, bit 1 factored SH gradient (dloss_dshs = dL/dcolour [N][3])
   const int accum = ((phase & EGS_BWD_ACCUMULATE) ? 1 : 0) | ((phase & EGS_BWD_FACTORED_SH) ? 2 : 0);
   const bool factored = (phase & EGS_BWD_FACTORED_SH) != 0;
-  // the render was anti-aliased (egs_fused_forward(_raw)_aa): the chain rule takes the AA instances
-  const bool aa = (phase & EGS_BWD_ANTIALIASED) != 0;
-  phase &= ~(EGS_BWD_KEEP_FORWARD_ORDER | EGS_BWD_CULLED_LISTS | EGS_BWD_ACCUMULATE | EGS_BWD_FACTORED_SH |
-             EGS_BWD_ANTIALIASED);
+  // the render was anti-aliased: the chain rule takes the AA instances
+  const bool aa = (phase & EGS_FUSED_ANTIALIASED) != 0;
+  const bool raw = (phase & EGS_FUSED_RAW) != 0;
+  phase &= ~(EGS_BWD_KEEP_FORWARD_ORDER | EGS_BWD_ACCUMULATE | EGS_BWD_FACTORED_SH | EGS_FUSED_CULLED_LISTS |
+             EGS_FUSED_ANTIALIASED | EGS_FUSED_RAW);
   EGS_CHECK_ARG(phase >= 0 && phase <= 2);
+  EGS_CHECK_ARG(raw || (!shs_high && !dloss_dshs_high));
   // pose (nullable): the camera gradient needs every row in one launch (k_pose_reduce sums all partial rows)
   if (pose) {
     EGS_CHECK_ARG(phase == 0 && pose->dloss_dRcw && pose->dloss_dtcw);
@@ -1159,139 +1111,6 @@ static int fused_backward_impl(bool raw, int n, int sh_dim, int64_t patches, int
     EGS_LAUNCH_OK();
   }
   return 0;
-}
-
-extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                                  const float* rots, const float* scales, const float* shs, const float* alphas,
-                                  const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx,
-                                  float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
-                                  const float* colors, const int32_t* areas, const void* rec, const float* depths,
-                                  const int32_t* contrib, const float* final_tau,
-                                  const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
-                                  const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
-                                  float* dloss_dshs, float* dloss_dalphas, float* dloss_dscales,
-                                  float* dloss_drots, float* dloss_dus, const int32_t* tile_order,
-                                  float* grad_records, const float* dcolor_dpws, int phase, int row_begin,
-                                  int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream) {
-  return fused_backward_impl(false, n, sh_dim, patches, width, height, pws, rots, scales, shs, nullptr, alphas, Rcw,
-                             tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths, contrib,
-                             final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes, dloss_dpws,
-                             dloss_dshs, nullptr, dloss_dalphas, dloss_dscales, dloss_drots, dloss_dus, tile_order,
-                             grad_records, dcolor_dpws, phase, row_begin, row_count, seg_ws, seg_ws_bytes, stream);
-}
-
-extern "C" int egs_fused_backward_raw(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                                      const float* rots_raw, const float* scales_raw, const float* low_shs,
-                                      const float* high_shs, const float* alphas_raw, const float* Rcw,
-                                      const float* tcw, const float* twc, float fx, float fy, float cx, float cy,
-                                      const EgsPolicy* pol, const float* us, const float* cinv2ds,
-                                      const float* colors, const int32_t* areas, const void* rec,
-                                      const float* depths, const int32_t* contrib, const float* final_tau,
-                                      const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
-                                      const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
-                                      float* dloss_dlow_shs, float* dloss_dhigh_shs, float* dloss_dalphas_raw,
-                                      float* dloss_dscales_raw, float* dloss_drots_raw, float* dloss_dus,
-                                      const int32_t* tile_order, float* grad_records, const float* dcolor_dpws,
-                                      int phase, int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes,
-                                      void* stream) {
-  return fused_backward_impl(true, n, sh_dim, patches, width, height, pws, rots_raw, scales_raw, low_shs, high_shs,
-                             alphas_raw, Rcw, tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths,
-                             contrib, final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes,
-                             dloss_dpws, dloss_dlow_shs, dloss_dhigh_shs, dloss_dalphas_raw, dloss_dscales_raw,
-                             dloss_drots_raw, dloss_dus, tile_order, grad_records, dcolor_dpws, phase, row_begin,
-                             row_count, seg_ws, seg_ws_bytes, stream);
-}
-
-// egs_fused_backward(_raw) of a render with extras (egs_splat_draw_rec_seg_ex): the same arguments and the same EgsExtras
-// (depths, background; dloss_ddepth / dloss_dalpha nullable); extras == NULL is the plain call
-extern "C" int egs_fused_backward_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                                     const float* rots, const float* scales, const float* shs, const float* alphas,
-                                     const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx,
-                                     float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
-                                     const float* colors, const int32_t* areas, const void* rec, const float* depths,
-                                     const int32_t* contrib, const float* final_tau,
-                                     const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
-                                     const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
-                                     float* dloss_dshs, float* dloss_dalphas, float* dloss_dscales,
-                                     float* dloss_drots, float* dloss_dus, const int32_t* tile_order,
-                                     float* grad_records, const float* dcolor_dpws, int phase, int row_begin,
-                                     int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
-                                     const EgsExtras* extras) {
-  return fused_backward_impl(false, n, sh_dim, patches, width, height, pws, rots, scales, shs, nullptr, alphas, Rcw,
-                             tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths, contrib,
-                             final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes, dloss_dpws,
-                             dloss_dshs, nullptr, dloss_dalphas, dloss_dscales, dloss_drots, dloss_dus, tile_order,
-                             grad_records, dcolor_dpws, phase, row_begin, row_count, seg_ws, seg_ws_bytes, stream,
-                             extras);
-}
-
-extern "C" int egs_fused_backward_raw_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                                         const float* rots_raw, const float* scales_raw, const float* low_shs,
-                                         const float* high_shs, const float* alphas_raw, const float* Rcw,
-                                         const float* tcw, const float* twc, float fx, float fy, float cx, float cy,
-                                         const EgsPolicy* pol, const float* us, const float* cinv2ds,
-                                         const float* colors, const int32_t* areas, const void* rec,
-                                         const float* depths, const int32_t* contrib, const float* final_tau,
-                                         const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
-                                         const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
-                                         float* dloss_dlow_shs, float* dloss_dhigh_shs, float* dloss_dalphas_raw,
-                                         float* dloss_dscales_raw, float* dloss_drots_raw, float* dloss_dus,
-                                         const int32_t* tile_order, float* grad_records, const float* dcolor_dpws,
-                                         int phase, int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes,
-                                         void* stream, const EgsExtras* extras) {
-  return fused_backward_impl(true, n, sh_dim, patches, width, height, pws, rots_raw, scales_raw, low_shs, high_shs,
-                             alphas_raw, Rcw, tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths,
-                             contrib, final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes,
-                             dloss_dpws, dloss_dlow_shs, dloss_dhigh_shs, dloss_dalphas_raw, dloss_dscales_raw,
-                             dloss_drots_raw, dloss_dus, tile_order, grad_records, dcolor_dpws, phase, row_begin,
-                             row_count, seg_ws, seg_ws_bytes, stream, extras);
-}
-
-// egs_fused_backward(_raw)_ex plus the camera pose gradient (include/egs_hip.h EgsPoseGrad)
-extern "C" int egs_fused_backward_pose(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                                       const float* rots, const float* scales, const float* shs, const float* alphas,
-                                       const float* Rcw, const float* tcw, const float* twc, float fx, float fy,
-                                       float cx, float cy, const EgsPolicy* pol, const float* us,
-                                       const float* cinv2ds, const float* colors, const int32_t* areas,
-                                       const void* rec, const float* depths, const int32_t* contrib,
-                                       const float* final_tau, const int32_t* patch_range_per_tile,
-                                       const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws,
-                                       size_t ws_bytes, float* dloss_dpws, float* dloss_dshs, float* dloss_dalphas,
-                                       float* dloss_dscales, float* dloss_drots, float* dloss_dus,
-                                       const int32_t* tile_order, float* grad_records, const float* dcolor_dpws,
-                                       int phase, int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes,
-                                       void* stream, const EgsExtras* extras, const EgsPoseGrad* pose) {
-  EGS_CHECK_ARG(pose);
-  return fused_backward_impl(false, n, sh_dim, patches, width, height, pws, rots, scales, shs, nullptr, alphas, Rcw,
-                             tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths, contrib,
-                             final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes, dloss_dpws,
-                             dloss_dshs, nullptr, dloss_dalphas, dloss_dscales, dloss_drots, dloss_dus, tile_order,
-                             grad_records, dcolor_dpws, phase, row_begin, row_count, seg_ws, seg_ws_bytes, stream,
-                             extras, pose);
-}
-
-extern "C" int egs_fused_backward_raw_pose(int n, int sh_dim, int64_t patches, int width, int height,
-                                           const float* pws, const float* rots_raw, const float* scales_raw,
-                                           const float* low_shs, const float* high_shs, const float* alphas_raw,
-                                           const float* Rcw, const float* tcw, const float* twc, float fx, float fy,
-                                           float cx, float cy, const EgsPolicy* pol, const float* us,
-                                           const float* cinv2ds, const float* colors, const int32_t* areas,
-                                           const void* rec, const float* depths, const int32_t* contrib,
-                                           const float* final_tau, const int32_t* patch_range_per_tile,
-                                           const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws,
-                                           size_t ws_bytes, float* dloss_dpws, float* dloss_dlow_shs,
-                                           float* dloss_dhigh_shs, float* dloss_dalphas_raw, float* dloss_dscales_raw,
-                                           float* dloss_drots_raw, float* dloss_dus, const int32_t* tile_order,
-                                           float* grad_records, const float* dcolor_dpws, int phase, int row_begin,
-                                           int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
-                                           const EgsExtras* extras, const EgsPoseGrad* pose) {
-  EGS_CHECK_ARG(pose);
-  return fused_backward_impl(true, n, sh_dim, patches, width, height, pws, rots_raw, scales_raw, low_shs, high_shs,
-                             alphas_raw, Rcw, tcw, twc, fx, fy, cx, cy, pol, us, cinv2ds, colors, areas, rec, depths,
-                             contrib, final_tau, patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes,
-                             dloss_dpws, dloss_dlow_shs, dloss_dhigh_shs, dloss_dalphas_raw, dloss_dscales_raw,
-                             dloss_drots_raw, dloss_dus, tile_order, grad_records, dcolor_dpws, phase, row_begin,
-                             row_count, seg_ws, seg_ws_bytes, stream, extras, pose);
 }
 
 extern "C" int egs_sh_grad_views(int n, int sh_dim, int views, const float* pws, const float* rows,

@@ -175,7 +175,7 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
   // this camera measured.  seg_hint (nullable, page-locked): receives the longest list of this render.
   // gsid_plain (nullable, with EGS_DRAW_MASKED_LISTS): receives the list values without their masks
   // flags & EGS_DRAW_CULLED_LISTS: the binning stage counted the footprint-culled tiles (egs_fused_forward with
-  // cull_lists): the lists are emitted with block masks in the high bits of their values and drawn from those
+  // EGS_FUSED_CULLED_LISTS): the lists are emitted with block masks in the high bits of their values and drawn from those
   // order_ready != 0: tile_order already holds a dispatch order (an earlier render through the SAME buffer left
   // it there): it is used as it stands, no k_tile_order launch; the work part is still rewritten by the draw
   // prev_tile_work != NULL (T ints): the work the draw kernel measured per tile the LAST time this camera was
@@ -394,32 +394,17 @@ extern "C" int egs_splat_draw_rec_dev_plain(int n, int64_t patch_capacity, const
                          nullptr, 0, flags, gsid_plain);
 }
 
-// the draw stage of egs_splat_draw_rec / _dev (total_patches NULL: `patches` is exact) with a segment workspace
+// the draw stage of egs_splat_draw_rec / _dev (total_patches NULL: `patches` is exact) with a segment workspace, and of
+// a render with extras (EgsExtras: depth / opacity maps, background; nullable).  With extras the lists are never split:
+// seg_ws must be NULL.
 extern "C" int egs_splat_draw_rec_seg(int n, int64_t patches, const uint32_t* total_patches, int width, int height,
                                       const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
                                       size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
                                       int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order,
                                       float* grad_records, const int32_t* prev_tile_work, int order_ready, int flags,
                                       void* seg_ws, size_t seg_ws_bytes, uint32_t* seg_hint, int32_t* walk_word,
-                                      int32_t* gsid_plain, void* stream) {
+                                      int32_t* gsid_plain, void* stream, const EgsExtras* extras) {
   // gsid_plain (nullable, with EGS_DRAW_MASKED_LISTS: the seven-op surface): receives the list without its masks
-  EGS_CHECK_ARG((rec || n == 0) && (!total_patches || patches > 0));
-  EGS_CHECK_ARG(!gsid_plain || ((((uintptr_t)gsid_plain | (uintptr_t)gsid_per_patch) & 15) == 0));
-  return splat_draw_impl(n, patches, width, height, nullptr, nullptr, nullptr, nullptr, nullptr, pol, ws_bin, ws_draw,
-                         ws_draw_bytes, (const float4*)rec, image, contrib, final_tau, patch_range_per_tile,
-                         gsid_per_patch, stream, total_patches, tile_order, grad_records, prev_tile_work, order_ready,
-                         flags, gsid_plain, seg_ws, seg_ws_bytes, seg_hint, walk_word);
-}
-
-// egs_splat_draw_rec_seg of a render with extras (EgsExtras: depth / opacity maps, background); extras == NULL is the
-// plain call.  With extras the lists are never split: seg_ws must be NULL.
-extern "C" int egs_splat_draw_rec_seg_ex(int n, int64_t patches, const uint32_t* total_patches, int width, int height,
-                                         const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
-                                         size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
-                                         int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order,
-                                         float* grad_records, const int32_t* prev_tile_work, int order_ready, int flags,
-                                         void* seg_ws, size_t seg_ws_bytes, uint32_t* seg_hint, int32_t* walk_word,
-                                         int32_t* gsid_plain, void* stream, const EgsExtras* extras) {
   EGS_CHECK_ARG((rec || n == 0) && (!total_patches || patches > 0));
   EGS_CHECK_ARG(!gsid_plain || ((((uintptr_t)gsid_plain | (uintptr_t)gsid_per_patch) & 15) == 0));
   return splat_draw_impl(n, patches, width, height, nullptr, nullptr, nullptr, nullptr, nullptr, pol, ws_bin, ws_draw,

@@ -62,9 +62,12 @@ static bool invert4(const float* m, double* inv) {
 
 using namespace egs;
 
-static int viewer_prep_impl(bool aa, int n, int sh_dim, const float* gs_data, const float* view_matrix,
-                            const float* projection_matrix, float focal_x, float focal_y, float* gs_prep, float* depth,
-                            void* stream) {
+extern "C" int egs_viewer_prep(int n, int sh_dim, const float* gs_data, const float* view_matrix,
+                               const float* projection_matrix, float focal_x, float focal_y, float* gs_prep,
+                               float* depth, int flags, void* stream) {
+  // flags & EGS_FUSED_ANTIALIASED: the alpha column is alpha comp (include/egs_hip.h)
+  EGS_CHECK_ARG((flags & ~EGS_FUSED_ANTIALIASED) == 0);
+  const bool aa = flags != 0;
   EGS_CHECK_ARG(n >= 0 && view_matrix && projection_matrix);
   EGS_CHECK_ARG(sh_dim == 3 || sh_dim == 12 || sh_dim == 27 || sh_dim == 48);
   if (n == 0) return 0;
@@ -91,19 +94,4 @@ static int viewer_prep_impl(bool aa, int n, int sh_dim, const float* gs_data, co
 #undef EGS_VP
   EGS_LAUNCH_OK();
   return 0;
-}
-
-extern "C" int egs_viewer_prep(int n, int sh_dim, const float* gs_data, const float* view_matrix,
-                               const float* projection_matrix, float focal_x, float focal_y, float* gs_prep,
-                               float* depth, void* stream) {
-  return viewer_prep_impl(false, n, sh_dim, gs_data, view_matrix, projection_matrix, focal_x, focal_y, gs_prep, depth,
-                          stream);
-}
-
-// the anti-aliased flavour (include/egs_hip.h): the alpha column is alpha comp
-extern "C" int egs_viewer_prep_aa(int n, int sh_dim, const float* gs_data, const float* view_matrix,
-                                  const float* projection_matrix, float focal_x, float focal_y, float* gs_prep,
-                                  float* depth, void* stream) {
-  return viewer_prep_impl(true, n, sh_dim, gs_data, view_matrix, projection_matrix, focal_x, focal_y, gs_prep, depth,
-                          stream);
 }

@@ -117,6 +117,59 @@ def _extra_grads(ctx, dloss_dgammas, rest):
     return dloss_dgammas, dd, da
 
 
+def _fused_forward(ctx, leaves, cam):
+    """The fused-path forward of a node (``ctx.opts`` set): renders ``leaves`` -- the node's Gaussian inputs in its
+    argument order, (pws, shs, alphas, scales, rots) or the raw (pws, low_shs, high_shs, alphas_raw, scales_raw,
+    rots_raw) -- through ``cam``, saves them for ``_fused_backward`` and returns the node's outputs"""
+    o = ctx.opts
+    ctx.extras = None if o is None else o.extras()
+    pws, shs, *rest = leaves
+    high_shs = rest.pop(0) if len(leaves) == 6 else None
+    res = _fused.forward(pws, shs, *rest, cam, high_shs=high_shs, need_grad=True, extras=ctx.extras,
+                         antialiased=o is not None and o.antialiased)
+    image, mask, ctx.state = res[:3]
+    ctx.cam = cam
+    ctx.save_for_backward(*leaves)
+    ctx.mark_non_differentiable(mask)
+    if ctx.extras is not None:
+        return _extra_outputs(ctx, image, mask, res[3], res[4])
+    return image, mask
+
+
+def _fused_backward(ctx, dloss_dgammas, rest, pose=False):
+    """The fused-path backward of a node whose forward ran ``_fused_forward``: its gradient tuple (``ctx.n_inputs``
+    entries).  ``pose``: a pose node -- the camera of the call is also differentiated (inputs Rcw, tcw behind ``us``)
+    and the call never takes a ChunkedExchange."""
+    dd = da = None
+    if ctx.extras is not None:
+        dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
+    if dloss_dgammas is None:  # the image did not take part in the loss
+        return (None,) * ctx.n_inputs
+    o = ctx.opts
+    leaves = ctx.saved_tensors
+    k = len(leaves)
+    pws, sh, others = leaves[0], leaves[1:k - 3], leaves[k - 3:]    # sh: (shs,) or (low_shs, high_shs)
+    exchange = None if (pose or o is None) else o.exchange
+    # a training step that keeps its SH gradient factored (dist_views.FactoredShGrad): this view leaves dL/dcolour
+    # [N,3] in the sink, autograd gets None for the SH inputs, the others go on as usual
+    sink = _fused.sh_sink_for(ctx, k, sh, None if o is None else (o.sh_sink, exchange))
+    acc = _fused.accumulation_targets((pws,) + others if sink is not None else leaves, ctx, k,
+                                      None if o is None else (o.accumulate, exchange))
+    cam = ctx.cam
+    res = _fused.backward(
+        pws, sh[0], *others, cam, ctx.state, dloss_dgammas.contiguous(), high_shs=sh[1] if len(sh) == 2 else None,
+        accumulate=acc, sh_sink=sink, exchange=None if pose else (_fused.DEFAULT if o is None else o.exchange),
+        dloss_ddepth=None if dd is None else dd.contiguous(), dloss_dalpha=None if da is None else da.contiguous(),
+        pose=(cam.Rcw, cam.tcw) if pose else None)
+    # acc: added to the leaves' .grad inside the kernel, nothing for autograd to accumulate
+    grads = res[:k + 1] if acc is None else (None,) * k + (res[k],)
+    tail = [None] * (ctx.n_inputs - k - 1)      # us's gradient is the last of `grads`; then Rcw, tcw, cam, opts
+    if pose:
+        tail[:2] = (res[k + 1] if ctx.needs_input_grad[k + 1] else None,
+                    res[k + 2] if ctx.needs_input_grad[k + 2] else None)
+    return tuple(grads) + tuple(tail)
+
+
 class GSFunction(torch.autograd.Function):
     # process-wide defaults of calls WITHOUT a RenderOptions argument
     mode = "fused"
@@ -133,21 +186,8 @@ class GSFunction(torch.autograd.Function):
         use_records = GSFunction.ops_use_records if opts is None else opts.ops_use_records
         # the mask output never carries a gradient: do not let autograd zero-fill one per step
         ctx.set_materialize_grads(False)
-        ctx.extras = None if opts is None else opts.extras()
         if ctx.mode == "fused":
-            aa = opts is not None and opts.antialiased
-            if ctx.extras is not None:
-                image, mask, state, depth, alpha = _fused.forward(pws, shs, alphas, scales, rots, cam, need_grad=True,
-                                                                  extras=ctx.extras, antialiased=aa)
-            else:
-                image, mask, state = _fused.forward(pws, shs, alphas, scales, rots, cam, need_grad=True, antialiased=aa)
-            ctx.cam = cam
-            ctx.state = state
-            ctx.save_for_backward(pws, shs, alphas, scales, rots)
-            ctx.mark_non_differentiable(mask)
-            if ctx.extras is not None:
-                return _extra_outputs(ctx, image, mask, depth, alpha)
-            return image, mask
+            return _fused_forward(ctx, (pws, shs, alphas, scales, rots), cam)
         # forward.md steps 1-5 == gsmodel.py:21-39
         us, pcs, depths, du_dpcs = gsc.project(pws, cam.Rcw, cam.tcw, cam.fx, cam.fy, cam.cx, cam.cy, True)
         cov3ds, dcov3d_drots, dcov3d_dscales = gsc.computeCov3D(rots, scales, depths, True)
@@ -176,28 +216,12 @@ class GSFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss_dgammas, _, *rest):
-        cam = ctx.cam
-        pad = (None,) * (ctx.n_inputs - 6)      # cam (and the options)
-        dd = da = None
-        if ctx.extras is not None:
-            dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
+        if ctx.mode == "fused":
+            return _fused_backward(ctx, dloss_dgammas, rest)
         if dloss_dgammas is None:  # the image did not take part in the loss
             return (None,) * ctx.n_inputs
-        if ctx.mode == "fused":
-            pws, shs, alphas, scales, rots = ctx.saved_tensors
-            o = ctx.opts
-            # a training step that keeps its SH gradient factored (dist_views.FactoredShGrad): this view leaves
-            # dL/dcolour [N,3] in the sink, autograd gets None for shs, the other four go on as usual
-            sink = _fused.sh_sink_for(ctx, 5, (shs,), None if o is None else (o.sh_sink, o.exchange))
-            leaves = (pws, alphas, scales, rots) if sink is not None else (pws, shs, alphas, scales, rots)
-            acc = _fused.accumulation_targets(leaves, ctx, 5, None if o is None else (o.accumulate, o.exchange))
-            dpws, dshs, dalphas, dscales, drots, dus = _fused.backward(
-                pws, shs, alphas, scales, rots, cam, ctx.state, dloss_dgammas.contiguous(), accumulate=acc,
-                sh_sink=sink, exchange=(_fused.DEFAULT if o is None else o.exchange),
-                dloss_ddepth=None if dd is None else dd.contiguous(), dloss_dalpha=None if da is None else da.contiguous())
-            if acc is not None:      # added to the leaves' .grad inside the kernel: nothing for autograd to accumulate
-                return (None, None, None, None, None, dus) + pad
-            return (dpws, dshs, dalphas, dscales, drots, dus) + pad
+        cam = ctx.cam
+        pad = (None,) * (ctx.n_inputs - 6)      # cam (and the options)
         (us, cinv2ds, alphas, depths, colors, contrib, final_tau, patch_range_per_tile, gsid_per_patch,
          dcinv2d_dcov2ds, dcov2d_dcov3ds, dcov3d_drots, dcov3d_dscales, dcolor_dshs, du_dpcs, dcov2d_dpcs,
          dcolor_dpws) = ctx.saved_tensors
@@ -223,39 +247,11 @@ class GSRawFunction(torch.autograd.Function):
         ctx.opts = opts            # (``mode`` does not apply: this node IS the fused path)
         ctx.n_inputs = 9     # (as GSFunction: the maximal tuple)
         ctx.set_materialize_grads(False)
-        ctx.extras = None if opts is None else opts.extras()
-        res = _fused.forward(pws, low_shs, alphas_raw, scales_raw, rots_raw, cam, high_shs=high_shs, need_grad=True,
-                             extras=ctx.extras, antialiased=opts is not None and opts.antialiased)
-        image, mask, state = res[:3]
-        ctx.cam = cam
-        ctx.state = state
-        ctx.save_for_backward(pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw)
-        ctx.mark_non_differentiable(mask)
-        if ctx.extras is not None:
-            return _extra_outputs(ctx, image, mask, res[3], res[4])
-        return image, mask
+        return _fused_forward(ctx, (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw), cam)
 
     @staticmethod
     def backward(ctx, dloss_dgammas, _, *rest):
-        dd = da = None
-        if ctx.extras is not None:
-            dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
-        if dloss_dgammas is None:
-            return (None,) * ctx.n_inputs
-        pad = (None,) * (ctx.n_inputs - 7)
-        o = ctx.opts
-        pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw = ctx.saved_tensors
-        sink = _fused.sh_sink_for(ctx, 6, (low_shs, high_shs), None if o is None else (o.sh_sink, o.exchange))
-        leaves = (pws, alphas_raw, scales_raw, rots_raw) if sink is not None else \
-            (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw)
-        acc = _fused.accumulation_targets(leaves, ctx, 6, None if o is None else (o.accumulate, o.exchange))
-        dpws, dlow, dhigh, dalphas, dscales, drots, dus = _fused.backward(
-            pws, low_shs, alphas_raw, scales_raw, rots_raw, ctx.cam, ctx.state, dloss_dgammas.contiguous(),
-            high_shs=high_shs, accumulate=acc, sh_sink=sink, exchange=(_fused.DEFAULT if o is None else o.exchange),
-            dloss_ddepth=None if dd is None else dd.contiguous(), dloss_dalpha=None if da is None else da.contiguous())
-        if acc is not None:
-            return (None, None, None, None, None, None, dus) + pad
-        return (dpws, dlow, dhigh, dalphas, dscales, drots, dus) + pad
+        return _fused_backward(ctx, dloss_dgammas, rest)
 
 
 def camera_centre(Rcw, tcw):
@@ -285,7 +281,6 @@ def _pose_setup(ctx, opts, Rcw, tcw, cam, like):
     Rcw, tcw = _fused.pose_tensors(Rcw, tcw, like)
     ctx.opts = opts
     ctx.set_materialize_grads(False)
-    ctx.extras = None if opts is None else opts.extras()
     return _PoseCamera(cam, Rcw.detach(), tcw.detach())
 
 
@@ -302,38 +297,11 @@ class GSPoseFunction(torch.autograd.Function):
     def forward(ctx, pws, shs, alphas, scales, rots, us, Rcw, tcw, cam, opts=None):
         pcam = _pose_setup(ctx, opts, Rcw, tcw, cam, pws)
         ctx.n_inputs = 10
-        res = _fused.forward(pws, shs, alphas, scales, rots, pcam, need_grad=True, extras=ctx.extras,
-                             antialiased=opts is not None and opts.antialiased)
-        image, mask, state = res[:3]
-        ctx.cam = pcam
-        ctx.state = state
-        ctx.save_for_backward(pws, shs, alphas, scales, rots)
-        ctx.mark_non_differentiable(mask)
-        if ctx.extras is not None:
-            return _extra_outputs(ctx, image, mask, res[3], res[4])
-        return image, mask
+        return _fused_forward(ctx, (pws, shs, alphas, scales, rots), pcam)
 
     @staticmethod
     def backward(ctx, dloss_dgammas, _, *rest):
-        dd = da = None
-        if ctx.extras is not None:
-            dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
-        if dloss_dgammas is None:
-            return (None,) * ctx.n_inputs
-        o = ctx.opts
-        cam = ctx.cam
-        pws, shs, alphas, scales, rots = ctx.saved_tensors
-        sink = _fused.sh_sink_for(ctx, 5, (shs,), None if o is None else (o.sh_sink, None))
-        leaves = (pws, alphas, scales, rots) if sink is not None else (pws, shs, alphas, scales, rots)
-        acc = _fused.accumulation_targets(leaves, ctx, 5, None if o is None else (o.accumulate, None))
-        dpws, dshs, dalphas, dscales, drots, dus, dR, dt = _fused.backward(
-            pws, shs, alphas, scales, rots, cam, ctx.state, dloss_dgammas.contiguous(), accumulate=acc, sh_sink=sink,
-            exchange=None, dloss_ddepth=None if dd is None else dd.contiguous(),
-            dloss_dalpha=None if da is None else da.contiguous(), pose=(cam.Rcw, cam.tcw))
-        pose = (dR if ctx.needs_input_grad[6] else None, dt if ctx.needs_input_grad[7] else None, None, None)
-        if acc is not None:
-            return (None, None, None, None, None, dus) + pose
-        return (dpws, dshs, dalphas, dscales, drots, dus) + pose
+        return _fused_backward(ctx, dloss_dgammas, rest, pose=True)
 
 
 class GSRawPoseFunction(torch.autograd.Function):
@@ -345,40 +313,11 @@ class GSRawPoseFunction(torch.autograd.Function):
     def forward(ctx, pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw, us, Rcw, tcw, cam, opts=None):
         pcam = _pose_setup(ctx, opts, Rcw, tcw, cam, pws)
         ctx.n_inputs = 11
-        res = _fused.forward(pws, low_shs, alphas_raw, scales_raw, rots_raw, pcam, high_shs=high_shs, need_grad=True,
-                             extras=ctx.extras, antialiased=opts is not None and opts.antialiased)
-        image, mask, state = res[:3]
-        ctx.cam = pcam
-        ctx.state = state
-        ctx.save_for_backward(pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw)
-        ctx.mark_non_differentiable(mask)
-        if ctx.extras is not None:
-            return _extra_outputs(ctx, image, mask, res[3], res[4])
-        return image, mask
+        return _fused_forward(ctx, (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw), pcam)
 
     @staticmethod
     def backward(ctx, dloss_dgammas, _, *rest):
-        dd = da = None
-        if ctx.extras is not None:
-            dloss_dgammas, dd, da = _extra_grads(ctx, dloss_dgammas, rest)
-        if dloss_dgammas is None:
-            return (None,) * ctx.n_inputs
-        o = ctx.opts
-        cam = ctx.cam
-        pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw = ctx.saved_tensors
-        sink = _fused.sh_sink_for(ctx, 6, (low_shs, high_shs), None if o is None else (o.sh_sink, None))
-        leaves = (pws, alphas_raw, scales_raw, rots_raw) if sink is not None else \
-            (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw)
-        acc = _fused.accumulation_targets(leaves, ctx, 6, None if o is None else (o.accumulate, None))
-        dpws, dlow, dhigh, dalphas, dscales, drots, dus, dR, dt = _fused.backward(
-            pws, low_shs, alphas_raw, scales_raw, rots_raw, cam, ctx.state, dloss_dgammas.contiguous(),
-            high_shs=high_shs, accumulate=acc, sh_sink=sink, exchange=None,
-            dloss_ddepth=None if dd is None else dd.contiguous(), dloss_dalpha=None if da is None else da.contiguous(),
-            pose=(cam.Rcw, cam.tcw))
-        pose = (dR if ctx.needs_input_grad[7] else None, dt if ctx.needs_input_grad[8] else None, None, None)
-        if acc is not None:
-            return (None, None, None, None, None, None, dus) + pose
-        return (dpws, dlow, dhigh, dalphas, dscales, drots, dus) + pose
+        return _fused_backward(ctx, dloss_dgammas, rest, pose=True)
 
 
 def render(pws, shs, alphas, scales, rots, cam, calc_J=False):

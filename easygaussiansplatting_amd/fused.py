@@ -44,10 +44,12 @@ SEG_SPECULATE_FLAG = 8    # include/egs_hip.h EGS_DRAW_SEG_SPECULATE
 # a camera without a walk on record on the segment path: "auto" = all its segments at once when the scene's recent renders
 # walked at least half of their longest list (nothing saturates: reset_alpha), "1" always, "0" never (segment 0 only)
 SEG_SPECULATE = os.environ.get("EGS_SEG_SPECULATE", "auto")
-CULLED_LISTS = 32         # include/egs_hip.h EGS_BWD_CULLED_LISTS
 ACCUMULATE = 64           # include/egs_hip.h EGS_BWD_ACCUMULATE
 FACTORED_SH = 128         # include/egs_hip.h EGS_BWD_FACTORED_SH
-ANTIALIASED = 256         # include/egs_hip.h EGS_BWD_ANTIALIASED
+# the render's flags (FusedState.flags): egs_fused_forward's `flags`, OR-ed into every egs_fused_backward phase
+CULLED_LISTS = 32         # include/egs_hip.h EGS_FUSED_CULLED_LISTS
+ANTIALIASED = 256         # include/egs_hip.h EGS_FUSED_ANTIALIASED
+RAW = 512                 # include/egs_hip.h EGS_FUSED_RAW
 GSID_MASK = 0x0FFFFFFF    # csrc/egs_common.h EGS_GSID_MASK
 MAILBOX_SLOTS = 64
 HINT_SLOTS = 16           # problem sizes that keep a hint slot (longest list / longest walk of their recent renders)
@@ -57,8 +59,18 @@ class FusedState:
     """Tensors the backward pass needs (all produced by ``forward``).  ``ticket`` is set while the render's
     patch count has not been validated yet (deferred validation, see ``deferred``)."""
     __slots__ = ("us", "depths", "cinv2ds", "colors", "areas", "rec", "contrib", "final_tau", "ranges", "gsid",
-                 "order", "order_by_work", "gpack", "dcw", "culled", "width", "height", "ticket", "_patches", "_keep",
-                 "seg", "extras", "antialiased")
+                 "order", "order_by_work", "gpack", "dcw", "flags", "width", "height", "ticket", "_patches", "_keep",
+                 "seg", "extras")
+
+    @property
+    def culled(self):
+        """the tile lists are footprint-culled (``CULLED_LISTS``)"""
+        return bool(self.flags & CULLED_LISTS)
+
+    @property
+    def antialiased(self):
+        """the render was anti-aliased (``ANTIALIASED``)"""
+        return bool(self.flags & ANTIALIASED)
 
     def patch_count(self) -> int:
         """P of this render (waits for its read-back if it has not been looked at yet)."""
@@ -388,8 +400,8 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
     ``need_grad``: a backward pass will follow (the draw kernel then also zeroes its gradient records).
     With ``high_shs`` the inputs are the RAW training tensors (``shs`` = low_shs, ``alphas`` =
     alphas_raw, ``scales`` = scales_raw, ``rots`` = rots_raw) and the activations of
-    gsplat/utils.py:121-150 run inside the kernel (egs_fused_forward_raw).
-    ``antialiased``: the opacity compensation of the 2D filter (egs_fused_forward(_raw)_aa) -- every
+    gsplat/utils.py:121-150 run inside the kernel (``RAW``).
+    ``antialiased``: the opacity compensation of the 2D filter (``ANTIALIASED``) -- every
     Gaussian is binned and drawn with opacity alpha sqrt(det(Sigma) / det(Sigma + 0.3 I)); the state records it and
     ``backward`` follows."""
     raw = high_shs is not None
@@ -417,7 +429,6 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
     S = FusedState()
     S.width, S.height = W, H
     S.ticket, S._patches, S._keep, S.seg, S.extras = None, None, None, None, None
-    S.antialiased = bool(antialiased)
     # the draw kernels (forward and backward) work from the packed records alone: us / cinv2ds / colors /
     # areas are not materialised
     S.us = S.cinv2ds = S.colors = S.areas = None
@@ -425,20 +436,22 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
     # reach, and every list value carries the tile's block mask (include/egs_hip.h EGS_DRAW_CULLED_LISTS).  The
     # lists are internal to this path -- the seven-op surface always returns the reference's.
     pol_ = _pol()
-    S.culled = bool(CULL_LISTS and pol_.footprint == 0 and pol_.alpha_skip > 0 and n < (1 << 28))
+    culled = CULL_LISTS and pol_.footprint == 0 and pol_.alpha_skip > 0 and n < (1 << 28)
+    S.flags = (CULLED_LISTS if culled else 0) | (ANTIALIASED if antialiased else 0) | (RAW if raw else 0)
     S.depths = torch.empty((n,), dtype=f32, device=dev)
     S.rec = torch.empty((max(n, 1), 12), dtype=f32, device=dev)   # packed 2D records, reused by backward
     mask = torch.empty((n,), dtype=torch.bool, device=dev)        # depths > 0.2, written by the kernel
     ws_bin_bytes = lib.egs_splat_bin_ws_bytes(n)
     ws_bin = torch.empty(ws_bin_bytes, dtype=torch.uint8, device=dev)
     host_slot = [None]       # mailbox slot the binning kernels also write {P, max key} into (enqueue-ahead path)
-    tail = lambda hint, total: (_ptr(alphas), _ptr(Rcw), _ptr(tcw), _ptr(twc), float(cam.fx), float(cam.fy),
-                                float(cam.cx), float(cam.cy), W, H, pol, _ptr(S.us), _ptr(S.depths), _ptr(S.cinv2ds),
-                                _ptr(S.colors), _ptr(S.areas), _ptr(S.rec), _ptr(mask), _ptr(S.dcw),
-                                1 if S.culled else 0, hint, _ptr(ws_bin), ws_bin_bytes, _ptr(total), host_slot[0], st)
+    enqueue_bin = lambda hint, total: _lib.check(lib.egs_fused_forward(
+        n, K, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), _ptr(high_shs), _ptr(alphas), _ptr(Rcw), _ptr(tcw),
+        _ptr(twc), float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), W, H, pol, _ptr(S.us), _ptr(S.depths),
+        _ptr(S.cinv2ds), _ptr(S.colors), _ptr(S.areas), _ptr(S.rec), _ptr(mask), _ptr(S.dcw), S.flags, hint,
+        _ptr(ws_bin), ws_bin_bytes, _ptr(total), host_slot[0], st))
     image = torch.empty((3, H, W), dtype=f32, device=dev)       # fully written by the draw stage
     depth_map = alpha_map = None
-    ex = None           # EgsExtras of the draw stage (render extras), None: the plain entry point
+    ex = None           # EgsExtras of the draw stage (render extras), None: a plain render
     if extras is not None:
         S.extras = extras
         if extras.depth:
@@ -447,11 +460,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
             alpha_map = torch.empty((1, H, W), dtype=f32, device=dev)
         ex = _egs_extras(S.depths, extras.background_rgb(), depth_map, alpha_map)
     done = (lambda: (image, mask, S)) if extras is None else (lambda: (image, mask, S, depth_map, alpha_map))
-
-    def draw_rec(*args):
-        if ex is None:
-            return lib.egs_splat_draw_rec_seg(*args)
-        return lib.egs_splat_draw_rec_seg_ex(*args, C.byref(ex))
+    draw_rec = lambda *args: lib.egs_splat_draw_rec_seg(*args, None if ex is None else C.byref(ex))
     S.contrib = torch.empty((H, W), dtype=i32, device=dev)
     S.final_tau = torch.empty((H, W), dtype=f32, device=dev)
     S.ranges = torch.empty((_tiles(W, H), 2), dtype=i32, device=dev)
@@ -478,15 +487,6 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
                                               order_ready, draw_flags, _ptr(S.seg),
                                               S.seg.numel() if S.seg is not None else 0,
                                               None if (redo and walk_word is not None) else seg_hint, _ptr(walk_word), None, st))
-
-    if raw:
-        fwd = lib.egs_fused_forward_raw_aa if S.antialiased else lib.egs_fused_forward_raw
-        enqueue_bin = lambda hint, total: _lib.check(fwd(
-            n, K, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), _ptr(high_shs), *tail(hint, total)))
-    else:
-        fwd = lib.egs_fused_forward_aa if S.antialiased else lib.egs_fused_forward
-        enqueue_bin = lambda hint, total: _lib.check(fwd(
-            n, K, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), *tail(hint, total)))
 
     ctx = _ctx(dev)
     key = (n, W, H)
@@ -550,7 +550,7 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
         with ctx.lock:
             tw[ck] = (ref, S.order, renders, (n, W, H))
     S.order_by_work = prev_work is not None or order_ready == 1
-    draw_flags = (1 if S.culled else 0) | (SEG_HISTORY if (use_seg and walk_known) else 0) | \
+    draw_flags = (1 if culled else 0) | (SEG_HISTORY if (use_seg and walk_known) else 0) | \
         (SEG_SPECULATE_FLAG if (use_seg and getattr(_tls, "seg_speculate", False)) else 0)
     # (SPECULATE with a walk on record: the plan distrusts a record that is far shorter than the tile's list while the
     # scene's recent renders walk most of theirs -- the renders right after reset_alpha, gsmodel.py:320-324)
@@ -744,7 +744,7 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     ``pose`` = (Rcw [3,3], tcw [3]), float32 on the device: the camera of the forward call (``cam.twc`` must be
     -Rcw^T tcw), whose gradient is also formed -> the usual tuple followed by (dloss_dRcw [3,3], dloss_dtcw [3]).  The
     pose gradient belongs to this view: always written, never added to ``accumulate``.  Excludes ``exchange``.
-    An anti-aliased render (``forward(..., antialiased=True)``, recorded in ``S``) takes the AA chain rule."""
+    An anti-aliased render (``forward(..., antialiased=True)``, recorded in ``S.flags``) takes the AA chain rule."""
     raw = high_shs is not None
     pws = _chk(pws, "pws", torch.float32, (None, 3))
     n = pws.shape[0]
@@ -756,6 +756,9 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     alphas = _alphas(alphas, n)
     scales = _chk(scales, "scales", torch.float32, (n, 3))
     rots = _chk(rots, "rots", torch.float32, (n, 4))
+    if raw != bool(S.flags & RAW):
+        raise ValueError("fused.backward: the inputs must have the layout of the forward call (raw tensors with "
+                         "high_shs, or activated ones without)")
     W, H = S.width, S.height
     dl = _chk(dloss_dgammas, "dloss_dgammas", torch.float32, (3, H, W))
     rx = getattr(S, "extras", None)
@@ -823,44 +826,25 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     dus = torch.empty((n, 2), dtype=f32, device=dev)
     ws_bytes = lib.egs_fused_backward_ws_bytes(n)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    mid = (_ptr(alphas), _ptr(Rcw), _ptr(tcw), _ptr(cam.twc), float(cam.fx), float(cam.fy), float(cam.cx),
-           float(cam.cy), C.byref(_pol()), _ptr(S.us), _ptr(S.cinv2ds), _ptr(S.colors), _ptr(S.areas), _ptr(S.rec),
-           _ptr(S.depths), _ptr(S.contrib), _ptr(S.final_tau), _ptr(S.ranges), _ptr(S.gsid), _ptr(dl), _ptr(ws),
-           ws_bytes, _ptr(dpws), _ptr(dshs))
     st = _stream()
     gpack, S.gpack = S.gpack, None      # zeroed by the forward draw kernel: good for ONE backward pass
     seg = getattr(S, "seg", None)       # the forward pass split its long lists: the backward pass walks its segments
     seg_bytes = seg.numel() if seg is not None else 0
-    # (render extras: the _ex entry points with the same arguments and the EgsExtras behind them)
-    tail = () if ex is None else (C.byref(ex),)
-    if pg is not None:      # (pose: the _pose entry points, EgsExtras nullable, then the EgsPoseGrad)
-        tail = (None if ex is None else C.byref(ex), C.byref(pg))
-    if raw:
-        fn = lib.egs_fused_backward_raw if ex is None else lib.egs_fused_backward_raw_ex
-        if pg is not None:
-            fn = lib.egs_fused_backward_raw_pose
-        launch = lambda phase, b, c: _lib.check(fn(
-            n, K, S.gsid.shape[0], W, H, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), _ptr(high_shs), *mid,
-            _ptr(dhigh), _ptr(dalphas), _ptr(dscales), _ptr(drots), _ptr(dus), _ptr(S.order), _ptr(gpack),
-            _ptr(getattr(S, "dcw", None)), phase, b, c, _ptr(seg), seg_bytes, st, *tail))
-    else:
-        fn = lib.egs_fused_backward if ex is None else lib.egs_fused_backward_ex
-        if pg is not None:
-            fn = lib.egs_fused_backward_pose
-        launch = lambda phase, b, c: _lib.check(fn(
-            n, K, S.gsid.shape[0], W, H, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), *mid, _ptr(dalphas),
-            _ptr(dscales), _ptr(drots), _ptr(dus), _ptr(S.order), _ptr(gpack), _ptr(getattr(S, "dcw", None)), phase,
-            b, c, _ptr(seg), seg_bytes, st, *tail))
+    # every phase and chunk carries the render's flags (culled lists, anti-aliased, raw inputs) from the forward's state
+    launch = lambda phase, b, c: _lib.check(lib.egs_fused_backward(
+        n, K, S.gsid.shape[0], W, H, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), _ptr(high_shs), _ptr(alphas),
+        _ptr(Rcw), _ptr(tcw), _ptr(cam.twc), float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy),
+        C.byref(_pol()), _ptr(S.us), _ptr(S.cinv2ds), _ptr(S.colors), _ptr(S.areas), _ptr(S.rec), _ptr(S.depths),
+        _ptr(S.contrib), _ptr(S.final_tau), _ptr(S.ranges), _ptr(S.gsid), _ptr(dl), _ptr(ws), ws_bytes, _ptr(dpws),
+        _ptr(dshs), _ptr(dhigh), _ptr(dalphas), _ptr(dscales), _ptr(drots), _ptr(dus), _ptr(S.order), _ptr(gpack),
+        _ptr(getattr(S, "dcw", None)), phase | S.flags, b, c, _ptr(seg), seg_bytes, st,
+        None if ex is None else C.byref(ex), None if pg is None else C.byref(pg)))
     # the forward pass was dispatched by remembered work: the backward pass keeps its order (no second order kernel)
     keep = KEEP_FORWARD_ORDER if (REUSE_ORDER and getattr(S, "order_by_work", False)) else 0
-    if getattr(S, "culled", False):
-        keep |= CULLED_LISTS          # the list values carry block masks
     if accumulate is not None:
         keep |= ACCUMULATE            # the outputs hold earlier views' gradients: add to them
     if sh_sink is not None:
         keep |= FACTORED_SH
-    if getattr(S, "antialiased", False):
-        keep |= ANTIALIASED           # (from the forward's state: the backward pass can never mismatch it)
     if hook is not None and sh_sink is not None:
         raise RuntimeError("fused.backward: sh_sink and an attached ChunkedExchange exclude each other")
     chunks = hook.chunks if hook is not None else 1
@@ -879,7 +863,7 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
         launch(1 | keep, 0, 0)
         for b in range(0, n, rows):
             c = min(rows, n - b)
-            launch(2 | (keep & (ACCUMULATE | FACTORED_SH | ANTIALIASED)), b, c)
+            launch(2 | (keep & (ACCUMULATE | FACTORED_SH)), b, c)
             hook.on_chunk([p[b:b + c] for p in parts])
     tail = () if pg is None else (dRcw, dtcw)
     if sh_sink is not None:

@@ -607,7 +607,7 @@ def _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep):
                                               flags | seg_flags, _ptr(seg_ws[0]),
                                               seg_ws[0].numel() if use_seg else 0,
                                               None if (redo and walk_word is not None) else seg_hint, _ptr(walk_word),
-                                              _ptr(gsid) if masks else None, st))
+                                              _ptr(gsid) if masks else None, st, None))
         if masks:
             lists[0] = walked
         return gsid
@@ -651,7 +651,7 @@ def _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep):
                                               _ptr(final_tau), _ptr(ranges), _ptr(walked_full), _ptr(order),
                                               _ptr(gpack), None, 0, flags | seg_flags, _ptr(seg_ws[0]),
                                               seg_ws[0].numel() if use_seg else 0, seg_hint, _ptr(walk_word),
-                                              _ptr(gsid_full) if masks else None, st))
+                                              _ptr(gsid_full) if masks else None, st, None))
     except BaseException:
         # Kernels enqueued before the failure (the arm, the binning chain) still store {P, max key} into the slot:
         # it may only go back on the free list once they have run, or a later render that picks it up could settle

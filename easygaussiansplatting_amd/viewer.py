@@ -10,7 +10,7 @@ matrices: 4x4, mathematical convention (``pc = V @ pw``), i.e. what gaussian_ite
 ``set_uniform_mat4`` transposes them for OpenGL.  ``prep`` [N,12] = ``{u 3 (NDC), covinv 3, color 3, area 2,
 alpha}``; rows the shader culls carry ``u = -100`` and are otherwise zero here (the shader leaves stale
 buffer contents).  The OpenGL drawing itself (gau_vert/gau_frag, the bitonic sort) is out of scope.
-``gau_prep(..., antialiased=True)`` (``egs_viewer_prep_aa``) previews a model trained anti-aliased: the alpha column
+``gau_prep(..., antialiased=True)`` (``EGS_FUSED_ANTIALIASED``) previews a model trained anti-aliased: the alpha column
 is alpha times the opacity compensation of the 2D filter, formed from the viewer's own 2D covariance.
 """
 from __future__ import annotations
@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .fused import ANTIALIASED
 
 
 def pack_gs_data(gs) -> np.ndarray:
@@ -47,8 +48,9 @@ def gau_prep(gs_data, view_matrix, projection_matrix, focal, antialiased=False):
     prep = torch.zeros((n, 12), dtype=torch.float32, device=gs_data.device)
     depth = torch.empty((n,), dtype=torch.float32, device=gs_data.device)
     fp = C.POINTER(C.c_float)
-    fn = lib.egs_viewer_prep_aa if antialiased else lib.egs_viewer_prep   # AA: alpha column times comp
-    _lib.check(fn(n, sh_dim, C.c_void_p(gs_data.data_ptr()), V.ctypes.data_as(fp), P.ctypes.data_as(fp),
-                  float(focal[0]), float(focal[1]), C.c_void_p(prep.data_ptr()), C.c_void_p(depth.data_ptr()),
-                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    flags = ANTIALIASED if antialiased else 0   # AA: alpha column times comp
+    _lib.check(lib.egs_viewer_prep(n, sh_dim, C.c_void_p(gs_data.data_ptr()), V.ctypes.data_as(fp),
+                                   P.ctypes.data_as(fp), float(focal[0]), float(focal[1]), C.c_void_p(prep.data_ptr()),
+                                   C.c_void_p(depth.data_ptr()), flags,
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return prep, depth

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define EGS_ABI_VERSION 10
+#define EGS_ABI_VERSION 11
 
 #define EGS_ERR_BAD_ARG 10001
 #define EGS_ERR_WORKSPACE 10002
@@ -267,7 +267,30 @@ int egs_chain_rule(int n, int sh_dim, const float* dloss_dus, const float* dloss
  *   egs_fused_backward  = splatB's draw pass into packed gradient records + ONE kernel that
  *                         re-derives the Jacobians in registers and applies backward.md
  *                         eq (3)(4)(5)(7) (gsmodel.py:71-85).
- * `depths`/`areas` are the arrays egs_fused_forward produced (incl. the in-place culling). */
+ * `depths`/`areas` are the arrays egs_fused_forward produced (incl. the in-place culling).
+ * ABI 11: one forward and one backward entry point; the render's properties are the EGS_FUSED_* bits below, passed
+ * as `flags` of egs_fused_forward and OR-ed into `phase` of egs_fused_backward (the same value for both calls). */
+/* the tile lists are the FOOTPRINT-CULLED ones.  A Gaussian is then listed only for the tiles of its rect (getRects,
+ * kernel.cu:82-122) that its footprint {alpha' >= alpha_skip} can reach -- the tiles left out are tiles in which the
+ * reference `continue`s on every pixel (kernel.cu:246), so images and gradients are unchanged, but list positions
+ * (and with them `contrib`) refer to the culled lists -- and every list value carries, above the low 28 bits of the
+ * Gaussian index, the 4-bit mask of the 8x8 pixel blocks of the tile the footprint reaches; the draw stage takes
+ * EGS_DRAW_CULLED_LISTS.  Needs `rec`.  Internal to the fused path: the seven-op surface (egs_splat_bin /
+ * egs_splat_draw) always produces the reference's lists. */
+#define EGS_FUSED_CULLED_LISTS 32
+/* Anti-aliased rendering (the 2D filter of Mip-Splatting): every Gaussian is binned and drawn with opacity alpha comp,
+ * comp = sqrt(det(Sigma) / det(Sigma + 0.3 I)), Sigma the 2D covariance before the +0.3 dilation (which, like the
+ * radius, stays); comp = 0 when det(Sigma) <= 0 or comp is not finite.  `rec` is required, even for n == 0.  In the
+ * backward pass the draw pass's dL/dalpha is that of the compensated opacity alpha comp; the chain rule applies
+ * dL/dalpha = g comp and adds g alpha dcomp/dcov2d to dL/dcov2d, and with it to the scale, rotation, position and pose
+ * gradients.  Without it a backward pass of an anti-aliased render is wrong. */
+#define EGS_FUSED_ANTIALIASED 256
+/* The inputs are the OPTIMIZER's tensors (gsplat/gsmodel.py:96-129: alphas_raw, scales_raw, rots_raw, low_shs [N,3],
+ * high_shs [N,sh_dim-3]): the activations of gsplat/utils.py:121-150 (sigmoid, exp, normalize, cat) are applied
+ * inside the kernels and the gradients come back with respect to the raw tensors, i.e. GSModel.forward
+ * (gsmodel.py:185-212) + GSFunction in two calls.  `rec` is required (the activated alpha only exists inside the
+ * records).  Without it the inputs are activated: shs is [N][sh_dim] and high_shs must be NULL (EGS_ERR_BAD_ARG). */
+#define EGS_FUSED_RAW 512
 /* rec (nullable): 48 N bytes; receives the packed 2D records of the draw kernels so that
  * egs_splat_draw_rec / egs_fused_backward skip their own packing pass.  With rec given, each of
  * us / cinv2ds / colors / areas may be NULL (they are only needed to continue on the seven-op surface)
@@ -277,12 +300,12 @@ int egs_chain_rule(int n, int sh_dim, const float* dloss_dus, const float* dloss
  * host_totals (nullable): device-visible address of a page-locked host uint32[2] (egs_mailbox_slot) that the
  * binning kernels write {P, max depth key} into as well -- the enqueue-ahead path then needs no copy. */
 int egs_fused_forward(int n, int sh_dim, const float* pws, const float* rots, const float* scales,
-                      const float* shs, const float* alphas, const float* Rcw, const float* tcw,
-                      const float* twc, float fx, float fy, float cx, float cy, int width, int height,
-                      const EgsPolicy* pol, float* us, float* depths, float* cinv2ds, float* colors,
-                      int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws /*nullable*/, int cull_lists,
-                      int key_bits_hint, void* ws_bin, size_t ws_bin_bytes, uint32_t* total_patches,
-                      uint32_t* host_totals, void* stream);
+                      const float* shs, const float* high_shs /*EGS_FUSED_RAW only*/, const float* alphas,
+                      const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx, float cy,
+                      int width, int height, const EgsPolicy* pol, float* us, float* depths, float* cinv2ds,
+                      float* colors, int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws /*nullable*/,
+                      int flags /*EGS_FUSED_* bits*/, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
+                      uint32_t* total_patches, uint32_t* host_totals, void* stream);
 /* dcolor_dpws (nullable, [N][9] floats, 16-B aligned): dcolor/dpw of every Gaussian (what sh2Color's calc_J hands
  * back as dcolor_dpws, gausplat.cu:298-338), kept for the backward pass: egs_fused_backward given the same pointer
  * never reads the SH coefficients again -- eq (7)'s colour term is the only thing it needs them for, dL/dsh needs
@@ -317,7 +340,7 @@ size_t egs_tile_order_len(int width, int height);   /* ints: [forward dispatch o
  * associative on (colour, tau) pairs -- by one wave each where this camera's previous render predicts the walk
  * (flags & EGS_DRAW_SEG_HISTORY: the walk part of tile_order is that render's), sequentially otherwise; either way the
  * workspace then holds, per segment end and pixel, the transmittance and the colour of everything behind it, and
- * egs_fused_backward(_raw) given the SAME workspace walks every segment with a wave of its own (no sequential
+ * egs_fused_backward given the SAME workspace walks every segment with a wave of its own (no sequential
  * dependence is left in the backward pass).  Tile-footprint policies with alpha_skip > 0 and tau_stop > 0 only.
  * Images / contrib / final_tau equal the unsplit kernels' up to the rounding of  sum_s T_s C_s  against one running sum.
  * seg_hint (nullable, page-locked host memory, e.g. a mailbox slot, two words): [0] receives the longest list, [1] the
@@ -344,26 +367,6 @@ size_t egs_seg_ws_bytes(int64_t patch_capacity, int width, int height);
  * and its backward call no longer matters).  A workspace sized under a larger setting than the one planned with simply
  * has fewer slots than tiles could use: tiles that do not fit stay unsplit. */
 int egs_seg_config(int segment_len, int split_min, int* out2);
-int egs_splat_draw_rec_seg(int n, int64_t patches, const uint32_t* total_patches /*nullable*/, int width, int height,
-                           const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
-                           size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
-                           int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order /*nullable*/,
-                           float* grad_records /*nullable*/, const int32_t* prev_tile_work /*nullable*/, int order_ready,
-                           int flags, void* seg_ws /*nullable: the unsplit draw stage*/, size_t seg_ws_bytes,
-                           uint32_t* seg_hint /*nullable*/, int32_t* walk_word /*nullable*/,
-                           int32_t* gsid_plain /*nullable; with EGS_DRAW_MASKED_LISTS: the list without its masks, what
-                                                 the caller of `splat` gets (as egs_splat_draw_rec_plain)*/,
-                           void* stream);
-/* splatB for a host that may or may not have kept what its forward pass left (the seven-op surface: `splatB` is handed
- * tensors).  rec (nullable: packed here from us / cinv2ds / alphas / colors), tile_order / grad_records (nullable: the
- * forward draw's [order | work | walk] buffer and cleared gradient records), flags as egs_splat_bwd_rec_lists.
- * seg_ws == NULL: the unsplit kernel (egs_splat_bwd / egs_splat_bwd_rec_lists).  seg_ws + rebuild == 0: the workspace the
- * forward's egs_splat_draw_rec_seg filled.  seg_ws of egs_seg_rebuild_ws_bytes(patches, ..) + rebuild != 0: nothing
- * was kept -- every tile's walk is read off `contrib`, the forward segment launches run once more over [0, walk) with
- * their pixels going to scratch (they only rebuild the segment-end states: about the cost of a forward draw), then
- * every segment is walked backward by a wave of its own: on scene.skewed_scene after reset_alpha 3.4 ms of one-wave-
- * per-tile backward draw become ~1.2 ms.  seg_hint (nullable): page-locked words that learn the longest walk from
- * either path -- a host decides from them whether its next call brings a workspace. */
 /* Render extras (ABI 10): per pixel, with w_i = T_i alpha'_i the blend weight of the draw kernel (same skip / stop / clamp
  * rules),  depth = sum w_i z_i  (z_i = depths[i], camera-space z; NOT normalised: depth / alpha is the expected depth),
  * alpha = sum w_i = 1 - T_final  (0 on tiles without patches), and  image_c = sum w_i c_i + T_final bg_c.  final_tau keeps
@@ -378,14 +381,26 @@ typedef struct EgsExtras {
   const float* dloss_ddepth;   /* nullable [H][W] */
   const float* dloss_dalpha;   /* nullable [H][W] */
 } EgsExtras;
-/* egs_splat_draw_rec_seg + extras (NULL: exactly the plain call) */
-int egs_splat_draw_rec_seg_ex(int n, int64_t patches, const uint32_t* total_patches /*nullable*/, int width, int height,
-                              const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
-                              size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
-                              int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order,
-                              float* grad_records, const int32_t* prev_tile_work, int order_ready, int flags,
-                              void* seg_ws /*must be NULL with extras*/, size_t seg_ws_bytes, uint32_t* seg_hint,
-                              int32_t* walk_word, int32_t* gsid_plain, void* stream, const EgsExtras* extras);
+int egs_splat_draw_rec_seg(int n, int64_t patches, const uint32_t* total_patches /*nullable*/, int width, int height,
+                           const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
+                           size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
+                           int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order /*nullable*/,
+                           float* grad_records /*nullable*/, const int32_t* prev_tile_work /*nullable*/, int order_ready,
+                           int flags, void* seg_ws /*nullable: the unsplit draw stage*/, size_t seg_ws_bytes,
+                           uint32_t* seg_hint /*nullable*/, int32_t* walk_word /*nullable*/,
+                           int32_t* gsid_plain /*nullable; with EGS_DRAW_MASKED_LISTS: the list without its masks, what
+                                                 the caller of `splat` gets (as egs_splat_draw_rec_plain)*/,
+                           void* stream, const EgsExtras* extras /*nullable; with extras seg_ws must be NULL*/);
+/* splatB for a host that may or may not have kept what its forward pass left (the seven-op surface: `splatB` is handed
+ * tensors).  rec (nullable: packed here from us / cinv2ds / alphas / colors), tile_order / grad_records (nullable: the
+ * forward draw's [order | work | walk] buffer and cleared gradient records), flags as egs_splat_bwd_rec_lists.
+ * seg_ws == NULL: the unsplit kernel (egs_splat_bwd / egs_splat_bwd_rec_lists).  seg_ws + rebuild == 0: the workspace the
+ * forward's egs_splat_draw_rec_seg filled.  seg_ws of egs_seg_rebuild_ws_bytes(patches, ..) + rebuild != 0: nothing
+ * was kept -- every tile's walk is read off `contrib`, the forward segment launches run once more over [0, walk) with
+ * their pixels going to scratch (they only rebuild the segment-end states: about the cost of a forward draw), then
+ * every segment is walked backward by a wave of its own: on scene.skewed_scene after reset_alpha 3.4 ms of one-wave-
+ * per-tile backward draw become ~1.2 ms.  seg_hint (nullable): page-locked words that learn the longest walk from
+ * either path -- a host decides from them whether its next call brings a workspace. */
 size_t egs_seg_rebuild_ws_bytes(int64_t patch_capacity, int width, int height);
 int egs_splat_bwd_seg(int n, int64_t patches, int width, int height, const float* us, const float* cinv2ds,
                       const float* alphas, const float* colors, const void* rec /*nullable*/, const EgsPolicy* pol,
@@ -441,22 +456,14 @@ size_t egs_fused_backward_ws_bytes(int n);
  * (prev_tile_work != NULL), so the backward pass keeps that order instead of sorting the tiles again by the
  * work this render measured (one k_tile_order launch, 8 us, less; without the flag it sorts). */
 #define EGS_BWD_KEEP_FORWARD_ORDER 16
-/* OR-ed into `phase` / passed as `flags` of egs_splat_draw_rec*: the lists are the FOOTPRINT-CULLED ones of
- * egs_fused_forward(cull_lists = 1).  A Gaussian is then listed only for the tiles of its rect (getRects,
- * kernel.cu:82-122) that its footprint {alpha' >= alpha_skip} can reach -- the tiles left out are tiles in which the
- * reference `continue`s on every pixel (kernel.cu:246), so images and gradients are unchanged, but list positions
- * (and with them `contrib`) refer to the culled lists -- and every list value carries, above the low 28 bits of the
- * Gaussian index, the 4-bit mask of the 8x8 pixel blocks of the tile the footprint reaches.  Internal to the fused
- * path: the seven-op surface (egs_splat_bin / egs_splat_draw) always produces the reference's lists. */
-#define EGS_BWD_CULLED_LISTS 32
-/* OR-ed into `phase` of egs_fused_backward(_raw): the parameter-gradient outputs (dloss_dpws, dloss_dshs | low + high,
+/* OR-ed into `phase` of egs_fused_backward: the parameter-gradient outputs (dloss_dpws, dloss_dshs | low + high,
  * dloss_dalphas, dloss_dscales, dloss_drots) already hold the gradients of earlier views of the step; this view's are
  * ADDED to them by the chain-rule kernel (dloss_dus is per view and always written).  Replaces autograd's separate
  * accumulation kernels for a rank that renders several views per step (bench.py --views-per-rank, Trainer.step). */
 #define EGS_BWD_ACCUMULATE 64
-/* OR-ed into `phase` of egs_fused_backward(_raw): the SH gradient of this view stays in its FACTORED form.  Eq (5)
+/* OR-ed into `phase` of egs_fused_backward: the SH gradient of this view stays in its FACTORED form.  Eq (5)
  * (gsmodel.py:84-85: dL/dshs = dL/dcolors @ dcolor/dshs) is an outer product per Gaussian -- dL/dcolour[rgb] times the
- * SH basis of the direction from the camera centre -- so `dloss_dshs` (raw: `dloss_dlow_shs`) receives the THREE
+ * SH basis of the direction from the camera centre -- so `dloss_dshs` (raw: the low [N][3] part) receives the THREE
  * floats dL/dcolour per Gaussian ([N][3]; always written, never accumulated; zero for a Gaussian this view did not
  * draw) FOLLOWED by the view's camera centre twc[3] -- 3 n + 3 floats, one row of egs_sh_grad_views' input -- and
  * `dloss_dhigh_shs` is not touched (may be NULL).  The rows are formed once per step, for all views, by
@@ -464,11 +471,7 @@ size_t egs_fused_backward_ws_bytes(int n);
  * a data-parallel host all-gathers 12 bytes per Gaussian and VIEW instead of all-reducing 4 sh_dim per Gaussian
  * (192 of the 236 bytes of SURVEY 8e's exchange at degree 3). */
 #define EGS_BWD_FACTORED_SH 128
-/* OR-ed into `phase` of every egs_fused_backward* entry point (plain, _raw, _ex, _raw_ex, _pose, _raw_pose): the render
- * was anti-aliased (egs_fused_forward(_raw)_aa), so the draw pass's dL/dalpha is that of the compensated opacity
- * alpha comp; the chain rule applies dL/dalpha = g comp and adds g alpha dcomp/dcov2d to dL/dcov2d, and with it to the
- * scale, rotation, position and pose gradients.  Without it a backward pass of an anti-aliased render is wrong. */
-#define EGS_BWD_ANTIALIASED 256
+/* flags of egs_splat_draw_rec*: the lists are the footprint-culled ones of EGS_FUSED_CULLED_LISTS */
 #define EGS_DRAW_CULLED_LISTS 1
 /* flags of egs_splat_draw_rec* / egs_splat_bwd_rec_lists: the lists are the REFERENCE's complete lists (every tile of
  * every rect, kernel.cu:46-80) whose values carry the same 4-bit block masks above the Gaussian index -- what
@@ -477,102 +480,13 @@ size_t egs_fused_backward_ws_bytes(int n);
  * gradients are unchanged (the pixels skipped are pixels the reference `continue`s on, kernel.cu:246).  The caller
  * hands gsid_per_patch back to ITS caller without the masks (egs_splat_draw_rec_plain, or egs_strip_list_masks). */
 #define EGS_DRAW_MASKED_LISTS 2
-/* phase 0: the whole backward pass.  phase 1: only splatB's draw pass (packed gradient records -> ws).
- * phase 2: only the per-Gaussian chain rule for rows [row_begin, row_begin + row_count), row_begin a multiple
- * of 256, reading the records phase 1 left in the SAME ws: a data-parallel caller launches the rows in a few
- * chunks and hands each chunk's gradients to RCCL while the next chunk is computed (dist_views.ChunkedExchange). */
-int egs_fused_backward(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                       const float* rots, const float* scales, const float* shs, const float* alphas,
-                       const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx,
-                       float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
-                       const float* colors, const int32_t* areas, const void* rec /*nullable*/,
-                       const float* depths,
-                       const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
-                       const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
-                       float* dloss_dpws, float* dloss_dshs, float* dloss_dalphas, float* dloss_dscales,
-                       float* dloss_drots, float* dloss_dus, const int32_t* tile_order /*nullable*/,
-                       float* grad_records /*nullable: zeroed by the forward draw*/,
-                       const float* dcolor_dpws /*nullable: left by egs_fused_forward*/, int phase, int row_begin,
-                       int row_count, void* seg_ws /*nullable: the forward's egs_splat_draw_rec_seg workspace*/,
-                       size_t seg_ws_bytes, void* stream);
-
-/* The same pair on the OPTIMIZER's tensors (gsplat/gsmodel.py:96-129: alphas_raw, scales_raw, rots_raw,
- * low_shs [N,3], high_shs [N,sh_dim-3]): the activations of gsplat/utils.py:121-150 (sigmoid, exp,
- * normalize, cat) are applied inside the kernels and the gradients come back with respect to the raw
- * tensors, i.e. GSModel.forward (gsmodel.py:185-212) + GSFunction in two calls.  `rec` is required (the
- * activated alpha only exists inside the records). */
-int egs_fused_forward_raw(int n, int sh_dim, const float* pws, const float* rots_raw, const float* scales_raw,
-                          const float* low_shs, const float* high_shs, const float* alphas_raw, const float* Rcw,
-                          const float* tcw, const float* twc, float fx, float fy, float cx, float cy, int width,
-                          int height, const EgsPolicy* pol, float* us, float* depths, float* cinv2ds, float* colors,
-                          int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws /*nullable*/,
-                          int cull_lists, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
-                          uint32_t* total_patches, uint32_t* host_totals, void* stream);
-int egs_fused_backward_raw(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                           const float* rots_raw, const float* scales_raw, const float* low_shs,
-                           const float* high_shs, const float* alphas_raw, const float* Rcw, const float* tcw,
-                           const float* twc, float fx, float fy, float cx, float cy, const EgsPolicy* pol,
-                           const float* us, const float* cinv2ds, const float* colors, const int32_t* areas,
-                           const void* rec, const float* depths, const int32_t* contrib, const float* final_tau,
-                           const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
-                           const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
-                           float* dloss_dlow_shs, float* dloss_dhigh_shs, float* dloss_dalphas_raw,
-                           float* dloss_dscales_raw, float* dloss_drots_raw, float* dloss_dus,
-                           const int32_t* tile_order /*nullable*/, float* grad_records /*nullable*/,
-                           const float* dcolor_dpws /*nullable*/, int phase, int row_begin, int row_count,
-                           void* seg_ws /*nullable*/, size_t seg_ws_bytes, void* stream);
-/* Anti-aliased rendering (the 2D filter of Mip-Splatting): egs_fused_forward(_raw) with every Gaussian binned and
- * drawn with opacity alpha comp, comp = sqrt(det(Sigma) / det(Sigma + 0.3 I)), Sigma the 2D covariance before the +0.3
- * dilation (which, like the radius, stays); comp = 0 when det(Sigma) <= 0 or comp is not finite.  The same arguments as
- * the plain pair; `rec` is required (EGS_ERR_BAD_ARG otherwise).  The backward pass of such a render passes
- * EGS_BWD_ANTIALIASED in `phase`. */
-int egs_fused_forward_aa(int n, int sh_dim, const float* pws, const float* rots, const float* scales,
-                         const float* shs, const float* alphas, const float* Rcw, const float* tcw, const float* twc,
-                         float fx, float fy, float cx, float cy, int width, int height, const EgsPolicy* pol,
-                         float* us, float* depths, float* cinv2ds, float* colors, int32_t* areas, void* rec,
-                         uint8_t* visible, float* dcolor_dpws /*nullable*/, int cull_lists, int key_bits_hint,
-                         void* ws_bin, size_t ws_bin_bytes, uint32_t* total_patches, uint32_t* host_totals,
-                         void* stream);
-int egs_fused_forward_raw_aa(int n, int sh_dim, const float* pws, const float* rots_raw, const float* scales_raw,
-                             const float* low_shs, const float* high_shs, const float* alphas_raw, const float* Rcw,
-                             const float* tcw, const float* twc, float fx, float fy, float cx, float cy, int width,
-                             int height, const EgsPolicy* pol, float* us, float* depths, float* cinv2ds,
-                             float* colors, int32_t* areas, void* rec, uint8_t* visible,
-                             float* dcolor_dpws /*nullable*/, int cull_lists, int key_bits_hint, void* ws_bin,
-                             size_t ws_bin_bytes, uint32_t* total_patches, uint32_t* host_totals, void* stream);
-/* egs_fused_backward / egs_fused_backward_raw of a render with extras: the EgsExtras of the forward call (depths,
- * background) with dloss_ddepth / dloss_dalpha; dL/dz is added to dloss_dpws.  extras == NULL: the plain call. */
-int egs_fused_backward_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                          const float* rots, const float* scales, const float* shs, const float* alphas,
-                          const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx,
-                          float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
-                          const float* colors, const int32_t* areas, const void* rec, const float* depths,
-                          const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
-                          const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
-                          float* dloss_dpws, float* dloss_dshs, float* dloss_dalphas, float* dloss_dscales,
-                          float* dloss_drots, float* dloss_dus, const int32_t* tile_order, float* grad_records,
-                          const float* dcolor_dpws, int phase, int row_begin, int row_count, void* seg_ws,
-                          size_t seg_ws_bytes, void* stream, const EgsExtras* extras);
-int egs_fused_backward_raw_ex(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                              const float* rots_raw, const float* scales_raw, const float* low_shs,
-                              const float* high_shs, const float* alphas_raw, const float* Rcw, const float* tcw,
-                              const float* twc, float fx, float fy, float cx, float cy, const EgsPolicy* pol,
-                              const float* us, const float* cinv2ds, const float* colors, const int32_t* areas,
-                              const void* rec, const float* depths, const int32_t* contrib, const float* final_tau,
-                              const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
-                              const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
-                              float* dloss_dlow_shs, float* dloss_dhigh_shs, float* dloss_dalphas_raw,
-                              float* dloss_dscales_raw, float* dloss_drots_raw, float* dloss_dus,
-                              const int32_t* tile_order, float* grad_records, const float* dcolor_dpws, int phase,
-                              int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
-                              const EgsExtras* extras);
-/* Camera pose gradients.  egs_fused_backward(_raw)_pose take the arguments of their _ex counterpart (extras nullable),
- * write every output of it, and also dL/dRcw [3][3] (row-major) and dL/dtcw [3] of this view -- always written, never
- * added to, whatever EGS_BWD_ACCUMULATE says of the per-Gaussian outputs.  The camera centre is treated as
- * twc = -Rcw^T tcw (the rotation convention; equal to -inv(Rcw) tcw on a true rotation): the caller passes that twc,
- * and its gradient is folded into dL/dRcw and dL/dtcw.  Near-culled Gaussians contribute nothing.  The base phase must
- * be 0 (EGS_ERR_BAD_ARG otherwise); ws of fewer than egs_pose_ws_bytes(n) bytes gives EGS_ERR_WORKSPACE.  The result
- * is bitwise reproducible: one partial row per workgroup of the chain-rule kernel, summed in a fixed order in double. */
+/* Camera pose gradients (`pose` of egs_fused_backward, nullable): dL/dRcw [3][3] (row-major) and dL/dtcw [3] of this
+ * view -- always written, never added to, whatever EGS_BWD_ACCUMULATE says of the per-Gaussian outputs.  The camera
+ * centre is treated as twc = -Rcw^T tcw (the rotation convention; equal to -inv(Rcw) tcw on a true rotation): the caller
+ * passes that twc, and its gradient is folded into dL/dRcw and dL/dtcw.  Near-culled Gaussians contribute nothing.  The
+ * base phase must be 0 (EGS_ERR_BAD_ARG otherwise); ws of fewer than egs_pose_ws_bytes(n) bytes gives
+ * EGS_ERR_WORKSPACE.  The result is bitwise reproducible: one partial row per workgroup of the chain-rule kernel, summed
+ * in a fixed order in double. */
 typedef struct EgsPoseGrad {
   float* dloss_dRcw;   /* [3][3] */
   float* dloss_dtcw;   /* [3] */
@@ -580,31 +494,29 @@ typedef struct EgsPoseGrad {
   size_t ws_bytes;
 } EgsPoseGrad;
 size_t egs_pose_ws_bytes(int n);
-int egs_fused_backward_pose(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                            const float* rots, const float* scales, const float* shs, const float* alphas,
-                            const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx,
-                            float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
-                            const float* colors, const int32_t* areas, const void* rec, const float* depths,
-                            const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
-                            const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
-                            float* dloss_dpws, float* dloss_dshs, float* dloss_dalphas, float* dloss_dscales,
-                            float* dloss_drots, float* dloss_dus, const int32_t* tile_order, float* grad_records,
-                            const float* dcolor_dpws, int phase, int row_begin, int row_count, void* seg_ws,
-                            size_t seg_ws_bytes, void* stream, const EgsExtras* extras /*nullable*/,
-                            const EgsPoseGrad* pose);
-int egs_fused_backward_raw_pose(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
-                                const float* rots_raw, const float* scales_raw, const float* low_shs,
-                                const float* high_shs, const float* alphas_raw, const float* Rcw, const float* tcw,
-                                const float* twc, float fx, float fy, float cx, float cy, const EgsPolicy* pol,
-                                const float* us, const float* cinv2ds, const float* colors, const int32_t* areas,
-                                const void* rec, const float* depths, const int32_t* contrib, const float* final_tau,
-                                const int32_t* patch_range_per_tile, const int32_t* gsid_per_patch,
-                                const float* dloss_dgammas, void* ws, size_t ws_bytes, float* dloss_dpws,
-                                float* dloss_dlow_shs, float* dloss_dhigh_shs, float* dloss_dalphas_raw,
-                                float* dloss_dscales_raw, float* dloss_drots_raw, float* dloss_dus,
-                                const int32_t* tile_order, float* grad_records, const float* dcolor_dpws, int phase,
-                                int row_begin, int row_count, void* seg_ws, size_t seg_ws_bytes, void* stream,
-                                const EgsExtras* extras /*nullable*/, const EgsPoseGrad* pose);
+/* phase 0: the whole backward pass.  phase 1: only splatB's draw pass (packed gradient records -> ws).
+ * phase 2: only the per-Gaussian chain rule for rows [row_begin, row_begin + row_count), row_begin a multiple
+ * of 256, reading the records phase 1 left in the SAME ws: a data-parallel caller launches the rows in a few
+ * chunks and hands each chunk's gradients to RCCL while the next chunk is computed (dist_views.ChunkedExchange).
+ * OR-ed into the phase: the forward's EGS_FUSED_* flags (every chunk) and the EGS_BWD_* bits of this call.
+ * Without EGS_FUSED_RAW, shs_high and dloss_dhigh_shs are NULL; with it the gradients are those of the raw tensors.
+ * extras (nullable): the EgsExtras of the forward's draw (depths, background) with dloss_ddepth / dloss_dalpha;
+ * dL/dz is added to dloss_dpws.  pose (nullable): also the camera pose gradient (EgsPoseGrad). */
+int egs_fused_backward(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
+                       const float* rots, const float* scales, const float* shs, const float* shs_high,
+                       const float* alphas, const float* Rcw, const float* tcw, const float* twc, float fx, float fy,
+                       float cx, float cy, const EgsPolicy* pol, const float* us, const float* cinv2ds,
+                       const float* colors, const int32_t* areas, const void* rec /*nullable*/, const float* depths,
+                       const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
+                       const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
+                       float* dloss_dpws, float* dloss_dshs, float* dloss_dhigh_shs, float* dloss_dalphas,
+                       float* dloss_dscales, float* dloss_drots, float* dloss_dus,
+                       const int32_t* tile_order /*nullable*/,
+                       float* grad_records /*nullable: zeroed by the forward draw*/,
+                       const float* dcolor_dpws /*nullable: left by egs_fused_forward*/, int phase, int row_begin,
+                       int row_count, void* seg_ws /*nullable: the forward's egs_splat_draw_rec_seg workspace*/,
+                       size_t seg_ws_bytes, void* stream, const EgsExtras* extras /*nullable*/,
+                       const EgsPoseGrad* pose /*nullable*/);
 /* The SH-coefficient gradient of a step from the factored form EGS_BWD_FACTORED_SH leaves:
  *     dloss_dshs[i][c][rgb] (+)= scale * sum_v  rows[v][3 i + rgb] * basis_c(pws[i] - twc_v)
  * rows: `views` rows of `row_stride` floats, row v = { dL/dcolour of view v [N][3], twc_v[3], padding } -- this rank's
@@ -708,15 +620,12 @@ int egs_nn_sqdist(int n, const float* points, void* ws, size_t ws_bytes, float* 
  * gs_data [n, 11 + sh_dim] = {pos 3, rot 4, scale 3, alpha, sh} -> gs_prep [n,12] = {u 3 (NDC), covinv 3,
  * color 3, area 2, alpha} and depth [n] (view-space z, the viewer's sort key).  Culled rows (|u.xy| > 1.3,
  * |u.z| > 1, det == 0) only get u = -100; the rest of the row is left untouched, as the shader does.
- * view_matrix / projection_matrix: HOST float[16], row-major, mathematical convention (pc = V pw). */
+ * view_matrix / projection_matrix: HOST float[16], row-major, mathematical convention (pc = V pw).
+ * flags = EGS_FUSED_ANTIALIASED, for a model trained anti-aliased: the alpha column is alpha comp, comp the opacity
+ * compensation of the anti-aliased render formed from the viewer's (unclamped) 2D covariance. */
 int egs_viewer_prep(int n, int sh_dim, const float* gs_data, const float* view_matrix,
                     const float* projection_matrix, float focal_x, float focal_y, float* gs_prep, float* depth,
-                    void* stream);
-/* egs_viewer_prep for a model trained anti-aliased: the same arguments; the alpha column is alpha comp, comp the opacity
- * compensation of egs_fused_forward_aa formed from the viewer's (unclamped) 2D covariance. */
-int egs_viewer_prep_aa(int n, int sh_dim, const float* gs_data, const float* view_matrix,
-                       const float* projection_matrix, float focal_x, float focal_y, float* gs_prep, float* depth,
-                       void* stream);
+                    int flags /*0 or EGS_FUSED_ANTIALIASED*/, void* stream);
 
 /* ---- per-kernel timing with HIP events on the launch stream ---------------
  * bench.py's `roofline` leg: when enabled, every kernel launch of this library

@@ -13,7 +13,8 @@ from oracle import gs_oracle as O
 from tests import aa_ref
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("egs_fused_forward_aa", "egs_fused_forward_raw_aa", "egs_viewer_prep_aa")
+# ABI 11 folded the anti-aliased entry points into egs_fused_forward / egs_viewer_prep (flag EGS_FUSED_ANTIALIASED)
+REMOVED_SYMBOLS = ("egs_fused_forward_aa", "egs_fused_forward_raw_aa", "egs_viewer_prep_aa")
 
 
 def _spd(rng, n, lo, hi):
@@ -135,17 +136,19 @@ def test_trainer_refuses_antialiased_ops_mode():
 
 
 # ------------------------------------------------------------------------------------------------------ 4. C ABI
-def test_antialiased_abi():
+def test_antialiased_flag_abi():
     from easygaussiansplatting_amd import _lib, fused
     hdr = open(os.path.join(REPO, "include", "egs_hip.h")).read()
-    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 10
-    for name in NEW_SYMBOLS:
-        assert ("int %s(" % name) in hdr and name in _lib.SIGNATURES, name
-    # the same arguments as the plain entry points
-    for name in NEW_SYMBOLS:
-        assert _lib.SIGNATURES[name] == _lib.SIGNATURES[name[:-3]], name
-    bits = {k: int(v) for k, v in re.findall(r"#define (EGS_BWD_\w+) (\d+)", hdr)}
-    aa = bits.pop("EGS_BWD_ANTIALIASED")
+    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 11
+    for name in REMOVED_SYMBOLS:
+        assert name not in hdr and name not in _lib.SIGNATURES, name
+    # the flag rides on the one forward entry point (`flags`) and the viewer's (`flags`, in front of the stream)
+    assert "int egs_fused_forward(" in hdr and "int egs_viewer_prep(" in hdr
+    assert _lib.SIGNATURES["egs_viewer_prep"][1][-2:] == [C.c_int, C.c_void_p]
+    # the render flags share `phase` with the per-call backward bits: one bit each, none overlapping
+    bits = {k: int(v) for k, v in re.findall(r"#define (EGS_(?:BWD|FUSED)_\w+) (\d+)", hdr)}
+    assert "EGS_BWD_ANTIALIASED" not in bits and "EGS_BWD_CULLED_LISTS" not in bits
+    aa = bits.pop("EGS_FUSED_ANTIALIASED")
     assert aa == 256 == fused.ANTIALIASED and aa & (aa - 1) == 0
     assert aa & 3 == 0                                  # the base phase 0 / 1 / 2
     for k, v in bits.items():
@@ -161,26 +164,60 @@ def lib():
     return _lib.load()
 
 
-def test_antialiased_exports(lib):
+def test_antialiased_variants_folded_in_exports(lib):
     from easygaussiansplatting_amd import _lib
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    for name in NEW_SYMBOLS:
-        assert name in exported, name
-    assert lib.egs_abi_version() == 10
+    for name in REMOVED_SYMBOLS:
+        assert name not in exported, name
+    assert "egs_fused_forward" in exported and "egs_viewer_prep" in exported
+    assert lib.egs_abi_version() == 11
 
 
-def test_antialiased_forward_requires_records(lib):
-    """rec == NULL is refused by the C ABI before anything reaches the device"""
+def _forward(lib, n, flags, high, rec):
+    """egs_fused_forward on fake pointers (every call here is refused before one is dereferenced)"""
     from easygaussiansplatting_amd import _lib
     pol = _lib.EgsPolicy()
     lib.egs_policy_gsplatcu(C.byref(pol))
     dummy = C.c_void_p(16)
-    total = C.c_void_p(16)
-    for fn, nptr in ((lib.egs_fused_forward_aa, 8), (lib.egs_fused_forward_raw_aa, 9)):
-        args = [1000, 3] + [dummy] * nptr + [256.0, 256.0, 128.0, 128.0, 256, 256, C.byref(pol)]
-        # us, depths, cinv2ds, colors, areas, rec (NULL), visible, dcolor_dpws
-        args += [dummy, dummy, dummy, dummy, dummy, None, dummy, None]
-        args += [0, 32, dummy, 1 << 20, total, None, None]
-        assert fn(*args) == 10001
-        assert "rec" in lib.egs_last_error_string().decode()
+    # pws, rots, scales, shs | low_shs, high_shs, alphas, Rcw, tcw, twc
+    args = [n, 3 if high is None else 12] + [dummy] * 4 + [high] + [dummy] * 4
+    args += [256.0, 256.0, 128.0, 128.0, 256, 256, C.byref(pol)]
+    # us, depths, cinv2ds, colors, areas, rec, visible, dcolor_dpws
+    args += [dummy, dummy, dummy, dummy, dummy, rec, dummy, None]
+    args += [flags, 32, dummy, 1 << 20, dummy, None, None]
+    return lib.egs_fused_forward(*args)
+
+
+def test_antialiased_flag_requires_records(lib):
+    """rec == NULL is refused by the C ABI before anything reaches the device, for activated and raw inputs, n == 0
+    included"""
+    from easygaussiansplatting_amd import fused
+    for n in (1000, 0):
+        for flags, high in ((fused.ANTIALIASED, None), (fused.ANTIALIASED | fused.RAW, C.c_void_p(16))):
+            assert _forward(lib, n, flags, high, None) == 10001
+            assert "rec" in lib.egs_last_error_string().decode()
+
+
+def test_forward_flags_are_checked(lib):
+    """high_shs belongs to raw inputs; bits outside the EGS_FUSED_* set are refused; so is a raw render without rec"""
+    from easygaussiansplatting_amd import fused
+    dummy = C.c_void_p(16)
+    assert _forward(lib, 1000, 0, dummy, dummy) == 10001
+    assert "shs_high" in lib.egs_last_error_string().decode()
+    assert _forward(lib, 1000, fused.ANTIALIASED, dummy, dummy) == 10001
+    assert _forward(lib, 1000, fused.RAW, dummy, None) == 10001
+    assert "rec" in lib.egs_last_error_string().decode()
+    assert _forward(lib, 1000, 1, None, dummy) == 10001
+    assert _forward(lib, 1000, 1024, None, dummy) == 10001
+
+
+def test_viewer_prep_flags_are_checked(lib):
+    """egs_viewer_prep takes EGS_FUSED_ANTIALIASED and nothing else"""
+    from easygaussiansplatting_amd import fused
+    m = (C.c_float * 16)(*np.eye(4, dtype=np.float32).ravel())
+    dummy = C.c_void_p(16)
+    for flags in (fused.CULLED_LISTS, fused.RAW, fused.ANTIALIASED | 1):
+        assert lib.egs_viewer_prep(10, 3, dummy, m, m, 100.0, 100.0, dummy, dummy, flags, None) == 10001
+    # n == 0: nothing to launch, and the flag is accepted
+    assert lib.egs_viewer_prep(0, 3, None, m, m, 100.0, 100.0, None, None, fused.ANTIALIASED, None) == 0

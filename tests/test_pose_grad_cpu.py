@@ -130,21 +130,21 @@ def lib():
     return _lib.load()
 
 
-def test_pose_exports_and_signatures(lib):
+def test_pose_argument_of_fused_backward(lib):
     from easygaussiansplatting_amd import _lib
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    for name in ("egs_pose_ws_bytes", "egs_fused_backward_pose", "egs_fused_backward_raw_pose"):
+    for name in ("egs_pose_ws_bytes", "egs_fused_backward"):
         assert name in exported and name in _lib.SIGNATURES, name
-    # the pose entry points take their _ex counterpart's arguments, then the EgsPoseGrad
-    for base in ("egs_fused_backward_ex", "egs_fused_backward_raw_ex"):
-        pose = base[:-3] + "_pose"
-        assert _lib.SIGNATURES[pose][1] == _lib.SIGNATURES[base][1] + [C.POINTER(_lib.EgsPoseGrad)]
-        assert _lib.SIGNATURES[pose][0] == _lib.SIGNATURES[base][0]
+    # ABI 11: the pose is the last, nullable argument of egs_fused_backward, behind the EgsExtras
+    for name in ("egs_fused_backward_pose", "egs_fused_backward_raw_pose"):
+        assert name not in exported and name not in _lib.SIGNATURES, name
+    assert _lib.SIGNATURES["egs_fused_backward"][1][-2:] == [C.POINTER(_lib.EgsExtras), C.POINTER(_lib.EgsPoseGrad)]
+    assert _lib.SIGNATURES["egs_fused_backward"][0] is C.c_int
     assert C.sizeof(_lib.EgsPoseGrad) == 32
     assert [f for f, _ in _lib.EgsPoseGrad._fields_] == ["dloss_dRcw", "dloss_dtcw", "ws", "ws_bytes"]
-    assert lib.egs_abi_version() == 10 and C.sizeof(_lib.EgsExtras) == 56
+    assert lib.egs_abi_version() == 11 and C.sizeof(_lib.EgsExtras) == 56
 
 
 def test_pose_ws_bytes_is_monotone(lib):
@@ -154,24 +154,28 @@ def test_pose_ws_bytes_is_monotone(lib):
     assert lib.egs_pose_ws_bytes(257) >= 2 * 16 * 4
 
 
-def test_pose_bad_arguments_are_refused_before_the_device(lib):
+def test_pose_argument_refusals_before_the_device(lib):
     """phase != 0 with a pose, a missing or short pose workspace: refused by the C ABI before anything is read"""
-    from easygaussiansplatting_amd import _lib
+    from easygaussiansplatting_amd import _lib, fused
     n = 1000
     pol = _lib.EgsPolicy()
     lib.egs_policy_gsplatcu(C.byref(pol))
     fake = C.c_void_p(256)      # never dereferenced: every check below fails first
 
-    def call(phase, pg):
-        args = [n, 3, 0, 64, 64] + [fake] * 8 + [256.0, 256.0, 32.0, 32.0] + [C.byref(pol)] + [fake] * 11 + \
-            [fake, 1 << 30] + [fake] * 6 + [None, None, None, phase, 0, n, None, 0, None, None, C.byref(pg)]
-        return lib.egs_fused_backward_pose(*args)
+    def call(phase, pg, raw):
+        # shs_high / dloss_dhigh_shs: the raw layout only
+        high, flags = (fake, fused.RAW) if raw else (None, 0)
+        args = [n, 12, 0, 64, 64] + [fake] * 4 + [high] + [fake] * 4 + [256.0, 256.0, 32.0, 32.0] + \
+            [C.byref(pol)] + [fake] * 11 + [fake, 1 << 30] + [fake, fake, high] + [fake] * 4 + \
+            [None, None, None, phase | flags, 0, n, None, 0, None, None, C.byref(pg)]
+        return lib.egs_fused_backward(*args)
     ok_ws = lib.egs_pose_ws_bytes(n)
-    assert call(1, _lib.EgsPoseGrad(256, 256, 256, ok_ws)) == 10001      # EGS_ERR_BAD_ARG
-    assert call(2, _lib.EgsPoseGrad(256, 256, 256, ok_ws)) == 10001
-    assert call(0, _lib.EgsPoseGrad(256, 256, 256, ok_ws - 1)) == 10002  # EGS_ERR_WORKSPACE
-    assert call(0, _lib.EgsPoseGrad(256, 256, None, ok_ws)) == 10002
-    assert call(0, _lib.EgsPoseGrad(None, 256, 256, ok_ws)) == 10001
+    for raw in (False, True):
+        assert call(1, _lib.EgsPoseGrad(256, 256, 256, ok_ws), raw) == 10001      # EGS_ERR_BAD_ARG
+        assert call(2, _lib.EgsPoseGrad(256, 256, 256, ok_ws), raw) == 10001
+        assert call(0, _lib.EgsPoseGrad(256, 256, 256, ok_ws - 1), raw) == 10002  # EGS_ERR_WORKSPACE
+        assert call(0, _lib.EgsPoseGrad(256, 256, None, ok_ws), raw) == 10002
+        assert call(0, _lib.EgsPoseGrad(None, 256, 256, ok_ws), raw) == 10001
 
 
 def _cpu_inputs(n=8):

@@ -29,22 +29,25 @@ def test_render_options_extras_validation():
             RenderOptions(background=bad)
 
 
-def test_extras_exports_and_abi_version():
+def test_extras_arguments_and_abi_version():
     from easygaussiansplatting_amd import _lib
     hdr = open(os.path.join(REPO, "include", "egs_hip.h")).read()
-    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 10
-    for name in ("egs_splat_draw_rec_seg_ex", "egs_fused_backward_ex", "egs_fused_backward_raw_ex"):
-        assert name in _lib.SIGNATURES and ("int %s(" % name) in hdr
-        # one more argument than the plain entry point: the trailing EgsExtras*
-        assert len(_lib.SIGNATURES[name][1]) == len(_lib.SIGNATURES[name[:-3]][1]) + 1
-        assert _lib.SIGNATURES[name][1][-1] is C.POINTER(_lib.EgsExtras)
+    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 11
+    # ABI 11: the EgsExtras* is a nullable argument of the draw and backward entry points, not separate _ex ones
+    removed = ("egs_splat_draw_rec_seg_ex", "egs_fused_backward_ex", "egs_fused_backward_raw_ex")
+    for name in removed:
+        assert name not in _lib.SIGNATURES and name not in hdr
+    assert _lib.SIGNATURES["egs_splat_draw_rec_seg"][1][-1] is C.POINTER(_lib.EgsExtras)
+    assert _lib.SIGNATURES["egs_fused_backward"][1][-2] is C.POINTER(_lib.EgsExtras)
     # the ctypes mirror has the C layout: 3 pointers, 3 floats (+4 padding), 2 pointers
     f = dict((n, getattr(_lib.EgsExtras, n).offset) for n, _ in _lib.EgsExtras._fields_)
     assert f["background"] == 24 and f["dloss_ddepth"] == 40 and C.sizeof(_lib.EgsExtras) == 56
     if os.path.exists(_lib.LIB_PATH):
         out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-        for name in ("egs_splat_draw_rec_seg_ex", "egs_fused_backward_ex", "egs_fused_backward_raw_ex"):
-            assert name in out
+        exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+        assert "egs_splat_draw_rec_seg" in exported and "egs_fused_backward" in exported
+        for name in removed:
+            assert name not in exported
 
 
 def _tiny():
