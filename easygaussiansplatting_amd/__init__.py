@@ -6,6 +6,7 @@ around it, on hand-written HIP kernels for gfx950 behind a C ABI (``include/egs_
     function   GSFunction (autograd boundary of gsmodel.py), GSRawFunction (GSModel.forward in one node),
                GSPoseFunction / GSRawPoseFunction (the same with camera pose gradients), render
     fused      the fused forward / backward behind GSFunction
+    _ahead     per-device render scheduling and the enqueue-ahead protocol both of them drive;  _host  plumbing
     loss       gau_loss (0.8 L1 + 0.2 (1 - SSIM)) as HIP kernels
     optim      FusedAdam;  density  DensityControl (prune / clone / split / alpha reset on the device)
     trainer    the train.py loop, one camera view per GPU;  dist_views  the RCCL gradient exchange

@@ -17,15 +17,16 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import os
-import threading
 import weakref
 
 import torch
 
-from . import _lib
-from . import gsplatcu as _gsc
+from . import _ahead, _lib
+# (re-exported: the scheduling state's public names, and what tests and lab tools reach through this module)
+from ._ahead import (_ctx, _seg_decision, _settle, _tls, _walk_word,  # noqa: F401
+                     commit, deferred, expect_long_walks, seg_hint)  # noqa: F401
+from ._host import _alphas, _chk, _lib_on, _pol, _ptr, _stream, _tiles
 from .dist_views import flat_grad_buffer  # noqa: F401  (re-exported: the buffer is allocated here)
-from .gsplatcu import _alphas, _bin_stage, _chk, _lib_on, _pol, _ptr, _stream, _tiles
 
 
 ENQUEUE_AHEAD = os.environ.get("EGS_ENQUEUE_AHEAD", "1") != "0"   # knob for A/B measurements and tests
@@ -39,6 +40,9 @@ CULL_LISTS = os.environ.get("EGS_CULL_LISTS", "1") != "0"            # A/B knob:
 # long tile lists split over several waves (include/egs_hip.h egs_splat_draw_rec_seg): "auto" = whenever the longest list
 # of the scene's last render exceeded the split threshold (and at first sight), "1" always, "0" never
 SEGMENTS = os.environ.get("EGS_SEGMENTS", "auto")
+# egs_splat_draw_rec_seg's `flags` (both surfaces)
+DRAW_CULLED_LISTS = 1     # include/egs_hip.h EGS_DRAW_CULLED_LISTS
+DRAW_MASKED_LISTS = 2     # include/egs_hip.h EGS_DRAW_MASKED_LISTS (egs_splat_bwd_seg takes it too)
 SEG_HISTORY = 4           # include/egs_hip.h EGS_DRAW_SEG_HISTORY
 SEG_SPECULATE_FLAG = 8    # include/egs_hip.h EGS_DRAW_SEG_SPECULATE
 # a camera without a walk on record on the segment path: "auto" = all its segments at once when the scene's recent renders
@@ -51,8 +55,6 @@ CULLED_LISTS = 32         # include/egs_hip.h EGS_FUSED_CULLED_LISTS
 ANTIALIASED = 256         # include/egs_hip.h EGS_FUSED_ANTIALIASED
 RAW = 512                 # include/egs_hip.h EGS_FUSED_RAW
 GSID_MASK = 0x0FFFFFFF    # csrc/egs_common.h EGS_GSID_MASK
-MAILBOX_SLOTS = 64
-HINT_SLOTS = 16           # problem sizes that keep a hint slot (longest list / longest walk of their recent renders)
 
 
 class FusedState:
@@ -129,259 +131,8 @@ def pose_tensors(Rcw, tcw, like):
     return Rcw.contiguous(), tcw.contiguous()
 
 
-class _Ticket:
-    """One enqueue-ahead render whose {P, max depth key} read-back is still in flight."""
-    __slots__ = ("ctx", "slot", "key", "cap", "hint", "state", "status", "patches", "need", "collected")
-    PENDING, OK, FAILED = 0, 1, 2
-
-
-class _DeviceCtx:
-    """Per-device host state of the fused path: the mailbox, what was learnt about each problem size
-    (patch-list capacity, significant depth-key bits) and the renders awaiting validation.  Nothing here
-    is shared between devices; access is serialised by ``lock`` (autograd runs backward on its own thread)."""
-
-    def __init__(self, lib, index):
-        self.index = index
-        self.lib = lib
-        self.mb = lib.egs_mailbox_create(MAILBOX_SLOTS)
-        if not self.mb:
-            raise RuntimeError("egs_mailbox_create failed (page-locked host memory)")
-        self.free = list(range(MAILBOX_SLOTS))
-        self.pending = collections.deque()
-        self.failed = []
-        self.capacity = {}      # (N, W, H) -> patch-list allocation size learnt from earlier renders
-        # (camera, stream) -> (weakref, its [order | work] buffer, renders so far, problem size): the dispatch order
-        # of the tiles is kept between the renders of a camera (a trainer meets every view again each epoch)
-        self.tile_work = {}
-        self.seg_hint = {}      # (N, W, H) -> mailbox slot kept as the landing zone of "longest list of the last render"
-        # ((N, W, H), stream) -> one persistent int32 device word (-1 = nothing gathered): the draw items of a render
-        # gather its longest walk there, the next render on that stream publishes it into the hint slot (egs_hip.h)
-        self.walk_word = {}
-        self.long_walks_expected = 0   # renders for which a caller announced long walks (expect_long_walks)
-        self.lock = threading.RLock()
-
-
-_contexts = {}
-_tls = threading.local()
 _exchange_hook = None    # dist_views.ChunkedExchange while attached (process-wide: backward runs on autograd's thread)
 _sh_sink = None          # dist_views.FactoredShGrad while attached: the SH gradient of a view stays dL/dcolour [N,3]
-
-
-def _ctx(dev) -> _DeviceCtx:
-    c = _contexts.get(dev.index)
-    if c is None:
-        c = _contexts.setdefault(dev.index, _DeviceCtx(_lib.load(), dev.index))
-    return c
-
-
-def _grow(p):
-    return p + p // 16 + 4096
-
-
-SIZE_TABLE_MAX = 1024    # problem sizes (N, W, H) a process remembers a patch capacity / depth-key hint for
-
-
-def _learn_capacity(ctx, key, patches):
-    """Raise the enqueue-ahead patch capacity of a problem size (ctx.lock held by the caller or not needed: one dict
-    store); the table is bounded -- a process that meets ever new sizes (a densifying trainer: one per densification; a
-    server rendering many scenes) forgets the sizes it met first."""
-    cap = ctx.capacity
-    val = max(cap.pop(key, 0), _grow(min(patches, 2**31 - 1)))
-    cap[key] = val                                      # (re-inserted: most recently learnt)
-    while len(cap) > SIZE_TABLE_MAX:
-        cap.pop(next(iter(cap)), None)
-
-
-def _settle(t: _Ticket, blocking: bool) -> bool:
-    """Look at the read-back of one render: True once it has been validated (either way)."""
-    ctx = t.ctx
-    with ctx.lock:
-        if t.status != _Ticket.PENDING:
-            return True
-        out = (C.c_uint32 * 2)()
-    rc = ctx.lib.egs_mailbox_fetch(ctx.mb, t.slot, 1 if blocking else 0, out)   # (the wait holds no lock, no GIL)
-    if rc == 0:
-        return False
-    if rc < 0:
-        # the slot never received its values (a HIP error behind the binning stage): the ticket is settled as
-        # FAILED and its slot handed back, so that later commit() calls do not trip over it again
-        with ctx.lock:
-            if t.status == _Ticket.PENDING:
-                t.status, t.patches, t.need = _Ticket.FAILED, 0, 0
-                ctx.free.append(t.slot)
-                try:
-                    ctx.pending.remove(t)
-                except ValueError:
-                    pass
-                if t.state is not None:
-                    t.state.ticket = None
-                    t.state._patches = 0
-        _lib.check(-rc)
-    with ctx.lock:
-        if t.status != _Ticket.PENDING:
-            return True
-        t.patches, mk = int(out[0]), int(out[1])
-        t.need = mk.bit_length()
-        ctx.free.append(t.slot)
-        try:
-            ctx.pending.remove(t)
-        except ValueError:
-            pass
-        ok = t.patches <= t.cap and not (t.hint < 32 and t.need > t.hint) and t.patches < 2**31
-        # what the next render of this size starts from
-        _gsc._learn_key_bits(ctx.index, t.key, t.need, missed=(t.hint < 32 and t.need > t.hint))
-        _learn_capacity(ctx, t.key, t.patches)
-        t.status = _Ticket.OK if ok else _Ticket.FAILED
-        S = t.state
-        if S is not None:
-            S._patches = t.patches
-            S.ticket = None
-            if ok:
-                S.gsid = S.gsid[:t.patches]
-        if not ok and not t.collected:
-            ctx.failed.append(t)
-    return True
-
-
-class deferred:
-    """``with fused.deferred() as d: ...; bad = d.commit()`` -- renders inside the block are NOT validated
-    when ``forward`` returns: the host never waits for the 8-byte read-back of the patch count inside a
-    step and can run a whole step ahead of the GPU.  ``commit()`` validates everything rendered so far
-    (it waits for the binning stage of the last render, not for its draw or backward kernels) and returns the
-    ``FusedState`` objects whose patch list outgrew the enqueue-ahead capacity or whose depth keys outgrew the
-    sort's bit hint: their images and gradients are INCOMPLETE and must be recomputed before anything
-    consumes them (the learnt capacity / hint are already raised, so recomputing succeeds).  Leaving the
-    block with such a failure uncollected raises."""
-
-    def __enter__(self):
-        self._prev = getattr(_tls, "deferred", False)
-        _tls.deferred = True
-        return self
-
-    def commit(self):
-        return commit()
-
-    def __exit__(self, et, ev, tb):
-        _tls.deferred = self._prev
-        if et is None and not self._prev:
-            bad = commit()
-            if bad:
-                raise RuntimeError("%d enqueue-ahead render(s) were incomplete (patch capacity or depth-key hint "
-                                   "exceeded) and nobody collected them with commit(): their results must not be used"
-                                   % len(bad))
-        return False
-
-
-def commit(device=None):
-    """Validate every render of ``device`` (default: the current one) that is still awaiting its read-back;
-    -> list of the FusedState objects that turned out incomplete since the last commit."""
-    index = torch.cuda.current_device() if device is None else torch.device(device).index
-    ctx = _contexts.get(index)
-    if ctx is None:
-        return []
-    while True:
-        with ctx.lock:
-            t = ctx.pending[0] if ctx.pending else None
-        if t is None:
-            break
-        _settle(t, True)
-    with ctx.lock:
-        bad, ctx.failed = ctx.failed, []
-    for t in bad:
-        t.collected = True
-    return [t.state for t in bad]
-
-
-def expect_long_walks(device=None, renders=4):
-    """A caller that KNOWS the next renders will walk their tile lists far (this package's ``DensityControl.reset_alpha``:
-    every opacity drops to 0.01, nothing saturates any more, gsmodel.py:320-324) says so: the next ``renders`` renders on
-    ``device`` take the segment path and speculate whole lists at once, instead of learning it from the hint words two
-    renders late (the draw stage publishes a render's longest walk at the start of the NEXT draw stage on its stream;
-    13 + 10 ms instead of 3.3 per training step on scene.skewed_scene's ring views).  An unmodified reference caller never
-    calls this and pays those two steps."""
-    index = torch.cuda.current_device() if device is None else torch.device(device).index
-    if index is None:
-        return
-    ctx = _contexts.get(index)
-    if ctx is None:
-        ctx = _ctx(torch.device("cuda", index))
-    with ctx.lock:
-        ctx.long_walks_expected = max(ctx.long_walks_expected, int(renders))
-
-
-def _seg_decision(ctx, lib, key, pol_):
-    """-> (use the segment path for this render, device-visible address of the hint slot or None).  The draw stage
-    leaves two numbers in a page-locked slot kept per problem size -- the longest list, and the longest WALK (largest
-    contributor index of a tile) of a recent render -- and a later render looks at them WITHOUT waiting (they may be a
-    render or two old; they only select between two exact paths): a scene whose tiles are all walked for less than the
-    split threshold takes the unsplit kernels (three launches less), at first sight and from then on long walks take
-    the segment path."""
-    _tls.seg_speculate = SEG_SPECULATE == "1"
-    if SEGMENTS == "0" or pol_.footprint != 0 or not (pol_.alpha_skip > 0) or not (pol_.tau_stop > 0):
-        return False, None
-    with ctx.lock:
-        slot = ctx.seg_hint.pop(key, None)
-        if slot is None:
-            # at most HINT_SLOTS problem sizes keep a slot; the least recently used one hands its slot on (a kernel of
-            # that size still in flight may write into it once more: a stale hint, never a wrong result)
-            if len(ctx.seg_hint) >= HINT_SLOTS:
-                slot = ctx.seg_hint.pop(next(iter(ctx.seg_hint)))
-            elif len(ctx.free) > MAILBOX_SLOTS // 2:     # (never starve the renders of their read-back slots)
-                slot = ctx.free.pop()
-            else:
-                return SEGMENTS == "1", None
-            _lib.check(lib.egs_mailbox_clear(ctx.mb, slot))
-        ctx.seg_hint[key] = slot                         # (re-inserted: most recently used)
-    out = (C.c_uint32 * 4)()
-    _lib.check(lib.egs_mailbox_peek(ctx.mb, slot, out))
-    cfg = (C.c_int * 2)()
-    _lib.check(lib.egs_seg_config(0, 0, cfg))
-    longest, walk = int(out[0]), int(out[1])
-    known = walk != 0xFFFFFFFF and longest != 0xFFFFFFFF
-    # no walk on record yet: the longest LIST bounds it (a scene whose lists all stay below the split threshold never
-    # pays for the segment workspace, ~6 KB per 256 entries of a split tile); nothing known at all: the segment path
-    unknown = walk == 0xFFFFFFFF and (longest == 0xFFFFFFFF or longest > cfg[1])
-    use = SEGMENTS == "1" or unknown or (walk != 0xFFFFFFFF and walk > cfg[1])
-    with ctx.lock:
-        announced = ctx.long_walks_expected > 0
-        if announced:
-            ctx.long_walks_expected -= 1
-    if announced and SEGMENTS != "0":
-        _tls.seg_speculate = SEG_SPECULATE != "0"
-        return True, C.c_void_p(lib.egs_mailbox_slot(ctx.mb, slot))
-    _tls.seg_speculate = SEG_SPECULATE == "1" or (SEG_SPECULATE == "auto" and known and 2 * walk >= longest)
-    return use, C.c_void_p(lib.egs_mailbox_slot(ctx.mb, slot))
-
-
-def _walk_word(ctx, key, dev, st, have_hint):
-    """The persistent device word of (problem size, stream) for the draw stage's longest-walk report, or None."""
-    if not have_hint:
-        return None
-    k = (key, int(st.value or 0))
-    with ctx.lock:
-        w = ctx.walk_word.get(k)
-        if w is None:
-            while len(ctx.walk_word) >= 4 * HINT_SLOTS:          # (bounded: streams and sizes that are gone)
-                ctx.walk_word.pop(next(iter(ctx.walk_word)))
-            w = ctx.walk_word[k] = torch.full((16,), -1, dtype=torch.int32, device=dev)
-    return w
-
-
-def seg_hint(device=None, key=None):
-    """(longest list, longest walk) the draw stage last reported for problem size ``key`` = (N, W, H) on ``device``
-    (None: nothing yet / no slot) -- what ``_seg_decision`` steers by; for bench lines and tests."""
-    index = torch.cuda.current_device() if device is None else torch.device(device).index
-    ctx = _contexts.get(index)
-    if ctx is None:
-        return None
-    with ctx.lock:
-        slot = ctx.seg_hint.get(key)
-    if slot is None:
-        return None
-    out = (C.c_uint32 * 4)()
-    _lib.check(ctx.lib.egs_mailbox_peek(ctx.mb, slot, out))
-    f = lambda v: None if v == 0xFFFFFFFF else int(v)
-    return f(out[0]), f(out[1])
 
 
 def _split_sh(low_shs, high_shs, n):
@@ -443,12 +194,12 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
     mask = torch.empty((n,), dtype=torch.bool, device=dev)        # depths > 0.2, written by the kernel
     ws_bin_bytes = lib.egs_splat_bin_ws_bytes(n)
     ws_bin = torch.empty(ws_bin_bytes, dtype=torch.uint8, device=dev)
-    host_slot = [None]       # mailbox slot the binning kernels also write {P, max key} into (enqueue-ahead path)
-    enqueue_bin = lambda hint, total: _lib.check(lib.egs_fused_forward(
+    # (host_slot: the mailbox slot the binning kernels also write {P, max key} into on the enqueue-ahead path)
+    enqueue_bin = lambda hint, total, host_slot: _lib.check(lib.egs_fused_forward(
         n, K, _ptr(pws), _ptr(rots), _ptr(scales), _ptr(shs), _ptr(high_shs), _ptr(alphas), _ptr(Rcw), _ptr(tcw),
         _ptr(twc), float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), W, H, pol, _ptr(S.us), _ptr(S.depths),
         _ptr(S.cinv2ds), _ptr(S.colors), _ptr(S.areas), _ptr(S.rec), _ptr(mask), _ptr(S.dcw), S.flags, hint,
-        _ptr(ws_bin), ws_bin_bytes, _ptr(total), host_slot[0], st))
+        _ptr(ws_bin), ws_bin_bytes, _ptr(total), host_slot, st))
     image = torch.empty((3, H, W), dtype=f32, device=dev)       # fully written by the draw stage
     depth_map = alpha_map = None
     ex = None           # EgsExtras of the draw stage (render extras), None: a plain render
@@ -460,7 +211,6 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
             alpha_map = torch.empty((1, H, W), dtype=f32, device=dev)
         ex = _egs_extras(S.depths, extras.background_rgb(), depth_map, alpha_map)
     done = (lambda: (image, mask, S)) if extras is None else (lambda: (image, mask, S, depth_map, alpha_map))
-    draw_rec = lambda *args: lib.egs_splat_draw_rec_seg(*args, None if ex is None else C.byref(ex))
     S.contrib = torch.empty((H, W), dtype=i32, device=dev)
     S.final_tau = torch.empty((H, W), dtype=f32, device=dev)
     S.ranges = torch.empty((_tiles(W, H), 2), dtype=i32, device=dev)
@@ -471,22 +221,20 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
     # SH coefficients (36 B written + read instead of a 4K-byte row re-read; EGS_SAVE_DCOLOR=0: A/B knob)
     S.dcw = torch.empty((n, 9), dtype=f32, device=dev) if (need_grad and n > 0 and SAVE_DCOLOR) else None
 
-    def draw_exact(patches, redo=False):
-        # ``redo``: the draw stage of this render ran once already on truncated lists (more patches than the enqueue-ahead
-        # buffers held).  Its range kernel has published the PREVIOUS render's hint words; what that truncated draw
-        # raised in the walk word is nobody's longest walk: the second range kernel clears it without publishing
-        # (hint address withheld) -- otherwise a later render steers by (1189, 696) where the render walked (2063, 696)
-        S.gsid = torch.empty(patches, dtype=i32, device=dev)
-        ws_draw = torch.empty(lib.egs_splat_draw_ws_bytes(n, patches, W, H), dtype=torch.uint8, device=dev)
+    def draw(rows, total, redo):
+        # buffers for ``rows`` patches, the count from the device words ``total`` if given; ``redo``: see _ahead.render
+        S.gsid = torch.empty(rows, dtype=i32, device=dev)   # (entries past P are unused: the kernels walk `ranges`)
+        ws_draw = torch.empty(lib.egs_splat_draw_ws_bytes(n, rows, W, H), dtype=torch.uint8, device=dev)
         if use_seg:
-            S.seg = torch.empty(lib.egs_seg_ws_bytes(max(patches, 1), W, H), dtype=torch.uint8, device=dev)
+            S.seg = torch.empty(lib.egs_seg_ws_bytes(max(rows, 1), W, H), dtype=torch.uint8, device=dev)
         # (seg_ws NULL: the unsplit kernels; the hint slot still learns how far this camera's tiles are walked)
-        _lib.check(draw_rec(n, patches, None, W, H, _ptr(S.rec), pol, _ptr(ws_bin), _ptr(ws_draw),
-                                              ws_draw.numel(), _ptr(image), _ptr(S.contrib), _ptr(S.final_tau),
-                                              _ptr(S.ranges), _ptr(S.gsid), _ptr(S.order), _ptr(S.gpack), prev_work,
-                                              order_ready, draw_flags, _ptr(S.seg),
-                                              S.seg.numel() if S.seg is not None else 0,
-                                              None if (redo and walk_word is not None) else seg_hint, _ptr(walk_word), None, st))
+        _lib.check(lib.egs_splat_draw_rec_seg(
+            n, rows, _ptr(total), W, H, _ptr(S.rec), pol, _ptr(ws_bin), _ptr(ws_draw), ws_draw.numel(), _ptr(image),
+            _ptr(S.contrib), _ptr(S.final_tau), _ptr(S.ranges), _ptr(S.gsid), _ptr(S.order), _ptr(S.gpack), prev_work,
+            order_ready, draw_flags, _ptr(S.seg), S.seg.numel() if S.seg is not None else 0,
+            None if (redo and walk_word is not None) else seg_hint, _ptr(walk_word), None, st,
+            None if ex is None else C.byref(ex)))
+        remember_order()
 
     ctx = _ctx(dev)
     key = (n, W, H)
@@ -500,7 +248,8 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
     # no order kernel at all on most renders (10 us forward, 8 us backward at 1080p).
     prev_work, order_ready = None, 0
     cache_entry = None        # registered only AFTER the draw stage that writes the order buffer was enqueued
-    use_seg, seg_hint = _seg_decision(ctx, lib, key, pol_) if n > 0 else (False, None)
+    use_seg, seg_hint, speculate = _seg_decision(ctx, lib, key, pol_, SEGMENTS, SEG_SPECULATE) if n > 0 \
+        else (False, None, False)
     if extras is not None:    # the extras exist on the unsplit kernels only (the hint slot still learns from the render)
         use_seg = False
     walk_word = _walk_word(ctx, key, dev, st, seg_hint is not None)
@@ -530,9 +279,9 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
 
     def remember_order():
         """The render that just enqueued its draw stage wrote [order | work] (every path of the library does,
-        patches == 0 included): only now may the NEXT render of this camera rely on it.  A render that raised
-        before this point leaves the cache as it was.  The entry goes when the camera object dies (weakref
-        callback): callers that build a Camera per frame do not pile up order buffers."""
+        patches == 0 included): only now may the NEXT render of this camera rely on it (a redone draw registers the
+        same entry again).  A render that raised before this point leaves the cache as it was.  The entry goes when
+        the camera object dies (weakref callback): callers that build a Camera per frame do not pile up order buffers."""
         if cache_entry is None:
             return
         ck, renders = cache_entry
@@ -550,96 +299,16 @@ def forward(pws, shs, alphas, scales, rots, cam, high_shs=None, need_grad=False,
         with ctx.lock:
             tw[ck] = (ref, S.order, renders, (n, W, H))
     S.order_by_work = prev_work is not None or order_ready == 1
-    draw_flags = (1 if culled else 0) | (SEG_HISTORY if (use_seg and walk_known) else 0) | \
-        (SEG_SPECULATE_FLAG if (use_seg and getattr(_tls, "seg_speculate", False)) else 0)
+    draw_flags = (DRAW_CULLED_LISTS if culled else 0) | (SEG_HISTORY if (use_seg and walk_known) else 0) | \
+        (SEG_SPECULATE_FLAG if (use_seg and speculate) else 0)
     # (SPECULATE with a walk on record: the plan distrusts a record that is far shorter than the tile's list while the
     # scene's recent renders walk most of theirs -- the renders right after reset_alpha, gsmodel.py:320-324)
-    cap = ctx.capacity.get(key, 0) if ENQUEUE_AHEAD else 0
-
-    def render_exact(redo=False):
-        """Synchronous form: read P back (8 bytes, as the reference does at gausplat.cu:67), then draw."""
-        patches = _bin_stage(enqueue_bin, dev, key)
-        draw_exact(patches, redo)
-        remember_order()
+    cap = ctx.capacity.get(key, 0) if (ENQUEUE_AHEAD and n > 0) else 0
+    # inside a ``deferred()`` block the render stays pending (S.ticket) and commit() reports S if it was incomplete
+    patches = _ahead.render(ctx, dev, key, st, cap, _ahead.wait_slot, enqueue_bin, draw, S,
+                            getattr(_tls, "deferred", False), MAILBOX_COPY)
+    if patches is not None:
         S._patches = patches
-        if n > 0:
-            with ctx.lock:
-                _learn_capacity(ctx, key, patches)
-
-    if cap == 0 or n == 0:
-        render_exact()                               # first render of this size
-        return done()
-    # The draw stage is enqueued AHEAD of the read-back: buffers sized by the largest patch count seen so
-    # far, the kernels take the real count from device memory, and {P, max depth key} travel to a page-locked
-    # mailbox slot by a copy enqueued between the two stages (egs_mailbox_post).  The GPU never waits for the
-    # host (the reference, like the seven-op path, idles around cudaMemcpy(&P), gausplat.cu:67).  An overflow
-    # of the capacity or of the depth-key hint is detected after the fact -- here (one C-side wait on the
-    # slot's event) or, inside a ``deferred()`` block, at ``commit()`` -- and the render is redone.
-    t = _Ticket()
-    t.ctx, t.key, t.cap, t.state, t.status, t.collected = ctx, key, cap, S, _Ticket.PENDING, False
-    t.hint = _gsc._get_key_bits(dev.index, key)
-    while True:
-        with ctx.lock:
-            if ctx.free:
-                t.slot = ctx.free.pop()
-                break
-            oldest = ctx.pending[0] if ctx.pending else None
-        if oldest is None:
-            raise RuntimeError("fused.forward: no mailbox slot free and no render in flight (slots leaked)")
-        _settle(oldest, True)                         # every slot in flight: wait for the oldest render
-    try:
-        total = torch.empty(2, dtype=i32, device=dev)
-        if MAILBOX_COPY:          # {P, max key} by an 8-byte device-to-host copy behind the binning stage
-            enqueue_bin(t.hint, total)
-            _lib.check(lib.egs_mailbox_post(ctx.mb, t.slot, _ptr(total), st))
-        else:                     # the binning kernels store them into the page-locked slot themselves
-            _lib.check(lib.egs_mailbox_arm(ctx.mb, t.slot, st))
-            host_slot[0] = C.c_void_p(lib.egs_mailbox_slot(ctx.mb, t.slot))
-            enqueue_bin(t.hint, total)
-            host_slot[0] = None   # (a later synchronous re-render must not write into a slot that was handed back)
-        gsid_full = torch.empty(cap, dtype=i32, device=dev)
-        ws_draw = torch.empty(lib.egs_splat_draw_ws_bytes(n, cap, W, H), dtype=torch.uint8, device=dev)
-        if use_seg:
-            S.seg = torch.empty(lib.egs_seg_ws_bytes(cap, W, H), dtype=torch.uint8, device=dev)
-        _lib.check(draw_rec(n, cap, _ptr(total), W, H, _ptr(S.rec), pol, _ptr(ws_bin),
-                                              _ptr(ws_draw), ws_draw.numel(), _ptr(image), _ptr(S.contrib),
-                                              _ptr(S.final_tau), _ptr(S.ranges), _ptr(gsid_full), _ptr(S.order),
-                                              _ptr(S.gpack), prev_work, order_ready, draw_flags, _ptr(S.seg),
-                                              S.seg.numel() if S.seg is not None else 0, seg_hint, _ptr(walk_word), None, st))
-    except BaseException:
-        # Whatever was enqueued before the failure (the arm, the binning chain) still stores {P, max key} into the
-        # slot: it goes back on the free list only once those kernels have run -- otherwise a render on another
-        # ViewStreams lane could pick it up and settle on THEIR values.  Rare path: a stream wait is fine.
-        try:
-            torch.cuda.current_stream(dev).synchronize()
-        except Exception:
-            pass
-        with ctx.lock:
-            t.status = _Ticket.FAILED
-            ctx.free.append(t.slot)
-        raise
-    remember_order()
-    S.gsid = gsid_full                                # entries past P are unused (the kernels walk `ranges`)
-    S._patches = None
-    S.ticket = t
-    with ctx.lock:
-        ctx.pending.append(t)
-    if getattr(_tls, "deferred", False):
-        with ctx.lock:                                # look at whatever has landed meanwhile (no waiting)
-            waiting = list(ctx.pending)
-        for old in waiting:
-            if old is not t and not _settle(old, False):
-                break
-        return done()
-    t.collected = True                                # validated right here: never reported by commit()
-    _settle(t, True)
-    if t.status == _Ticket.FAILED:
-        if t.patches >= 2**31:
-            raise RuntimeError("splat: %d tile patches overflow int32 indexing" % t.patches)
-        if t.hint < 32 and t.need > t.hint:           # stale depth-key hint: everything again
-            render_exact(redo=True)
-        else:                                         # more patches than ever before: redo the draw stage
-            draw_exact(t.patches, redo=True)
     return done()
 
 

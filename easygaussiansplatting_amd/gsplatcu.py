@@ -26,86 +26,17 @@ supersets:
 from __future__ import annotations
 
 import ctypes as C
-import threading
 
 import torch
 
-from . import _lib
-from ._lib import EgsPolicy
+from . import _ahead, _lib
+from . import fused as _fused
+# (re-exported: the depth-key bit hints, for tests and lab tools that reach them through this module)
+from ._ahead import KEY_BITS_DECAY, _get_key_bits, _key_bits, _learn_key_bits, _set_key_bits  # noqa: F401
+from ._host import _alphas, _chk, _lib_on, _out, _pol, _ptr, _stream, _tiles, get_policy, set_policy
 
 __all__ = ["project", "computeCov3D", "computeCov2D", "sh2Color", "inverseCov2D", "splat", "splatB",
            "set_policy", "get_policy", "chain_rule", "clear_memo", "set_memo", "splat_with_records", "SplatRecords"]
-
-_policy_name = "gsplatcu"
-_policy = None
-
-
-def _pol() -> EgsPolicy:
-    global _policy
-    if _policy is None:
-        set_policy(_policy_name)
-    return _policy
-
-
-def set_policy(name: str) -> None:
-    """Select which of the reference's pipeline definitions the ops follow:
-    ``"gsplatcu"`` (gsplatcu/kernel.cu; default) or ``"forward_cpu"``
-    (gsplat/gausplat.py as driven by forward_cpu.py).  ``"gsplatcu_nan_skip"``: the default with one opt-in
-    deviation -- a Gaussian whose conic holds a NaN is skipped instead of blended at min(0.99, alpha) (the CUDA
-    extension's ``max(0.0f, NaN) == 0``, kernel.cu:243-246): no NaN colour can reach the image."""
-    global _policy, _policy_name
-    lib = _lib.load()
-    p = EgsPolicy()
-    if name in ("gsplatcu", "gsplatcu_nan_skip"):
-        lib.egs_policy_gsplatcu(C.byref(p))
-        p.nan_maha = 1 if name == "gsplatcu_nan_skip" else 0
-    elif name == "forward_cpu":
-        lib.egs_policy_forward_cpu(C.byref(p))
-    else:
-        raise ValueError("unknown raster policy %r (expected 'gsplatcu', 'gsplatcu_nan_skip' or 'forward_cpu')" % (name,))
-    _policy, _policy_name = p, name
-
-
-def get_policy() -> str:
-    return _policy_name
-
-
-# ------------------------------------------------------------------ helpers
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _chk(t, name, dtype, shape):
-    """dtype/device/shape validation; returns a contiguous tensor (a copy only
-    if the caller's tensor was not contiguous, like the reference's .contiguous())."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise ValueError("%s must live on the GPU (got device %s)" % (name, t.device))
-    if t.dtype != dtype:
-        raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if len(shape) != t.dim() or any(s is not None and s != d for s, d in zip(shape, t.shape)):
-        raise ValueError("%s must have shape %s, got %s" % (name, list(shape), list(t.shape)))
-    return t.contiguous()
-
-
-def _out(shape, like, dtype=torch.float32):
-    """Output of an op: the kernels write EVERY row (culled Gaussians as zeros, what the reference's zero-filled
-    ``torch::full(..., 0)`` outputs read as, gausplat.cu:170-178), so no fill kernel runs -- torch.zeros here cost
-    528 B per Gaussian and training step of pure memset."""
-    return torch.empty(shape, dtype=dtype, device=like.device)
-
-
-def _lib_on(t):
-    lib = _lib.load()
-    if t.device.index is not None and t.device.index != torch.cuda.current_device():
-        raise ValueError("tensors live on %s but the current device is cuda:%d"
-                         % (t.device, torch.cuda.current_device()))
-    return lib
 
 
 # ------------------------------------------------------------------ the seven ops
@@ -197,86 +128,6 @@ def inverseCov2D(cov2ds, depths, calc_J):
     return [cinv, areas, J] if calc_J else [cinv, areas]
 
 
-_key_bits = {}   # (device index, problem key) -> significant depth-key bits learnt from the previous call
-
-
-def _get_key_bits(dev_index, key=None) -> int:
-    return _key_bits.get((dev_index, key), 32)
-
-
-def _set_key_bits(dev_index, key, bits) -> None:
-    _key_bits[(dev_index, key)] = int(bits)
-    _key_low.pop((dev_index, key), None)
-
-
-_key_low = {}    # (device index, problem key) -> [renders in a row that needed fewer bits, the most they needed]
-KEY_BITS_DECAY = 32   # renders in a row with a smaller need before the hint is lowered
-
-
-def _learn_key_bits(dev_index, key, need, missed=False) -> None:
-    """Update the depth-key bit hint of a problem size from one render's largest key (``need`` bits).
-    The hint is shared by all cameras that render this problem size, so it follows a slowly decaying MAXIMUM:
-    raised at once, lowered only after KEY_BITS_DECAY renders in a row needed less (to the most they needed) --
-    cameras whose depth ranges differ by a bit or two then never miss, where "need + 1 after every success"
-    made them alternate between a miss (a redone step under deferred validation) and a reset.  A miss sets
-    the hint to 32 for the redo; the first success after that adopts need + 1."""
-    k = (dev_index, key)
-    target = min(32, int(need) + 1)
-    while len(_key_bits) > 1024:          # (bounded like the capacity table: fused.SIZE_TABLE_MAX)
-        old = next(iter(_key_bits))
-        _key_bits.pop(old, None)
-        _key_low.pop(old, None)
-    if missed:
-        _key_bits[k] = 32
-        _key_low.pop(k, None)
-        return
-    hint = _key_bits.get(k, 32)
-    if hint >= 32 or target >= hint:
-        _key_bits[k] = target
-        _key_low.pop(k, None)
-        return
-    low = _key_low.setdefault(k, [0, 0])
-    low[0] += 1
-    low[1] = max(low[1], target)
-    if low[0] >= KEY_BITS_DECAY:
-        _key_bits[k] = low[1]
-        _key_low.pop(k, None)
-
-
-def _bin_stage(enqueue, device, key=None, while_waiting=None):
-    """Run the binning stage with the depth-key bit-count hint protocol of egs_splat_bin:
-    ``enqueue(hint, total)`` enqueues the stage; returns the patch count P.  The single
-    8-byte read-back (reference: gausplat.cu:67) also brings the largest depth key, which
-    sizes the next call's sort (depth keys rarely need more than 16 of their 32 bits; the hint is kept
-    per device and problem ``key``); a too-small hint triggers one full-width re-run.
-    ``while_waiting()`` runs between the enqueue and the blocking read: host work that does not need
-    P (output allocations) belongs there, so that the GPU idles as briefly as possible afterwards."""
-    total = torch.empty(2, dtype=torch.int32, device=device)
-    hint = _get_key_bits(device.index, key)
-    enqueue(hint, total)
-    if while_waiting is not None:
-        while_waiting()
-    p, mk = (int(v) & 0xFFFFFFFF for v in total.tolist())
-    need = mk.bit_length()
-    if hint < 32 and need > hint:
-        enqueue(32, total)
-        p, mk = (int(v) & 0xFFFFFFFF for v in total.tolist())
-    _learn_key_bits(device.index, key, need)
-    if p >= 2**31:
-        raise RuntimeError("splat: %d tile patches overflow int32 indexing" % p)
-    return p
-
-
-def _tiles(width, height):
-    return ((width + 15) // 16) * ((height + 15) // 16)
-
-
-def _alphas(alphas, n):
-    if not isinstance(alphas, torch.Tensor) or alphas.numel() != n:
-        raise ValueError("alphas must be a tensor of shape [N] or [N,1] with N=%d" % n)
-    return _chk(alphas.reshape(n), "alphas", torch.float32, (n,))
-
-
 # ---- what `splat` keeps for the `splatB` that follows it ------------------------------------------------------
 # GSFunction.backward (gsmodel.py:67-69) calls splatB with the very tensors its forward gave to splat: the list with
 # block masks the forward draw walked, the draw's [dispatch order | measured work] buffer and an [N][12] gradient-record
@@ -323,7 +174,6 @@ MEMO_MAX = 8
 _pair_states_enabled = "content"     # "content" (default) | True (identity + version, unvalidated) | False (nothing kept)
 _pair_states = {}       # (device, stream) -> dict(outs, sig, in_sig, seg, lists, width, height, policy)
 _last_splatB = {"segments": False, "rebuilt": False, "kept_states": False}
-_pair_tls = threading.local()   # hands the segment workspace of a _splat call to the public splat() around it
 MASKED_LISTS = True     # A/B knob: exact block masks in the seven-op surface's list values (egs_splat_bin_pack)
 
 
@@ -334,7 +184,7 @@ class SplatRecords:
 
     def matches(self, dev, st, tensors, width, height):
         if (self.dev_index != dev.index or self.stream != int(st.value or 0) or self.width != width
-                or self.height != height or self.policy != _policy_name):
+                or self.height != height or self.policy != get_policy()):
             return False
         sig = _memo_sig(tensors)
         return sig is not None and sig == self.sig and _memo_sig(self.tensors) == self.sig
@@ -423,7 +273,7 @@ def _make_records(dev, st, tensors, width, height, rec, order, gpack, lists=None
         return None
     h = SplatRecords()
     h.stamp, h.n, h.npatch, h.visible, h.seg = stamp, n, npatch, None, None
-    h.tensors, h.sig, h.width, h.height, h.policy = tensors, sig, width, height, _policy_name
+    h.tensors, h.sig, h.width, h.height, h.policy = tensors, sig, width, height, get_policy()
     h.rec, h.order, h.gpack, h.dev_index, h.stream = rec, order, gpack, dev.index, int(st.value or 0)
     # the list WITH block masks the forward draw walked, valid for the (gsid_per_patch, patch_range_per_tile) pair
     # this splat returned -- and only for it
@@ -454,7 +304,12 @@ def _take_records(h, dev, st, tensors, width, height):
 def splat_with_records(height, width, us, cinv2ds, alphas, depths, colors, areas):
     """``splat`` + a ``SplatRecords`` handle (or None) for ``splatB(..., records=handle)``.  For callers that own
     the four input tensors until that ``splatB`` (see the note above ``SplatRecords``)."""
-    return _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep="handle")
+    return _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep="handle")[:2]
+
+
+def _stream_key(dev, st):
+    """(device index, stream): what the kept state of the ``splat`` -> ``splatB`` pair is filed under"""
+    return (dev.index, int(st.value or 0))
 
 
 def splat(height, width, us, cinv2ds, alphas, depths, colors, areas):
@@ -462,12 +317,11 @@ def splat(height, width, us, cinv2ds, alphas, depths, colors, areas):
            patch_range_per_tile[T,2] int32, gsid_per_patch[P] int32].
     ``depths`` and ``areas`` are updated IN PLACE for Gaussians whose tile rect is
     empty (kernel.cu:114-119).  Reference: ext.cpp:10-18, gausplat.cu:24-112."""
-    out, h = _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep="public" if _memo_enabled else False)
+    out, h, kept = _splat(height, width, us, cinv2ds, alphas, depths, colors, areas,
+                          keep="public" if _memo_enabled else False)
+    key = _stream_key(us.device, _stream())
     if _pair_states_enabled:
-        key = (us.device.index, int(_stream().value or 0))
         _pair_states.pop(key, None)
-        kept = getattr(_pair_tls, "seg_of_last_call", None)
-        _pair_tls.seg_of_last_call = None
         if kept is not None:
             # (the inputs as splatB will see them: it normalises ``alphas`` [N,1] -> [N] before it forms its signature --
             # through GSFunction, which hands both calls the [N,1] tensor, nothing ever matched before this line said so)
@@ -490,12 +344,11 @@ def splat(height, width, us, cinv2ds, alphas, depths, colors, areas):
             elif sig is not None and in_sig is not None:
                 ent = dict(outs=tuple(out[1:5]), sig=sig, in_sig=in_sig)
             if ent is not None:
-                ent.update(seg=kept[0], lists=kept[1], width=int(width), height=int(height), policy=_policy_name)
+                ent.update(seg=kept[0], lists=kept[1], width=int(width), height=int(height), policy=get_policy())
                 _pair_states[key] = ent
                 while len(_pair_states) > MEMO_MAX:
                     _pair_states.pop(next(iter(_pair_states)))
     if _memo_enabled:
-        key = (us.device.index, int(_stream().value or 0))
         _splat_memo.pop(key, None)          # (an older entry must not outlive its splat; re-inserted = most recent)
         if h is not None:
             _splat_memo[key] = h
@@ -505,7 +358,9 @@ def splat(height, width, us, cinv2ds, alphas, depths, colors, areas):
 
 
 def _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep):
-    """-> ([image, contrib, final_tau, patch_range_per_tile, gsid_per_patch], SplatRecords or None)."""
+    """-> ([image, contrib, final_tau, patch_range_per_tile, gsid_per_patch], SplatRecords or None,
+    (segment workspace, walked list) of a draw that split its long lists -- what the public ``splat`` may keep for
+    the ``splatB`` of the tensors it returns -- or None)."""
     height, width = int(height), int(width)
     if height <= 0 or width <= 0:
         raise ValueError("height and width must be positive")
@@ -538,7 +393,7 @@ def _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep):
     # lists are the reference's (gsid_per_patch bit-exact), their values carry exact 8x8-block masks the draw kernels
     # take instead of testing a box per entry.  The masked list stays internal; the caller gets the stripped copy.
     masks = MASKED_LISTS and n > 0 and _pol().footprint == 0 and _pol().alpha_skip > 0 and n < (1 << 28)
-    flags = 2 if masks else 0            # EGS_DRAW_MASKED_LISTS
+    flags = _fused.DRAW_MASKED_LISTS if masks else 0
     if n > 0:
         if not masks:
             _lib.check(lib.egs_pack_records(n, width, height, _ptr(us), _ptr(cinv2ds), _ptr(alphas), _ptr(colors),
@@ -549,38 +404,24 @@ def _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep):
             gpack = torch.empty((n, 12), dtype=torch.float32, device=dev)
     # Long tile lists split over several waves (include/egs_hip.h egs_splat_draw_rec_seg): taken when the longest walk a
     # recent call of this problem size reported exceeds the split threshold (page-locked hint words, read without
-    # waiting; fused._seg_decision).  The op has no camera identity, so there is no walk on record per view: every
+    # waiting; _ahead._seg_decision).  The op has no camera identity, so there is no walk on record per view: every
     # segment of a list is speculated when the scene's renders walk most of their lists, else segment 0 + one wave
     # continuing -- the BACKWARD pass is split either way (with the handle: from these states; public splatB: rebuilt).
-    from . import fused as _fused            # (the per-device mailbox / capacity / hint state lives there)
-    ctx = _fused._ctx(dev)
-    use_seg, seg_hint = _fused._seg_decision(ctx, lib, key, _pol()) if n > 0 else (False, None)
-    walk_word = _fused._walk_word(ctx, key, dev, st, seg_hint is not None)
-    seg_flags = 8 if (use_seg and getattr(_fused._tls, "seg_speculate", False)) else 0     # EGS_DRAW_SEG_SPECULATE
-    seg_ws = [None]
-    lists = [None]     # the list the draw kernels walked (with masks), kept for the backward draw
+    ctx = _ahead._ctx(dev)
+    use_seg, seg_hint, speculate = _ahead._seg_decision(ctx, lib, key, _pol(), _fused.SEGMENTS, _fused.SEG_SPECULATE) \
+        if n > 0 else (False, None, False)
+    walk_word = _ahead._walk_word(ctx, key, dev, st, seg_hint is not None)
+    flags |= _fused.SEG_SPECULATE_FLAG if (use_seg and speculate) else 0
+    # what the (last) draw stage of this call allocated: the caller's list, the list the draw kernels walked (with
+    # masks; kept for the backward draw), the segment workspace
+    drawn = dict(gsid=None, lists=None, seg=None)
     # content stamps of us / cinv2ds / alphas (public pair: splatB validates what it is given against them)
     stamp = torch.empty(lib.egs_pair_stamp_words(n), dtype=torch.int32, device=dev) if (masks and keep == "public") else None
     # depths > 0.2 after this op's in-place cull (the mask of gsmodel.py:50), written by the packing kernel on the side
     # for a caller that asked for the handle (this package's GSFunction): no separate compare kernel
     visible = torch.empty(n, dtype=torch.bool, device=dev) if (masks and keep == "handle") else None
 
-    def records(gsid):    # only once the draw stage is enqueued: the order buffer is written, the gradient records cleared
-        # (the public splat may keep this draw's segment states for the splatB of the tensors it returns: see above)
-        _pair_tls.seg_of_last_call = (seg_ws[0], lists[0]) if (seg_ws[0] is not None and keep != "handle") else None
-        if keep == "handle":
-            h = _make_records(dev, st, (us, cinv2ds, alphas, colors), width, height, rec, order, gpack,
-                              lists[0], (gsid, ranges) if lists[0] is not None else None)
-            if h is not None:
-                h.visible = visible
-                h.seg = seg_ws[0]       # the segment states of this draw (long lists split over waves), if any
-            return h
-        if keep == "public" and lists[0] is not None:   # no tensor is referenced, no record kept: values are validated
-            return _make_records(dev, st, None, width, height, None, order, gpack, lists[0], None, stamp, n,
-                                 int(gsid.shape[0]))
-        return None
-
-    def enqueue_bin(hint, total, host_slot=None):
+    def enqueue_bin(hint, total, host_slot):
         if masks:
             _lib.check(lib.egs_splat_bin_pack(n, width, height, _ptr(us), _ptr(cinv2ds), _ptr(alphas), _ptr(colors),
                                               _ptr(areas), _ptr(depths), pol, hint, _ptr(ws_bin), ws_bin_bytes,
@@ -592,93 +433,41 @@ def _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep):
             _lib.check(lib.egs_splat_bin(n, width, height, _ptr(us), _ptr(areas), _ptr(depths), pol, hint,
                                          _ptr(ws_bin), ws_bin_bytes, _ptr(total), st))
 
-    def draw_exact(patches, redo=False):
-        # (``redo``: see fused.forward -- the second range kernel of a render clears the walk word without publishing it)
-        gsid = torch.empty(patches, dtype=torch.int32, device=dev)
-        walked = torch.empty(patches, dtype=torch.int32, device=dev) if masks else gsid
-        ws_draw_bytes = lib.egs_splat_draw_ws_bytes(n, patches, width, height)
+    def draw(rows, total, redo):
+        # buffers for ``rows`` patches, the count from the device words ``total`` if given; ``redo``: see _ahead.render
+        gsid = torch.empty(rows, dtype=torch.int32, device=dev)
+        walked = torch.empty(rows, dtype=torch.int32, device=dev) if masks else gsid
+        ws_draw_bytes = lib.egs_splat_draw_ws_bytes(n, rows, width, height)
         ws_draw = torch.empty(ws_draw_bytes, dtype=torch.uint8, device=dev)
+        seg = torch.empty(lib.egs_seg_ws_bytes(max(rows, 1), width, height), dtype=torch.uint8, device=dev) if use_seg \
+            else None
         # (with masks the range kernel also writes the plain list the caller gets: no strip launch)
-        seg_ws[0] = torch.empty(lib.egs_seg_ws_bytes(max(patches, 1), width, height), dtype=torch.uint8,
-                                device=dev) if use_seg else None
-        _lib.check(lib.egs_splat_draw_rec_seg(n, patches, None, width, height, _ptr(rec), pol, _ptr(ws_bin),
+        _lib.check(lib.egs_splat_draw_rec_seg(n, rows, _ptr(total), width, height, _ptr(rec), pol, _ptr(ws_bin),
                                               _ptr(ws_draw), ws_draw_bytes, _ptr(image), _ptr(contrib), _ptr(final_tau),
-                                              _ptr(ranges), _ptr(walked), _ptr(order), _ptr(gpack), None, 0,
-                                              flags | seg_flags, _ptr(seg_ws[0]),
-                                              seg_ws[0].numel() if use_seg else 0,
+                                              _ptr(ranges), _ptr(walked), _ptr(order), _ptr(gpack), None, 0, flags,
+                                              _ptr(seg), seg.numel() if use_seg else 0,
                                               None if (redo and walk_word is not None) else seg_hint, _ptr(walk_word),
                                               _ptr(gsid) if masks else None, st, None))
-        if masks:
-            lists[0] = walked
-        return gsid
+        drawn.update(gsid=gsid, lists=walked if masks else None, seg=seg)
 
-    def render_exact(redo=False):
-        """The reference's sequence (gausplat.cu:50-105): bin, read P back, draw -- the GPU idles around the read."""
-        patches = _bin_stage(enqueue_bin, dev, key)
-        return patches, draw_exact(patches, redo)
-
-    # From the second call of a problem size on, the draw stage is enqueued BEHIND the binning stage before the
-    # host has seen P: buffers sized by the largest count met so far (+6 %), the count taken from device memory,
-    # {P, max depth key} delivered into a page-locked mailbox slot by the binning kernels.  `gsid_per_patch` must
-    # come back with exactly P rows, so the host still waits for P -- while the GPU draws.
+    # From the second call of a problem size on, the draw stage is enqueued BEHIND the binning stage before the host has
+    # seen P (_ahead.render).  `gsid_per_patch` must come back with exactly P rows, so the host still waits for P --
+    # while the GPU draws; with no mailbox slot free the call takes the reference's sequence (gausplat.cu:50-105).
     cap = ctx.capacity.get(key, 0) if (_fused.ENQUEUE_AHEAD and n > 0) else 0
-    slot = None
-    if cap > 0:
-        with ctx.lock:
-            if ctx.free:
-                slot = ctx.free.pop()
-    if slot is None:
-        patches, gsid = render_exact()
-        if n > 0:
-            with ctx.lock:
-                _fused._learn_capacity(ctx, key, patches)
-        return [image, contrib, final_tau, ranges, gsid], records(gsid)
-    t = _fused._Ticket()
-    t.ctx, t.key, t.cap, t.state, t.status, t.collected, t.slot = ctx, key, cap, None, _fused._Ticket.PENDING, True, slot
-    t.hint = _get_key_bits(dev.index, key)
-    try:
-        total = torch.empty(2, dtype=torch.int32, device=dev)
-        _lib.check(lib.egs_mailbox_arm(ctx.mb, slot, st))
-        enqueue_bin(t.hint, total, C.c_void_p(lib.egs_mailbox_slot(ctx.mb, slot)))
-        gsid_full = torch.empty(cap, dtype=torch.int32, device=dev)
-        walked_full = torch.empty(cap, dtype=torch.int32, device=dev) if masks else gsid_full
-        ws_draw_bytes = lib.egs_splat_draw_ws_bytes(n, cap, width, height)
-        ws_draw = torch.empty(ws_draw_bytes, dtype=torch.uint8, device=dev)
-        seg_ws[0] = torch.empty(lib.egs_seg_ws_bytes(cap, width, height), dtype=torch.uint8, device=dev) if use_seg \
-            else None
-        _lib.check(lib.egs_splat_draw_rec_seg(n, cap, _ptr(total), width, height, _ptr(rec), pol, _ptr(ws_bin),
-                                              _ptr(ws_draw), ws_draw_bytes, _ptr(image), _ptr(contrib),
-                                              _ptr(final_tau), _ptr(ranges), _ptr(walked_full), _ptr(order),
-                                              _ptr(gpack), None, 0, flags | seg_flags, _ptr(seg_ws[0]),
-                                              seg_ws[0].numel() if use_seg else 0, seg_hint, _ptr(walk_word),
-                                              _ptr(gsid_full) if masks else None, st, None))
-    except BaseException:
-        # Kernels enqueued before the failure (the arm, the binning chain) still store {P, max key} into the slot:
-        # it may only go back on the free list once they have run, or a later render that picks it up could settle
-        # on THEIR values.  Rare path: a device-wide wait is fine.
-        try:
-            torch.cuda.current_stream(dev).synchronize()
-        except Exception:
-            pass
-        with ctx.lock:
-            t.status = _fused._Ticket.FAILED
-            ctx.free.append(slot)
-        raise
-    with ctx.lock:
-        ctx.pending.append(t)
-    _fused._settle(t, True)                  # one C-side wait on the slot; learns capacity and depth-key bits
-    if t.status == _fused._Ticket.FAILED:
-        if t.patches >= 2**31:
-            raise RuntimeError("splat: %d tile patches overflow int32 indexing" % t.patches)
-        if t.hint < 32 and t.need > t.hint:  # stale depth-key hint: everything again (the stage is idempotent)
-            gsid = render_exact(redo=True)[1]
-        else:
-            gsid = draw_exact(t.patches, redo=True)     # more patches than ever before
-        return [image, contrib, final_tau, ranges, gsid], records(gsid)
-    gsid = gsid_full[:t.patches]
-    if masks:
-        lists[0] = walked_full
-    return [image, contrib, final_tau, ranges, gsid], records(gsid)
+    patches = _ahead.render(ctx, dev, key, st, cap, _ahead.try_slot, enqueue_bin, draw)
+    gsid, lists, seg_ws = drawn["gsid"][:patches], drawn["lists"], drawn["seg"]
+    # only now, with the draw stage enqueued, is the order buffer written and are the gradient records cleared
+    h = None
+    if keep == "handle":
+        h = _make_records(dev, st, (us, cinv2ds, alphas, colors), width, height, rec, order, gpack,
+                          lists, (gsid, ranges) if lists is not None else None)
+        if h is not None:
+            h.visible = visible
+            h.seg = seg_ws              # the segment states of this draw (long lists split over waves), if any
+    elif keep == "public" and lists is not None:    # no tensor is referenced, no record kept: values are validated
+        h = _make_records(dev, st, None, width, height, None, order, gpack, lists, None, stamp, n, int(gsid.shape[0]))
+    kept = (seg_ws, lists) if (seg_ws is not None and keep != "handle") else None
+    return [image, contrib, final_tau, ranges, gsid], h, kept
 
 
 def splatB(height, width, us, cinv2ds, alphas, depths, colors, contrib, final_tau, patch_range_per_tile,
@@ -715,8 +504,8 @@ def splatB(height, width, us, cinv2ds, alphas, depths, colors, contrib, final_ta
     rec, order, gpack, walked = (None, None, None, None)
     seg, rebuild, seg_hint = None, 0, None
     if n > 0 and pol.footprint != 1:   # (the pixel-box policy's records also depend on `areas`, which splat mutates)
-        from . import fused as _fused
-        use_seg, seg_hint = _fused._seg_decision(_fused._ctx(dev), lib, (n, width, height), pol)
+        use_seg, seg_hint, _ = _ahead._seg_decision(_ahead._ctx(dev), lib, (n, width, height), pol, _fused.SEGMENTS,
+                                                    _fused.SEG_SPECULATE)
         if records is not None:        # explicit handle: trusted if the signatures still match
             rec, order, gpack = _take_records(records, dev, st, (us, cinv2ds, alphas, colors), width, height)
             if rec is not None:        # ... and the list with block masks, if gsid / ranges are that splat's own pair
@@ -726,10 +515,10 @@ def splatB(height, width, us, cinv2ds, alphas, depths, colors, contrib, final_ta
                 if records.seg is not None and sig is not None and sig == records.pair_sig:
                     seg = records.seg
         elif _memo_enabled:            # public pair: what the last splat of this stream kept, validated by CONTENT
-            h = _splat_memo.get((dev.index, int(st.value or 0)))
+            h = _splat_memo.get(_stream_key(dev, st))
             npatch = gsid.shape[0]
             if (h is not None and h.tensors is None and h.lists is not None and h.n == n and h.width == width
-                    and h.height == height and h.policy == _policy_name and h.npatch == npatch > 0   # (the kept
+                    and h.height == height and h.policy == get_policy() and h.npatch == npatch > 0   # (the kept
                     # list is valid for exactly that many entries: a capacity-sized buffer holds garbage behind them)
                     and pol.alpha_skip > 0 and (gsid.data_ptr() & 15) == 0):
                 rec = torch.empty((n, 12), dtype=torch.float32, device=dev)
@@ -744,8 +533,8 @@ def splatB(height, width, us, cinv2ds, alphas, depths, colors, contrib, final_ta
         if seg is None and records is None and _pair_states_enabled and gsid.shape[0] > 0:
             # the public pair: the states the splat of exactly these tensors left (same four outputs by memory and
             # version -- held alive by the entry --, same inputs by memory and version, same policy and size)
-            e = _pair_states.get((dev.index, int(st.value or 0)))
-            if e is not None and not (e["width"] == width and e["height"] == height and e["policy"] == _policy_name):
+            e = _pair_states.get(_stream_key(dev, st))
+            if e is not None and not (e["width"] == width and e["height"] == height and e["policy"] == get_policy()):
                 e = None
             if e is not None and "snap" in e:
                 # CONTENT mode: differentiate the snapshot of that splat from its own states at once (self-consistent
@@ -766,13 +555,13 @@ def splatB(height, width, us, cinv2ds, alphas, depths, colors, contrib, final_ta
                                                      _ptr(v[3]), None, C.byref(pol), _ptr(v[4]), _ptr(v[5]), _ptr(v[6]),
                                                      _ptr(e["lists"] if lists_ok else v[7]), _ptr(dl), _ptr(ws), ws_bytes,
                                                      None, None, _ptr(d_us), _ptr(d_cinv), _ptr(d_alpha), _ptr(d_color),
-                                                     2 if lists_ok else 0, _ptr(e["seg"]), e["seg"].numel(), 0,
-                                                     seg_hint, st))
+                                                     _fused.DRAW_MASKED_LISTS if lists_ok else 0, _ptr(e["seg"]),
+                                                     e["seg"].numel(), 0, seg_hint, st))
                     verdict.synchronize()
                     if not bool(e["flag"][0]):
                         _last_splatB.update(segments=True, rebuilt=False, kept_states=True)
                         return [d_us, d_cinv, d_alpha, d_color]
-                    _pair_states.pop((dev.index, int(st.value or 0)), None)     # (not this call's tensors: again, below)
+                    _pair_states.pop(_stream_key(dev, st), None)     # (not this call's tensors: again, below)
             elif (e is not None and _memo_sig((contrib, final_tau, ranges, gsid)) == e["sig"]
                     and _memo_sig(e["outs"]) == e["sig"] and _memo_sig((us, cinv2ds, alphas, colors)) == e["in_sig"]):
                 seg, kept_states = e["seg"], True
@@ -788,11 +577,9 @@ def splatB(height, width, us, cinv2ds, alphas, depths, colors, contrib, final_ta
                                          _ptr(colors), _ptr(rec), C.byref(pol), _ptr(contrib), _ptr(final_tau),
                                          _ptr(ranges), _ptr(gsid if walked is None else walked), _ptr(dl), _ptr(ws),
                                          ws_bytes, _ptr(order), _ptr(gpack), _ptr(d_us), _ptr(d_cinv), _ptr(d_alpha),
-                                         _ptr(d_color), 0 if walked is None else 2, _ptr(seg),
+                                         _ptr(d_color), 0 if walked is None else _fused.DRAW_MASKED_LISTS, _ptr(seg),
                                          seg.numel() if seg is not None else 0, rebuild, seg_hint, st))
         _last_splatB.update(segments=seg is not None, rebuilt=bool(rebuild), kept_states=kept_states)
-    elif rec is not None:   # (unreachable: records are only taken under the tile-footprint policies)
-        raise AssertionError
     else:
         _lib.check(lib.egs_splat_bwd(n, gsid.shape[0], width, height, _ptr(us), _ptr(cinv2ds), _ptr(alphas),
                                      _ptr(colors), _ptr(areas), C.byref(pol), _ptr(contrib), _ptr(final_tau),

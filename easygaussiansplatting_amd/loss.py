@@ -17,7 +17,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .gsplatcu import _chk, _lib_on, _ptr, _stream
+from ._host import _chk, _lib_on, _ptr, _stream
 
 
 def gau_loss_with_grad(image, gt_image, loss_lambda=0.2, need_grad=True, grad_scale=1.0):

@@ -347,7 +347,7 @@ def test_segment_end_states_equal_the_oracles(fx, reset, spec):
 
 
 def test_hint_words_are_a_completed_renders_pair_and_steer_the_path(fx):
-    """What the host steers the path by (fused._seg_decision): {longest list, longest walk} of ONE completed render,
+    """What the host steers the path by (_ahead._seg_decision): {longest list, longest walk} of ONE completed render,
     published to the page-locked slot by the NEXT render's range kernel (csrc/egs_bin.hip k_tile_ranges; round 6 found the
     earlier forms -- running maxima, words from two different cameras -- flipping the path mid-epoch).  Two cameras of
     very different walks alternate; after every render the slot must hold exactly the previous render's pair, computed

@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--warm", type=int, default=3,
-                help="steps in front, each waited for: the draw stage's path selection (fused._seg_decision) steers by what "
+                help="steps in front, each waited for: the draw stage's path selection (_ahead._seg_decision) steers by what "
                      "EARLIER renders reported, and a render's report reaches the host with the next render's binning "
                      "stage -- without them a 3-step counter pass measures the first-sight path (round 6: the segment "
                      "kernels on the bench scene), not the steady state")
