@@ -1208,19 +1208,11 @@ def test_gau_loss_full_hd_vs_oracle_and_torch(gsc):
     loss = gau_loss(xt, dev(y))
     loss.backward()
     # plain PyTorch fp32 reference of the same op on the device (five depthwise convs + autograd)
-    import torch.nn.functional as F
-    gw = torch.from_numpy(O.ssim_window().astype(np.float32)).cuda()
-    w2 = (gw[:, None] @ gw[None, :]).expand(3, 1, 11, 11).contiguous()
-    xr = dev(x).requires_grad_(True); yr = dev(y)
-    conv = lambda t: F.conv2d(t, w2, padding=5, groups=3)
-    mu1, mu2 = conv(xr), conv(yr)
-    s11 = conv(xr * xr) - mu1 * mu1; s22 = conv(yr * yr) - mu2 * mu2; s12 = conv(xr * yr) - mu1 * mu2
-    ss = ((2 * mu1 * mu2 + 1e-4) * (2 * s12 + 9e-4)) / ((mu1 * mu1 + mu2 * mu2 + 1e-4) * (s11 + s22 + 9e-4))
-    lr = 0.8 * (xr - yr).abs().mean() + 0.2 * (1 - ss.mean())
-    lr.backward()
+    from tests.loss_cases import ref32
+    lr, ref_grad, _ = ref32(x, y, 0.2, "cuda")
     assert abs(float(loss) - float(lr)) < 2e-6
-    gmax = float(xr.grad.abs().max())
-    assert float((xt.grad - xr.grad).abs().max()) < 2e-4 * gmax
+    gmax = float(ref_grad.abs().max())
+    assert float((xt.grad - ref_grad).abs().max()) < 2e-4 * gmax
     # and the float64 oracle on a crop that includes two image borders
     lo, go, _ = O.gau_loss(x[:, :40, :70], y[:, :40, :70], 0.2, calc_grad=True)
     xc = dev(x[:, :40, :70]).requires_grad_(True)
