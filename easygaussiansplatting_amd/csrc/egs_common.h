@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 
 #include "../../include/egs_hip.h"
 
@@ -63,6 +64,33 @@ struct ProfScope {
     ::egs::ProfScope ps__(name, stream);                                 \
     hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);     \
   } while (0)
+
+// ---- runtime flags -> template arguments --------------------------------------
+// A kernel's flavour is a set of template arguments; a launch site turns its runtime flags into them once:
+//   decltype(&k<false, false>) kern = nullptr;
+//   with_bools([&](auto raw, auto aa) { kern = k<raw.value, aa.value>; }, is_raw, is_aa);
+//   EGS_LAUNCH(label, kern, grid, block, stream, arguments...);
+// calls the generic lambda with one std::true_type / std::false_type per flag (2^flags instantiations of its body:
+// exactly the kernel instances it names).  The lambda only picks the instance -- every instance of a template has one
+// signature -- so the launch, its arguments and its profiler bracket exist once per site, not once per instance.
+template <typename F>
+inline void with_bools(F&& f) { f(); }
+template <typename F, typename... B>
+inline void with_bools(F&& f, bool b0, B... rest) {
+  if (b0) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+// SH row width (3 (degree + 1)^2 floats; checked by the caller) -> f(std::integral_constant<int, NC>): NC coefficients
+// per colour channel
+template <typename F>
+inline void with_sh_dim(int sh_dim, F&& f) {
+  switch (sh_dim) {
+    case 3: f(std::integral_constant<int, 1>{}); break;
+    case 12: f(std::integral_constant<int, 4>{}); break;
+    case 27: f(std::integral_constant<int, 9>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+  }
+}
 
 static inline int div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

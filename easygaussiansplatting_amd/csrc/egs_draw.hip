@@ -263,34 +263,237 @@ int draw_grid(const DrawParams& p) {
 // the per-block scalar branches and the early exit.
 //
 // EXTRA (render extras, DrawExtras): the same walk also blends the Gaussian's camera-space z (depth) and the constant 1
-// (alpha = 1 - T_final) and adds T_final * bg to the image.  k_draw is the EXTRA = false instance of this body.
-template <bool BOX, bool FLOOR, bool CLAMP, bool SKIP>
+// (alpha = 1 - T_final) and adds T_final * bg to the image.
+// Non-BOX entries carry z in the free pair of their third piece (11 floats), BOX entries in sZ.  k_draw's occupancy cap
+// kept: at eight waves the depth accumulators spill 16 B per lane outside the blend loop, and that is faster than six
+// waves without spills (bench scene: 166 against 197 us).  `ex` is read by the EXTRA instances only.
+template <bool BOX, bool FLOOR, bool CLAMP, bool SKIP, bool EXTRA>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((!BOX && SKIP) ? 8 : 6, 8))) void k_draw(DrawParams p, int32_t* __restrict__ ranges,
-                                             const int32_t* __restrict__ gsid,
-                                             const float4* __restrict__ rec, float* __restrict__ image,
-                                             int32_t* __restrict__ contrib, float* __restrict__ final_tau) {
-  // staged entry: 12 floats (BOX: three b128 pieces) or 10 (two b128 + one b64: an entry's broadcast reads are
-  // 50 of the ~130 SIMD cycles it costs, on an LDS pipe the CU's four SIMDs share; b64 is half a b128)
-  // (the third piece keeps the 16-B slot stride: all three reads are immediate offsets from ONE address register)
-  __shared__ float4 sA[64], sB[64], sC[64];
-  constexpr bool EXTRA = false;
-  const DrawExtras ex = {};
-  float* const sZ = nullptr;
-#include "egs_draw_fwd.inc"
-}
-// the EXTRA flavour: non-BOX entries carry z in the free pair of their third piece (11 floats), BOX entries in sZ.
-// k_draw's occupancy cap kept: at eight waves the depth accumulators spill 16 B per lane outside the blend loop, and that
-// is faster than six waves without spills (bench scene: 166 against 197 us)
-template <bool BOX, bool FLOOR, bool CLAMP, bool SKIP>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((!BOX && SKIP) ? 8 : 6, 8))) void k_draw_extra(DrawParams p, int32_t* __restrict__ ranges,
                                              const int32_t* __restrict__ gsid,
                                              const float4* __restrict__ rec, float* __restrict__ image,
                                              int32_t* __restrict__ contrib, float* __restrict__ final_tau,
                                              DrawExtras ex) {
+  // staged entry: 12 floats (BOX: three b128 pieces) or 10 (two b128 + one b64: an entry's broadcast reads are
+  // 50 of the ~130 SIMD cycles it costs, on an LDS pipe the CU's four SIMDs share; b64 is half a b128)
+  // (the third piece keeps the 16-B slot stride: all three reads are immediate offsets from ONE address register)
   __shared__ float4 sA[64], sB[64], sC[64];
-  __shared__ float sZ[BOX ? 64 : 1];
-  constexpr bool EXTRA = true;
-#include "egs_draw_fwd.inc"
+  __shared__ float sZ[(EXTRA && BOX) ? 64 : 1];   // (never touched by the other instances: no LDS there)
+  const int lane = threadIdx.x;
+  if (p.zero_buf) {   // every workgroup of the grid (padding ones included) clears its slice
+    const uint32_t z0 = blockIdx.x * p.zero_per, z1 = min(p.zero_n4, z0 + p.zero_per);
+    float4* __restrict__ zb = p.zero_buf;
+    for (uint32_t i = z0 + lane; i < z1; i += 64) zb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const int tile = xcd_tile(blockIdx.x, p);
+  if (tile < 0) return;
+  const int r0 = ranges[2 * (size_t)tile], r1 = ranges[2 * (size_t)tile + 1];
+  const int n = r1 - r0;
+  const int tx0 = (tile % p.gx) * EGS_TILE, ty0 = (tile / p.gx) * EGS_TILE;
+  // pixel k = 2*by + bx of this lane: (tx0 + (lane&7) + 8 bx, ty0 + (lane>>3) + 8 by)
+  const int pxb[2] = {tx0 + (lane & 7), tx0 + (lane & 7) + 8};
+  const int pyb[2] = {ty0 + (lane >> 3), ty0 + (lane >> 3) + 8};
+  if (n <= 0) {  // empty tile: image = 0, contrib = 0 and final_tau = 0 (NOT 1), exactly what the
+                 // reference's early return leaves in its zero-filled outputs (kernel.cu:182)
+    if (p.work_out && lane == 0) { p.work_out[tile] = 0; if (p.walk_out) p.walk_out[tile] = 0; walk_raise(p.walk_max, 0); }
+    // a tile without patches still holds the (INT_MAX, 0) the binning initialised it with: (0, 0), as the reference
+    if (lane == 0 && (r0 != 0 || r1 != 0)) { ranges[2 * (size_t)tile] = 0; ranges[2 * (size_t)tile + 1] = 0; }
+    const size_t HW0 = (size_t)p.W * p.H;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int px = pxb[k & 1], py = pyb[k >> 1];
+      if (px < p.W && py < p.H) {
+        const size_t pix = (size_t)py * p.W + px;
+        if constexpr (EXTRA) {   // T = 1 here: the background, no depth, no opacity (final_tau keeps its quirk)
+          image[pix] = ex.bg[0]; image[HW0 + pix] = ex.bg[1]; image[2 * HW0 + pix] = ex.bg[2];
+          if (ex.depth_out) ex.depth_out[pix] = 0.f;
+          if (ex.alpha_out) ex.alpha_out[pix] = 0.f;
+        } else {
+          image[pix] = 0.f; image[HW0 + pix] = 0.f; image[2 * HW0 + pix] = 0.f;
+        }
+        contrib[pix] = 0; final_tau[pix] = 0.f;
+      }
+    }
+    return;
+  }
+  // The exponent of alpha' = exp2(e) is evaluated as a polynomial in the pixel's offset (X, Y) from the TILE
+  // CENTRE:  e = c0 + c1 X + c2 Y + qxx XX + qxy XY + qyy YY  with the entry's  c0 = log2(alpha) + E(D),
+  // (c1, c2) = grad E(D), D = tile centre - u, computed once per (tile, entry) by the lane that stages the
+  // entry (64 entries in parallel), and the six monomials per-lane CONSTANTS (|X|, |Y| <= 7.5).  Five FMAs
+  // per 8x8 block and no per-entry set-up (the separable form cxx[bx] + cyy[by] + cxy[bx] dy[by] cost 14
+  // VALU instructions per entry before the first block); same accuracy as differences from u itself
+  // (emulated in fp32 on the 1 M scene: mean |error| 6e-7, max 4e-5 in the log2 domain, either way).
+  const float X[2] = {(float)(lane & 7) - 7.5f, (float)(lane & 7) + 0.5f};
+  const float Y[2] = {(float)(lane >> 3) - 7.5f, (float)(lane >> 3) + 0.5f};
+  const float XX[2] = {X[0] * X[0], X[1] * X[1]}, YY[2] = {Y[0] * Y[0], Y[1] * Y[1]};
+  const float XY[4] = {X[0] * Y[0], X[1] * Y[0], X[0] * Y[1], X[1] * Y[1]};
+  // A pixel is finished when its tau fell below tau_stop (kernel.cu:256-260): `tau >= stop` IS the
+  // "still blending" test, so no separate done flag is kept.  Lanes outside the image start at -1.
+  float tau[4], cr[4], cg[4], cb[4];
+  float cd[4];   // EXTRA: sum w z
+  int cont[4];
+  int live = 0;  // wave-uniform: bit k set while block k still has an unfinished pixel
+  const float stop = p.tau_stop, lskip = p.lskip;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    cont[k] = 0;
+    tau[k] = ((pxb[k & 1] < p.W) && (pyb[k >> 1] < p.H)) ? 1.f : -1.f;
+    cr[k] = 0.f; cg[k] = 0.f; cb[k] = 0.f;
+    cd[k] = 0.f;
+    if (__any(tau[k] >= stop)) live |= 1 << k;
+  }
+  constexpr float L99 = -0.014499569695115089f;  // log2(0.99): min(0.99, a) == exp2(min(log2 a, L99))
+  const float cx0 = (float)tx0 + 7.5f, cy0 = (float)ty0 + 7.5f;
+  // alpha' >= alpha_skip (kernel.cu:246) in the exponent domain: e >= log2(skip), a kernel constant (SKIP =
+  // the policy has a skip threshold, compiled in); without one only a NaN exponent fails the compare
+  const float lthr = SKIP ? lskip : -INFINITY;
+  // the list value of the NEXT chunk is fetched one chunk ahead: the staging of a chunk then pays one global
+  // latency (the record gather), not two dependent ones
+  int gnext = (lane < n) ? gsid[r0 + lane] : 0;
+  for (int base = 0; base < n && live != 0; base += 64) {
+    __syncthreads();  // single-wave workgroup: orders the LDS reads of the previous chunk
+    int mymask = 0;   // reach mask of the entry THIS lane staged (lane j <-> entry base + j)
+    const int gm = gnext;
+    const int g = p.masked ? (int)((uint32_t)gm & EGS_GSID_MASK) : gm;
+    if (base + 64 + lane < n) gnext = gsid[r0 + base + 64 + lane];
+    if (base + lane < n) {
+      float4 A = rec[3 * (size_t)g], B = rec[3 * (size_t)g + 1];
+      const float4 C = rec[3 * (size_t)g + 2];
+      float z = 0.f;
+      if constexpr (EXTRA) z = ex.depths[g];
+      const bool nanfix = p.nan_blend && nan_entry_fix(A, B);
+      // the record's thr = log2(skip / alpha), +inf for an entry that never blends (alpha < skip, or
+      // alpha < 0 when there is no skip test): such an entry reaches nothing
+      if (C.w < INFINITY) mymask = p.masked ? (int)((uint32_t)gm >> EGS_GSID_BITS) : reach_mask<BOX>(A, C, tx0, ty0);
+      if (nanfix && !BOX && !p.masked && C.w < INFINITY) mymask = 0xF;
+      // alpha' = exp2(e), e = log2(alpha) + log2 exp(-maha/2) (F.5.1, common.cuh:85-88, pre-scaled conic):
+      // no multiply by alpha; the floor (maha >= 0) and the 0.99 clamp are ONE min against `cap`
+      const float la = SKIP ? lskip - C.w : __builtin_amdgcn_logf(B.y);
+      float cap = 3.0e38f;
+      if (FLOOR) cap = CLAMP ? fminf(la, L99) : la;
+      else if (CLAMP) cap = L99;
+      const float Dx = cx0 - A.x, Dy = cy0 - A.y;
+      const float c0 = la + (A.z * Dx * Dx + A.w * Dx * Dy + B.x * Dy * Dy);
+      const float c1 = 2.f * A.z * Dx + A.w * Dy, c2 = 2.f * B.x * Dy + A.w * Dx;
+      sA[lane] = make_float4(A.z, A.w, B.x, cap);   // qxx, qxy, qyy, cap
+      if constexpr (BOX) {
+        sB[lane] = make_float4(c0, c1, c2, C.y);      // polynomial about the tile centre; x pixel box
+        sC[lane] = make_float4(B.z, B.w, C.x, C.z);   // colour; y pixel box
+        if constexpr (EXTRA) sZ[lane] = z;            // (no free float in the BOX slots: a piece of its own)
+      } else {
+        sB[lane] = make_float4(c0, c1, c2, B.z);      // polynomial about the tile centre; red
+        if constexpr (EXTRA) sC[lane] = make_float4(B.w, C.x, z, 0.f);   // green, blue, z
+        else *reinterpret_cast<float2*>(&sC[lane]) = make_float2(B.w, C.x);   // green, blue
+      }
+    }
+    __syncthreads();
+    // The reach masks of eight consecutive entries packed into one dword (4 bits each), gathered into the
+    // group's first lane through the LDS permute path (ds_bpermute: no VALU issue slot): the blend loop
+    // reads ONE SGPR per group of eight entries, skips the whole group when none of them reaches a live
+    // block, and is fully unrolled over the group -- LDS addresses are an immediate offset from one base,
+    // no per-entry v_readlane / v_mov / loop counter.  (Entries past the end of the list staged mask 0.)
+    int pk = mymask;
+    pk |= __shfl_down(pk, 1, 64) << 4;
+    pk |= __shfl_down(pk, 2, 64) << 8;
+    pk |= __shfl_down(pk, 4, 64) << 16;
+    const int m = __builtin_amdgcn_readfirstlane(min(64, n - base));
+    for (int j0 = 0; j0 < m && live != 0; j0 += 8) {  // eight entries, then the live-mask refresh
+    const uint32_t act = (uint32_t)__builtin_amdgcn_readlane(pk, j0) & ((uint32_t)live * 0x11111111u);
+    if (act != 0u) {
+    const int vidx0 = base + j0 + 1;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int reach = (int)((act >> (4 * t)) & 0xFu);
+      if (reach != 0) {  // scalar branch: some live block is within reach of this entry
+        const int j = j0 + t;
+        const float4 Q = sA[j], P = sB[j];            // wave-uniform address: LDS broadcast
+        float4 K;
+        float zj = 0.f;
+        if constexpr (BOX) { K = sC[j]; if constexpr (EXTRA) zj = sZ[j]; }
+        else if constexpr (EXTRA) { const float4 gbz = sC[j]; K = make_float4(P.w, gbz.x, gbz.y, 0.f); zj = gbz.z; }
+        else { const float2 gb = *reinterpret_cast<const float2*>(&sC[j]); K = make_float4(P.w, gb.x, gb.y, 0.f); }
+        bool inx[2] = {true, true}, iny[2] = {true, true};
+        if (BOX) {
+          const uint32_t bx = __float_as_uint(P.w), by = __float_as_uint(K.w);
+          const int x0 = bx & 0xFFFF, x1 = bx >> 16, y0 = by & 0xFFFF, y1 = by >> 16;
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            inx[b] = (pxb[b] >= x0) && (pxb[b] < x1);
+            iny[b] = (pyb[b] >= y0) && (pyb[b] < y1);
+          }
+        }
+        const int idx = vidx0 + t;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int bx = k & 1, by = k >> 1;
+          if (reach & (1 << k)) {  // scalar branch: the whole 8x8 block is live and in reach
+            float e = fmaf(P.z, Y[by], P.x);
+            e = fmaf(P.y, X[bx], e);
+            e = fmaf(Q.z, YY[by], e);
+            e = fmaf(Q.y, XY[k], e);
+            e = fmaf(Q.x, XX[bx], e);
+            // unfinished and alpha' >= alpha_skip; the cap cannot change the outcome of the skip test
+            // (cap >= log2(skip) for every entry that blends at all), so it is applied to the hits only
+            bool hit = (tau[k] >= stop) && (e >= lthr);
+            if (BOX) hit = hit && inx[bx] && iny[by];
+            if (hit) {
+              if (FLOOR || CLAMP) e = min_hi(e, Q.w);
+              const float w = tau[k] * __builtin_amdgcn_exp2f(e);  // F.5: tau alpha'
+              cr[k] += w * K.x; cg[k] += w * K.y; cb[k] += w * K.z;
+              if constexpr (EXTRA) cd[k] += w * zj;
+              tau[k] -= w;  // F.5.2: tau (1 - alpha')
+              cont[k] = idx;
+            }
+          }
+        }
+      }
+    }
+    // Finished pixels fail `tau >= stop` on their own, so the live-block mask only saves work: it is
+    // refreshed after a group that blended something instead of tracking "some pixel just finished" per
+    // block; when it empties, every pixel of the tile is finished and both loops end (scalar exit).
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((live & (1 << k)) && !__any(tau[k] >= stop)) live &= ~(1 << k);
+    }
+    }
+  }
+  if (p.work_out) {   // what k_draw_bwd will walk: the largest contributor index of the tile and of its blocks
+    int w = 0, wmax = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      int mx = cont[k];
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) mx = max(mx, __shfl_xor(mx, d, 64));
+      w += mx;
+      wmax = max(wmax, mx);
+    }
+    if (lane == 0) {
+      p.work_out[tile] = w + 2 * wmax;
+      if (p.walk_out) p.walk_out[tile] = wmax;
+      walk_raise(p.walk_max, wmax);
+      if (p.walk_max) walk_raise(p.walk_max + 1, n);      // ... and the longest list of the same render
+    }
+  }
+  const size_t HW = (size_t)p.W * p.H;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int px = pxb[k & 1], py = pyb[k >> 1];
+    if (px < p.W && py < p.H) {
+      const size_t pix = (size_t)py * p.W + px;
+      if constexpr (EXTRA) {   // what is left of the transmittance sees the background; alpha = 1 - T_final
+        image[pix] = fmaf(tau[k], ex.bg[0], cr[k]);
+        image[HW + pix] = fmaf(tau[k], ex.bg[1], cg[k]);
+        image[2 * HW + pix] = fmaf(tau[k], ex.bg[2], cb[k]);
+        if (ex.depth_out) ex.depth_out[pix] = cd[k];
+        if (ex.alpha_out) ex.alpha_out[pix] = 1.f - tau[k];
+      } else {
+        image[pix] = cr[k];
+        image[HW + pix] = cg[k];
+        image[2 * HW + pix] = cb[k];
+      }
+      contrib[pix] = cont[k];
+      final_tau[pix] = tau[k];
+    }
+  }
 }
 
 // ============================================================================
@@ -428,38 +631,321 @@ __device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c
 // EXTRA (render extras, DrawExtras; never with SEG): the loss also sees depth = sum w z and alpha = sum w, and the image
 // T_final * bg.  The scalar recurrence stays one register: lq starts at dL/dgamma . bg (the colour behind the last
 // contributor) minus dL/dalpha, and dq gains dL/ddepth z; a tenth partial dz = sum dL/ddepth w goes to gpack[i][9].
-template <bool BOX, bool FLOOR, bool CLAMP, int RED, bool SEG = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_draw_bwd(DrawParams p, const int32_t* __restrict__ ranges,
+// z of the staged entries in sZ, next to sD.  Four waves per SIMD (111-114 VGPRs): under the plain instances' cap of five
+// the tenth partial and the per-pixel dL/ddepth spill 44-60 B per lane, and that is slower (bench scene: 531 against
+// 494 us).
+// fa: the flavour's own argument -- SegArgs fa.sg, or DrawExtras fa.ex for EXTRA (DrawBwdFlavour, egs_raster.h)
+template <bool BOX, bool FLOOR, bool CLAMP, int RED, bool SEG, bool EXTRA>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 5, 8))) void k_draw_bwd(DrawParams p, const int32_t* __restrict__ ranges,
                                                  const int32_t* __restrict__ gsid,
                                                  const float4* __restrict__ rec,
                                                  const float* __restrict__ final_tau,
                                                  const int32_t* __restrict__ contrib,
                                                  const float* __restrict__ dLdg,
-                                                 float* __restrict__ gpack, SegArgs sg) {
+                                                 float* __restrict__ gpack, DrawBwdFlavour<EXTRA> fa) {
+  static_assert(!(SEG && EXTRA), "the EXTRA flavour draws unsplit lists only");
   __shared__ float4 sA[64], sB[64], sC[64], sD[64];  // sD = {cinv.x, cinv.y, cinv.z, gsid}
   __shared__ float4 szero[3];                        // a line of zeros (see the accumulator reset below)
-  constexpr bool EXTRA = false;
-  const DrawExtras ex = {};
-  float* const sZ = nullptr;
-#include "egs_draw_bwd.inc"
-}
-// the EXTRA flavour (unsplit lists only): z of the staged entries in sZ, next to sD.  Four waves per SIMD (111-114
-// VGPRs): under k_draw_bwd's cap of five the tenth partial and the per-pixel dL/ddepth spill 44-60 B per lane, and that
-// is slower (bench scene: 531 against 494 us)
-template <bool BOX, bool FLOOR, bool CLAMP, int RED>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_draw_bwd_extra(DrawParams p, const int32_t* __restrict__ ranges,
-                                                 const int32_t* __restrict__ gsid,
-                                                 const float4* __restrict__ rec,
-                                                 const float* __restrict__ final_tau,
-                                                 const int32_t* __restrict__ contrib,
-                                                 const float* __restrict__ dLdg,
-                                                 float* __restrict__ gpack, DrawExtras ex) {
-  __shared__ float4 sA[64], sB[64], sC[64], sD[64];
-  __shared__ float4 szero[3];
-  __shared__ float sZ[64];
-  constexpr bool SEG = false, EXTRA = true;
-  const SegArgs sg = {};
-#include "egs_draw_bwd.inc"
+  __shared__ float sZ[EXTRA ? 64 : 1];               // (never touched by the other instances: no LDS there)
+  constexpr bool ZLDS = (RED & 2) != 0, LAZY = (RED & 4) != 0;
+  constexpr int NQ = EXTRA ? 10 : 9;
+  if (ZLDS && threadIdx.x < 3) szero[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
+  const uint32_t zaddr = (uint32_t)(uintptr_t)szero;   // LDS byte offset of the zero line
+  int tile, seg_lo = 0, seg_hi = 0x7fffffff;   // SEG: the entries [seg_lo, seg_hi) of the tile's list are this wave's
+  size_t seg_state = 0;
+  bool seg_item = false;
+  if constexpr (SEG) {
+    if ((int)blockIdx.x >= min(fa.sg.hdr[SH_ITEMS1], fa.sg.item_cap)) return;
+    const uint32_t item = (uint32_t)fa.sg.items1[blockIdx.x];
+    tile = (int)(item & SEG_TILE_MASK);
+    if (tile >= p.T) return;
+    if ((item >> 30) == (uint32_t)SEG_SPEC) {
+      const int L = fa.sg.hdr[SH_L], sidx = (int)((item >> 19) & SEG_SEG_MASK);
+      seg_item = true;
+      seg_lo = sidx * L; seg_hi = seg_lo + L;
+      seg_state = ((size_t)(fa.sg.seg_base[tile] + sidx)) * 256 + threadIdx.x;
+    }
+  } else {
+    tile = xcd_tile(blockIdx.x, p);
+    if (tile < 0) return;
+  }
+  const int r0 = ranges[2 * (size_t)tile], r1 = ranges[2 * (size_t)tile + 1];
+  const int n = r1 - r0;
+  if (n <= 0) return;
+  if (SEG) seg_hi = min(seg_hi, n);
+  const int lane = threadIdx.x;
+  const int tx0 = (tile % p.gx) * EGS_TILE, ty0 = (tile / p.gx) * EGS_TILE;
+  const int pxb[2] = {tx0 + (lane & 7), tx0 + (lane & 7) + 8};
+  const int pyb[2] = {ty0 + (lane >> 3), ty0 + (lane >> 3) + 8};
+  const float fpx[2] = {(float)pxb[0], (float)pxb[1]};
+  const float fpy[2] = {(float)pyb[0], (float)pyb[1]};
+  const size_t HW = (size_t)p.W * p.H;
+  // lq = dL/dgamma . gamma_cur2last: the only combination of gamma_cur2last (kernel.cu:854,948)
+  // the gradient needs, so the 3-vector recurrence q += a'(c - q) is carried as one scalar
+  float tau[4], lr[4], lg[4], lb[4], lq[4];
+  float ld[4], la[4];   // EXTRA: dL/ddepth, dL/dalpha of the pixel
+  int cont[4];
+  int bmax[4];  // wave-uniform: largest contrib of block k -> entries >= bmax[k] are inert for it
+  int maxcont = 0;
+  // (all twenty loads requested first, from clamped addresses: guarded and inside the loop below, every block's
+  // five waited for their own round trip before the next block's were issued)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int px = pxb[k & 1], py = pyb[k >> 1];
+    const size_t pix = (size_t)min(py, p.H - 1) * p.W + min(px, p.W - 1);
+    tau[k] = final_tau[pix];
+    cont[k] = contrib[pix];
+    lr[k] = dLdg[pix]; lg[k] = dLdg[HW + pix]; lb[k] = dLdg[2 * HW + pix];
+    lq[k] = 0.f;
+    ld[k] = 0.f; la[k] = 0.f;
+    if constexpr (EXTRA) {
+      if (fa.ex.dl_depth) ld[k] = fa.ex.dl_depth[pix];
+      if (fa.ex.dl_alpha) la[k] = fa.ex.dl_alpha[pix];
+    }
+  }
+  if constexpr (EXTRA) {
+    // lq - dL/dalpha is carried instead of lq: dq = dL/dgamma . c + dL/ddepth z + dL/dalpha - lq with one FMA per hit,
+    // and the update lq += a' dq is the same for both
+#pragma unroll
+    for (int k = 0; k < 4; ++k) lq[k] = lr[k] * fa.ex.bg[0] + lg[k] * fa.ex.bg[1] + lb[k] * fa.ex.bg[2] - la[k];
+  }
+  float4 segE[4];
+  if constexpr (SEG) {   // (requested with the loads above; a DIRECT item or the last segment never uses them)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) segE[k] = seg_item ? fa.sg.st4[seg_state + 64 * k] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int px = pxb[k & 1], py = pyb[k >> 1];
+    if (!(px < p.W && py < p.H)) { tau[k] = 0.f; cont[k] = 0; lr[k] = 0.f; lg[k] = 0.f; lb[k] = 0.f; }
+    if constexpr (SEG) {
+      if (seg_item) {
+        if (cont[k] > seg_hi) {          // contributors behind this segment: start from the state at its end
+          tau[k] = segE[k].w;
+          lq[k] = lr[k] * segE[k].x + lg[k] * segE[k].y + lb[k] * segE[k].z;
+          cont[k] = seg_hi;
+        } else if (cont[k] <= seg_lo) {  // the pixel never got this far
+          cont[k] = 0;
+        }
+      }
+    }
+    int mx = cont[k];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mx = max(mx, __shfl_xor(mx, d, 64));
+    bmax[k] = __builtin_amdgcn_readfirstlane(min(mx, n));
+    maxcont = max(maxcont, bmax[k]);
+  }
+  if (maxcont <= 0) return;
+  // The loads above must be WAITED FOR here, not at their first use inside the loop: gfx9 counts stores and
+  // atomics in the same in-order vmcnt as loads, so a wait the compiler places at the first use (inside the
+  // hit body) would, from the second group on, also wait for the previous group's gradient atomics --
+  // a round trip to L2 per group of four entries on the critical path of the wave.
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    asm volatile("" ::"v"(tau[k]), "v"(lr[k]), "v"(lg[k]), "v"(lb[k]), "v"(cont[k]));
+  if constexpr (EXTRA) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(ld[k]), "v"(lq[k]));
+  }
+  // where the transposing reduction leaves the nine totals inside a row of 16 lanes, and what each of
+  // those lanes adds to the packed gradient record {dalpha, dcolor[3], du[2], dcinv[3]}
+  const int c16 = lane & 15;
+  int qoff = -1, kind = 0;
+  float kscale = 1.f;
+  if (c16 & 1) {
+    if (c16 == 1) { qoff = 8; kscale = -0.5f; }                         // M2yy -> dcinv.z
+    else if (EXTRA && c16 == 3) qoff = 9;                               // dz   -> the first pad slot
+  }
+  else if (c16 == 0) { qoff = 4; kind = 1; }                            // M1x  -> du.x
+  else if (c16 == 2) { qoff = 5; kind = 2; }                            // M1y  -> du.y
+  else if (c16 == 4) qoff = 0;                                          // dalpha
+  else if (c16 == 6) qoff = 1;                                          // dcolor.r
+  else if (c16 == 8) qoff = 2;                                          // dcolor.g
+  else if (c16 == 10) qoff = 3;                                         // dcolor.b
+  else if (c16 == 12) { qoff = 6; kscale = -0.5f; }                     // M2xx -> dcinv.x
+  else { qoff = 7; kscale = -1.f; }                                     // M2xy -> dcinv.y  (lane 14)
+
+  const int c_first = (maxcont - 1) >> 6;
+  int gnext = (c_first * 64 + lane < n) ? gsid[r0 + c_first * 64 + lane] : 0;   // one chunk ahead, as in k_draw
+  const int c_last = SEG ? (seg_lo >> 6) : 0;
+  for (int c = c_first; c >= c_last; --c) {
+    __syncthreads();
+    const int idx = c * 64 + lane;
+    int mymask = 0;  // reach mask of the entry THIS lane staged (lane j <-> entry c*64 + j)
+    const int gm = gnext;
+    const int g = p.masked ? (int)((uint32_t)gm & EGS_GSID_MASK) : gm;
+    if (c > c_last) gnext = gsid[r0 + idx - 64];
+    if (idx < n) {
+      float4 A = rec[3 * (size_t)g], B = rec[3 * (size_t)g + 1];
+      const float4 C = rec[3 * (size_t)g + 2];
+      constexpr float INVQ = 1.f / EGS_NHL2E;
+      // (cinv from the record as it is: an entry with a NaN conic hands NaN to du = -cinv M1, as kernel.cu:926-933 does)
+      const float4 Dc = make_float4(A.z * INVQ, A.w * (0.5f * INVQ), B.x * INVQ, __int_as_float(g));
+      const bool nanfix = p.nan_blend && nan_entry_fix(A, B);
+      mymask = p.masked ? (int)((uint32_t)gm >> EGS_GSID_BITS) : reach_mask<BOX>(A, C, tx0, ty0);
+      if (nanfix && !BOX && !p.masked) mymask = 0xF;
+      sA[lane] = A;
+      sB[lane] = B;
+      sC[lane] = C;
+      if constexpr (EXTRA) sZ[lane] = fa.ex.depths[g];
+      // cinv back out of the pre-scaled conic of the record (q = -0.5 log2(e) (cinv.x, 2 cinv.y, cinv.z)):
+      // no second 12-B gather per patch (131 MB of sector traffic at P = 4.1 M)
+      sD[lane] = Dc;
+    }
+    __syncthreads();
+    // Which entries of this chunk can contribute at all?  Every lane answers for the entry it staged: its
+    // reach mask minus the blocks no pixel of which ever got this far (entry index >= the block's largest
+    // contrib, kernel.cu:899); a scalar bit scan then walks the reachable entries in descending list order.
+    // Groups of four: each of the four accumulator slots takes entries until one of them HITS (a quarter
+    // of the entries that reach a live block hit no pixel: they leave the slot zero and cost neither a
+    // re-zeroing nor a share of a wave reduction).
+    int rl = mymask;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (idx >= bmax[k]) rl &= ~(1 << k);
+    unsigned long long todo = __ballot(rl != 0);
+    while (todo != 0ull) {
+      int je[4] = {-1, -1, -1, -1};   // chunk-local entry index held by slot e
+      float acc[4][NQ];
+      bool any = false;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (ZLDS) {
+          // The nine zeros come out of LDS: broadcast reads of a zero line cost the VALU nothing (nine v_mov_b32 or
+          // five v_mov_b64 are 21 issue cycles per slot in a kernel that is VALU-issue bound; the LDS pipe idles).
+          // Inline asm, because the compiler would hoist a plain load and hand out register copies again.  The
+          // wait is part of the statement: the compiler does not see these loads in its lgkmcnt bookkeeping and
+          // may copy the results anywhere afterwards.  (The wave parks for one LDS latency; its four neighbours
+          // on the SIMD issue meanwhile.)
+          typedef float f4v __attribute__((ext_vector_type(4)));
+          f4v z0, z1;
+          float z2;
+          asm volatile("ds_read_b128 %0, %3\n ds_read_b128 %1, %3 offset:16\n ds_read_b32 %2, %3 offset:32\n"
+                       " s_waitcnt lgkmcnt(0)"
+                       : "=v"(z0), "=v"(z1), "=v"(z2) : "v"(zaddr));
+          acc[e][0] = z0.x; acc[e][1] = z0.y; acc[e][2] = z0.z; acc[e][3] = z0.w;
+          acc[e][4] = z1.x; acc[e][5] = z1.y; acc[e][6] = z1.z; acc[e][7] = z1.w;
+          acc[e][8] = z2;
+        } else {  // nine zeros from five 64-bit moves (v_mov_b64 on gfx940+)
+#pragma unroll
+          for (int q = 0; q < 8; q += 2) {
+            unsigned long long z = 0ull;
+            asm volatile("" : "+v"(z));   // materialise the pair in VGPRs, keep it from being split into two constants
+            acc[e][q] = __uint_as_float((unsigned)z);
+            acc[e][q + 1] = __uint_as_float((unsigned)(z >> 32));
+          }
+          acc[e][8] = 0.f;
+        }
+        if constexpr (EXTRA) acc[e][NQ - 1] = 0.f;
+        while (todo != 0ull) {
+        const int j = 63 - __clzll((long long)todo);
+        todo &= ~(1ull << j);
+        bool any_e = false;
+        const int i = c * 64 + j;  // forward index of this entry in the tile list
+        const int reach = __builtin_amdgcn_readlane(rl, j);  // lane j's register: no LDS round trip
+        const float4 A = sA[j], B = sB[j], C = sC[j];
+        float zj = 0.f;
+        if constexpr (EXTRA) zj = sZ[j];
+        bool inx[2] = {true, true}, iny[2] = {true, true};
+        if (BOX) {
+          const uint32_t bx = __float_as_uint(C.y), by = __float_as_uint(C.z);
+          const int x0 = bx & 0xFFFF, x1 = bx >> 16, y0 = by & 0xFFFF, y1 = by >> 16;
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            inx[b] = (pxb[b] >= x0) && (pxb[b] < x1);
+            iny[b] = (pyb[b] >= y0) && (pyb[b] < y1);
+          }
+        }
+        // LAZY: the exponent from scratch per evaluated block (7 full-rate instructions) instead of the separable
+        // form (14 per entry up front + 2 per block): most entries reach one or two of the four blocks.
+        // (Measured and dropped: skipping the floor / clamp v_med3 for entries with a positive-definite conic and
+        // alpha <= 0.989 behind a wave-uniform flag -- the two scalar branches cost more than the two half-rate
+        // instructions they save: +1.5 %.)
+        float dx[2], dy[2], cxx[2], cxy[2], cyy[2];
+        if (!LAZY) {
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            dx[b] = A.x - fpx[b];
+            cxx[b] = A.z * dx[b] * dx[b];
+            cxy[b] = A.w * dx[b];
+            dy[b] = A.y - fpy[b];
+            cyy[b] = B.x * dy[b] * dy[b];
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int bx = k & 1, by = k >> 1;
+          if (!(reach & (1 << k))) continue;  // scalar branch: block culled or past its last contributor
+          float pw;
+          if (LAZY) {
+            dx[bx] = A.x - fpx[bx];
+            dy[by] = A.y - fpy[by];
+            float t = A.z * dx[bx];
+            t = fmaf(A.w, dy[by], t);
+            pw = t * dx[bx];
+            pw = fmaf(B.x * dy[by], dy[by], pw);
+          } else {
+            pw = cxx[bx] + cyy[by] + cxy[bx] * dy[by];
+          }
+          bool hit = (i < cont[k]) && (pw >= C.w);  // kernel.cu:899,913
+          if (BOX) hit = hit && inx[bx] && iny[by];
+          if (hit) {
+            const float g = __builtin_amdgcn_exp2f(FLOOR ? min_hi(pw, 0.f) : pw);
+            float ap = B.y * g;
+            if (CLAMP) ap = min_hi(ap, 0.99f);
+            const float tk = tau[k] * __builtin_amdgcn_rcpf(1.f - ap);  // undo F.5.2
+            tau[k] = tk;
+            float dq;   // dL/dgamma . (color - gamma_cur2last)
+            if constexpr (EXTRA) dq = fmaf(ld[k], zj, lr[k] * B.z + lg[k] * B.w + lb[k] * C.x) - lq[k];
+            else dq = (lr[k] * B.z + lg[k] * B.w + lb[k] * C.x) - lq[k];
+            const float dl_dap = tk * dq;  // B.5a
+            acc[e][0] += dl_dap * g;  // dalpha'/dalpha = g, also where the clamp binds (kernel.cu:921)
+            const float wgt = ap * tk;
+            acc[e][1] += lr[k] * wgt; acc[e][2] += lg[k] * wgt; acc[e][3] += lb[k] * wgt;
+            if constexpr (EXTRA) acc[e][NQ - 1] += ld[k] * wgt;   // dz
+            const float w = dl_dap * ap;
+            const float wx = w * dx[bx], wy = w * dy[by];
+            acc[e][4] += wx; acc[e][5] += wy;
+            acc[e][6] += wx * dx[bx]; acc[e][7] += wx * dy[by]; acc[e][8] += wy * dy[by];
+            lq[k] += ap * dq;  // gamma_cur2last <- a' color + (1 - a') gamma_cur2last, dotted with dL/dgamma
+            any_e = true;
+          }
+        }
+        if (__any(any_e)) {  // wave-uniform: the entry contributed, the slot is taken
+          je[e] = j;
+          any = true;
+          break;
+        }
+        }  // next reachable entry into the same (still zero) slot
+      }
+      if (any) {  // wave-uniform
+        // quantity order chosen so that the two first moments meet in one quad (lanes 0 and 2):
+        //   lane 0: M1x  2: M1y  4: dalpha  6,8,10: dcolor  12: M2xx  14: M2xy  odd: M2yy
+        float rows[NQ];
+        constexpr int ORDER[10] = {4, 2, 0, 6, 5, 3, 1, 7, 8, 9};   // acc index feeding leaf q0..q8 (EXTRA: q9)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+          rows[q] = rows_of4(acc[0][ORDER[q]], acc[1][ORDER[q]], acc[2][ORDER[q]], acc[3][ORDER[q]]);
+        const float v = (RED & 1) == 0 ? rows_to_lanes9(rows, c16) : rows_to_lanes9_bank(rows, c16);
+        // row r of the wave holds the totals of slot e = {0,2,1,3}[r]
+        const int row = lane >> 4;
+        const int e = ((row & 1) << 1) | (row >> 1);
+        const int j = (e == 0) ? je[0] : (e == 1) ? je[1] : (e == 2) ? je[2] : je[3];
+        // an empty slot (the chunk ran out of entries) holds zeros and no entry: it must not touch memory
+        const bool rowact = j >= 0;
+        const float4 D = sD[j & 63];
+        // B.5.2b / B.5.2c from the moments: du = -cinv (M1x, M1y) needs both first moments -> the partner
+        // comes from the other lane of the pair (quad_perm [2,3,0,1]); dcinv = -(M2xx/2, M2xy, M2yy/2).
+        // The 9 atomics of an entry are ONE instruction on ONE 48-byte gradient record.
+        const float nb = dpp_get<0x4E>(v);
+        const float c_own = (kind == 1) ? -D.x : ((kind == 2) ? -D.z : kscale);
+        float val = v * c_own;
+        if (kind != 0) val = fmaf(nb, -D.y, val);
+        if (rowact && qoff >= 0 && val != 0.f)
+          unsafeAtomicAdd(gpack + 12 * (size_t)__float_as_int(D.w) + qoff, val);
+      }
+    }
+  }
 }
 
 // packed [N][12] gradient records -> the four output tensors of splatB
@@ -541,117 +1027,50 @@ int tile_work_from_contrib(const DrawParams& p, const int32_t* contrib, int32_t*
   return 0;
 }
 
-// policy -> template instance (compile-time footprint / floor / clamp)
-int launch_draw_extra(const DrawParams& dp, const EgsPolicy* pol, int32_t* ranges, const int32_t* gsid,
-                      const float4* rec, float* image, int32_t* contrib, float* final_tau, const DrawExtras& ex,
-                      hipStream_t s) {
-#define EGS_DRAWX(BOX, FLOOR, CLAMP)                                                                               \
-  do {                                                                                                             \
-    if (pol->alpha_skip > 0.f)                                                                                     \
-      EGS_LAUNCH_LDS("k_draw_extra", (k_draw_extra<BOX, FLOOR, CLAMP, true>), dim3(draw_grid(dp)), dim3(64),       \
-                     draw_lds_pad(0), s, dp, ranges, gsid, rec, image, contrib, final_tau, ex);                   \
-    else                                                                                                           \
-      EGS_LAUNCH_LDS("k_draw_extra", (k_draw_extra<BOX, FLOOR, CLAMP, false>), dim3(draw_grid(dp)), dim3(64),      \
-                     draw_lds_pad(0), s, dp, ranges, gsid, rec, image, contrib, final_tau, ex);                   \
-  } while (0)
-  const int sel = (pol->footprint == 1 ? 4 : 0) | (pol->maha_floor ? 2 : 0) | (pol->alpha_clamp ? 1 : 0);
-  switch (sel) {
-    case 0: EGS_DRAWX(false, false, false); break;
-    case 1: EGS_DRAWX(false, false, true); break;
-    case 2: EGS_DRAWX(false, true, false); break;
-    case 3: EGS_DRAWX(false, true, true); break;
-    case 4: EGS_DRAWX(true, false, false); break;
-    case 5: EGS_DRAWX(true, false, true); break;
-    case 6: EGS_DRAWX(true, true, false); break;
-    default: EGS_DRAWX(true, true, true); break;
-  }
-#undef EGS_DRAWX
-  EGS_LAUNCH_OK();
-  return 0;
-}
-
+// policy -> template arguments (compile-time footprint / floor / clamp / skip) and flavour, forward draw
+// ex (nullable): the render extras
 int launch_draw(const DrawParams& dp, const EgsPolicy* pol, int32_t* ranges, const int32_t* gsid, const float4* rec,
-                float* image, int32_t* contrib, float* final_tau, hipStream_t s) {
-#define EGS_DRAW(BOX, FLOOR, CLAMP)                                                                                \
-  do {                                                                                                             \
-    if (pol->alpha_skip > 0.f)                                                                                     \
-      EGS_LAUNCH_LDS("k_draw", (k_draw<BOX, FLOOR, CLAMP, true>), dim3(draw_grid(dp)), dim3(64), draw_lds_pad(0), s, \
-                     dp, ranges, gsid, rec, image, contrib, final_tau);                                            \
-    else                                                                                                           \
-      EGS_LAUNCH_LDS("k_draw", (k_draw<BOX, FLOOR, CLAMP, false>), dim3(draw_grid(dp)), dim3(64), draw_lds_pad(0), s, \
-                     dp, ranges, gsid, rec, image, contrib, final_tau);                                            \
-  } while (0)
-  const int sel = (pol->footprint == 1 ? 4 : 0) | (pol->maha_floor ? 2 : 0) | (pol->alpha_clamp ? 1 : 0);
-  switch (sel) {
-    case 0: EGS_DRAW(false, false, false); break;
-    case 1: EGS_DRAW(false, false, true); break;
-    case 2: EGS_DRAW(false, true, false); break;
-    case 3: EGS_DRAW(false, true, true); break;
-    case 4: EGS_DRAW(true, false, false); break;
-    case 5: EGS_DRAW(true, false, true); break;
-    case 6: EGS_DRAW(true, true, false); break;
-    default: EGS_DRAW(true, true, true); break;
-  }
-#undef EGS_DRAW
+                float* image, int32_t* contrib, float* final_tau, const DrawExtras* ex, hipStream_t s) {
+  decltype(&k_draw<false, false, false, false, false>) kern = nullptr;
+  with_bools(
+      [&](auto box, auto flr, auto clamp, auto skip, auto extra) {
+        kern = k_draw<box.value, flr.value, clamp.value, skip.value, extra.value>;
+      },
+      pol->footprint == 1, pol->maha_floor != 0, pol->alpha_clamp != 0, pol->alpha_skip > 0.f, ex != nullptr);
+  EGS_LAUNCH_LDS(ex ? "k_draw_extra" : "k_draw", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(0), s, dp, ranges, gsid,
+                 rec, image, contrib, final_tau, ex ? *ex : DrawExtras{});
   EGS_LAUNCH_OK();
   return 0;
 }
 
+// ... backward draw.  ex (nullable): the render extras -- that flavour exists in the default reduction variant only
+// (EGS_DRAWB_RED is an A/B knob of the plain kernel)
 int launch_draw_bwd(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                     const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg, float* gpack,
-                    hipStream_t s) {
+                    const DrawExtras* ex, hipStream_t s) {
   // variants of the backward kernel (bit 0: in-row merges of the wave reduction with bank-masked DPP adds instead
   // of selects; bit 1: accumulator zeros loaded from LDS instead of moved; bit 2: exponent per evaluated block);
   // EGS_DRAWB_RED = 0 | 3 | 7 overrides
   static const int red = [] { const char* e = getenv("EGS_DRAWB_RED"); return e ? atoi(e) : EGS_DRAWB_RED_DEFAULT; }();
-  const SegArgs nosg = {};
-#define EGS_DRAWB(BOX, FLOOR, CLAMP)                                                                               \
-  do {                                                                                                             \
-    if (red == 0)                                                                                                  \
-      EGS_LAUNCH_LDS("k_draw_bwd", (k_draw_bwd<BOX, FLOOR, CLAMP, 0>), dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), \
-                     s, dp, ranges, gsid, rec, final_tau, contrib, dLdg, gpack, nosg);                             \
-    else if (red == 3)                                                                                             \
-      EGS_LAUNCH_LDS("k_draw_bwd", (k_draw_bwd<BOX, FLOOR, CLAMP, 3>), dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), \
-                     s, dp, ranges, gsid, rec, final_tau, contrib, dLdg, gpack, nosg);                             \
-    else                                                                                                           \
-      EGS_LAUNCH_LDS("k_draw_bwd", (k_draw_bwd<BOX, FLOOR, CLAMP, 7>), dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), \
-                     s, dp, ranges, gsid, rec, final_tau, contrib, dLdg, gpack, nosg);                             \
-  } while (0)
-  const int sel = (pol->footprint == 1 ? 4 : 0) | (pol->maha_floor ? 2 : 0) | (pol->alpha_clamp ? 1 : 0);
-  switch (sel) {
-    case 0: EGS_DRAWB(false, false, false); break;
-    case 1: EGS_DRAWB(false, false, true); break;
-    case 2: EGS_DRAWB(false, true, false); break;
-    case 3: EGS_DRAWB(false, true, true); break;
-    case 4: EGS_DRAWB(true, false, false); break;
-    case 5: EGS_DRAWB(true, false, true); break;
-    case 6: EGS_DRAWB(true, true, false); break;
-    default: EGS_DRAWB(true, true, true); break;
+  const bool box = pol->footprint == 1, flr = pol->maha_floor != 0, clamp = pol->alpha_clamp != 0;
+  if (ex) {   // the flavour's own kernel argument: two pointer types
+    decltype(&k_draw_bwd<false, false, false, EGS_DRAWB_RED_DEFAULT, false, true>) kern = nullptr;
+    with_bools([&](auto b, auto f, auto c) { kern = k_draw_bwd<b.value, f.value, c.value, EGS_DRAWB_RED_DEFAULT, false, true>; },
+               box, flr, clamp);
+    EGS_LAUNCH_LDS("k_draw_bwd_extra", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), s, dp, ranges, gsid, rec,
+                   final_tau, contrib, dLdg, gpack, DrawBwdFlavour<true>{*ex});
+  } else {
+    decltype(&k_draw_bwd<false, false, false, 0, false, false>) kern = nullptr;
+    with_bools(
+        [&](auto b, auto f, auto c) {
+          kern = red == 0   ? k_draw_bwd<b.value, f.value, c.value, 0, false, false>
+                 : red == 3 ? k_draw_bwd<b.value, f.value, c.value, 3, false, false>
+                            : k_draw_bwd<b.value, f.value, c.value, 7, false, false>;
+        },
+        box, flr, clamp);
+    EGS_LAUNCH_LDS("k_draw_bwd", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), s, dp, ranges, gsid, rec, final_tau,
+                   contrib, dLdg, gpack, DrawBwdFlavour<false>{});
   }
-#undef EGS_DRAWB
-  EGS_LAUNCH_OK();
-  return 0;
-}
-
-// (the EXTRA flavour exists in the default reduction variant only: EGS_DRAWB_RED is an A/B knob of the plain kernel)
-int launch_draw_bwd_extra(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
-                          const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg,
-                          float* gpack, const DrawExtras& ex, hipStream_t s) {
-#define EGS_DRAWBX(BOX, FLOOR, CLAMP)                                                                              \
-  EGS_LAUNCH_LDS("k_draw_bwd_extra", (k_draw_bwd_extra<BOX, FLOOR, CLAMP, EGS_DRAWB_RED_DEFAULT>), dim3(draw_grid(dp)), \
-                 dim3(64), draw_lds_pad(1), s, dp, ranges, gsid, rec, final_tau, contrib, dLdg, gpack, ex)
-  const int sel = (pol->footprint == 1 ? 4 : 0) | (pol->maha_floor ? 2 : 0) | (pol->alpha_clamp ? 1 : 0);
-  switch (sel) {
-    case 0: EGS_DRAWBX(false, false, false); break;
-    case 1: EGS_DRAWBX(false, false, true); break;
-    case 2: EGS_DRAWBX(false, true, false); break;
-    case 3: EGS_DRAWBX(false, true, true); break;
-    case 4: EGS_DRAWBX(true, false, false); break;
-    case 5: EGS_DRAWBX(true, false, true); break;
-    case 6: EGS_DRAWBX(true, true, false); break;
-    default: EGS_DRAWBX(true, true, true); break;
-  }
-#undef EGS_DRAWBX
   EGS_LAUNCH_OK();
   return 0;
 }
@@ -659,16 +1078,11 @@ int launch_draw_bwd_extra(const DrawParams& dp, const EgsPolicy* pol, const int3
 int launch_draw_bwd_seg(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                         const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg,
                         float* gpack, const SegArgs& sga, int grid, hipStream_t s) {
-#define EGS_DRAWBS(FLOOR, CLAMP)                                                                                   \
-  EGS_LAUNCH("k_draw_bwd_seg", (k_draw_bwd<false, FLOOR, CLAMP, 7, true>), dim3(grid), dim3(64), s, dp, ranges, gsid, \
-             rec, final_tau, contrib, dLdg, gpack, sga)
-  switch ((pol->maha_floor ? 2 : 0) | (pol->alpha_clamp ? 1 : 0)) {
-    case 0: EGS_DRAWBS(false, false); break;
-    case 1: EGS_DRAWBS(false, true); break;
-    case 2: EGS_DRAWBS(true, false); break;
-    default: EGS_DRAWBS(true, true); break;
-  }
-#undef EGS_DRAWBS
+  decltype(&k_draw_bwd<false, false, false, 7, true, false>) kern = nullptr;
+  with_bools([&](auto flr, auto clamp) { kern = k_draw_bwd<false, flr.value, clamp.value, 7, true, false>; },
+             pol->maha_floor != 0, pol->alpha_clamp != 0);
+  EGS_LAUNCH("k_draw_bwd_seg", kern, dim3(grid), dim3(64), s, dp, ranges, gsid, rec, final_tau, contrib, dLdg, gpack,
+             DrawBwdFlavour<false>{sga});
   EGS_LAUNCH_OK();
   return 0;
 }

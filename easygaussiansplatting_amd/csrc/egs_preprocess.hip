@@ -24,19 +24,23 @@ namespace egs {
 // (of 16-B units for K % 4 == 0): conflict-free -- and the span leaves as coalesced dwordx4 stores, full lines.
 // EVERY row is written, culled Gaussians as zeros: the callers allocate with torch.empty, not torch.zeros (the
 // reference's zero-filled outputs, gausplat.cu:170-178 etc., cost 528 B per Gaussian and step of pure fill here).
+// (the same layout serves the staged row LOADS of the fused kernels, stage_rows_in / stage_rows_out below)
 template <int K>
-struct RowsOut {
+struct RowStage {
   static constexpr bool V4 = (K % 4 == 0);
+  static constexpr int Q = K / 4;                                      // float4 per row (V4)
+  static constexpr int STRIDE = V4 ? 4 * ((Q + 1) | 1) : (K | 1);      // floats
+  static constexpr int LDS_FLOATS = 256 * STRIDE;
+  // rows_out only: rows of one or two floats leave directly and need no LDS
   static constexpr bool DIRECT = (K <= 2);
-  static constexpr int STRIDE = V4 ? 4 * ((K / 4 + 1) | 1) : (K | 1);   // floats
-  static constexpr int LDS_FLOATS = DIRECT ? 1 : 256 * STRIDE;
+  static constexpr int OUT_LDS_FLOATS = DIRECT ? 1 : LDS_FLOATS;
 };
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 // all 256 threads of the workgroup call this (barriers inside); `row` of lanes past n is ignored
 template <int K>
 __device__ __forceinline__ void rows_out(const float* row, float* __restrict__ dst, int n, int base, float* lds) {
-  using RO = RowsOut<K>;
+  using RO = RowStage<K>;
   const int tid = threadIdx.x;
   const int rows = min(256, n - base);
   if constexpr (RO::DIRECT) {
@@ -126,7 +130,7 @@ __global__ __launch_bounds__(256) void k_cov3d(int n, const float* __restrict__ 
                                                float* __restrict__ cov3ds,
                                                float* __restrict__ dcov3d_drots,
                                                float* __restrict__ dcov3d_dscales) {
-  __shared__ float stage[RowsOut<24>::LDS_FLOATS];
+  __shared__ float stage[RowStage<24>::OUT_LDS_FLOATS];
   const int base = blockIdx.x * 256, i = base + threadIdx.x;
   const bool jac = dcov3d_drots && dcov3d_dscales;
   float c6[6], dq[24], ds[18];
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(256) void k_cov2d(int n, const float* __restrict__ 
                                                float* __restrict__ cov2ds,
                                                float* __restrict__ dcov2d_dcov3ds,
                                                float* __restrict__ dcov2d_dpcs) {
-  __shared__ float stage[RowsOut<18>::LDS_FLOATS];
+  __shared__ float stage[RowStage<18>::OUT_LDS_FLOATS];
   const int base = blockIdx.x * 256, i = base + threadIdx.x;
   const bool jac = dcov2d_dcov3ds && dcov2d_dpcs;
   float c3[3] = {0.f, 0.f, 0.f}, J3[18], Jp[9];
@@ -207,7 +211,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EGS_SH2COLO
                                                   float* __restrict__ colors,
                                                   float* __restrict__ dcolor_dshs,
                                                   float* __restrict__ dcolor_dpws) {
-  __shared__ float stage[cmax(RowsOut<NC>::LDS_FLOATS, RowsOut<9>::LDS_FLOATS)];
+  __shared__ float stage[cmax(RowStage<NC>::OUT_LDS_FLOATS, RowStage<9>::OUT_LDS_FLOATS)];
   const int base = blockIdx.x * 256, i = base + threadIdx.x;
   constexpr int K = 3 * NC;
   const bool jac = dcolor_dshs && dcolor_dpws;
@@ -267,7 +271,7 @@ __global__ __launch_bounds__(256) void k_inv_cov2d(int n, const float* __restric
                                                    float* __restrict__ cinv2ds,
                                                    int32_t* __restrict__ areas,
                                                    float* __restrict__ dcinv2d_dcov2ds) {
-  __shared__ float stage[RowsOut<9>::LDS_FLOATS];
+  __shared__ float stage[RowStage<9>::OUT_LDS_FLOATS];
   const int base = blockIdx.x * 256, i = base + threadIdx.x;
   float ci[3] = {0.f, 0.f, 0.f}, ar[2] = {0.f, 0.f}, J[9];
 #pragma unroll
@@ -328,7 +332,7 @@ __global__ __launch_bounds__(256) void k_chain_rule(
     float* __restrict__ dL_dpw, float* __restrict__ dL_dsh, float* __restrict__ dL_dscale,
     float* __restrict__ dL_drot) {
   constexpr int K = 3 * NC;
-  __shared__ float stage[cmax(RowsOut<K>::LDS_FLOATS, RowsOut<3>::LDS_FLOATS)];
+  __shared__ float stage[cmax(RowStage<K>::OUT_LDS_FLOATS, RowStage<3>::OUT_LDS_FLOATS)];
   const int base = blockIdx.x * 256, i = base + threadIdx.x;
   float grot[4] = {0.f, 0.f, 0.f, 0.f}, gsc[3] = {0.f, 0.f, 0.f}, gpw[3] = {0.f, 0.f, 0.f}, gsh[K];
 #pragma unroll
@@ -417,15 +421,7 @@ __device__ __forceinline__ float4 act_rot(const float4& r, float& norm) {       
 // lanes are 4K bytes apart (64 different cache lines per instruction).  Staged instead: the
 // workgroup's 256 rows are one contiguous span, fetched with fully coalesced dwordx4 loads into LDS,
 // then every lane reads its row from LDS (row stride padded to an odd number of 16-B units:
-// conflict-free ds_read_b128).  Same for the dL/dsh rows on the way out.
-template <int K>
-struct RowStage {
-  static constexpr bool V4 = (K % 4 == 0);
-  static constexpr int Q = K / 4;                                      // float4 per row (V4)
-  static constexpr int STRIDE = V4 ? 4 * ((Q + 1) | 1) : (K | 1);      // floats
-  static constexpr int LDS_FLOATS = 256 * STRIDE;
-};
-
+// conflict-free ds_read_b128: RowStage above).  Same for the dL/dsh rows on the way out.
 template <int K>
 __device__ __forceinline__ void stage_rows_in(const float* __restrict__ src, int n, int base, float* lds, float* row) {
   using RS = RowStage<K>;
@@ -569,10 +565,11 @@ __device__ __forceinline__ void stage_span_out(const float* row, float* __restri
 #ifndef EGS_PRE_EARLY_LOADS
 #define EGS_PRE_EARLY_LOADS 0
 #endif
-template <int NC, bool RAW, bool JW>
 #ifndef EGS_PRE_JW_WAVES       // A/B knob: minimum waves per SIMD of the JW instances (register cap 512 / waves)
 #define EGS_PRE_JW_WAVES 1
 #endif
+// AA (anti-aliased rendering): every Gaussian is binned and drawn with opacity alpha comp
+template <int NC, bool RAW, bool JW, bool AA>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (JW ? EGS_PRE_JW_WAVES : 8), 8))) void k_preprocess_fwd(int n, PreParams pp, const float* __restrict__ pws,
                                                         const float* __restrict__ rots,
                                                         const float* __restrict__ scales,
@@ -589,29 +586,137 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
                                                         float4* __restrict__ rec, BinParams bp, BinCountOut bo,
                                                         uint8_t* __restrict__ visible,
                                                         float* __restrict__ dcolor_dpws) {
-  constexpr bool AA = false;
-#include "egs_preprocess_fwd.inc"
-}
-// the AA flavour (anti-aliased rendering): every Gaussian is binned and drawn with opacity alpha comp
-template <int NC, bool RAW, bool JW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (JW ? EGS_PRE_JW_WAVES : 8), 8))) void k_preprocess_fwd_aa(int n, PreParams pp, const float* __restrict__ pws,
-                                                        const float* __restrict__ rots,
-                                                        const float* __restrict__ scales,
-                                                        const float* __restrict__ shs,
-                                                        const float* __restrict__ shs_high,
-                                                        const float* __restrict__ alphas,
-                                                        const float* __restrict__ Rcw,
-                                                        const float* __restrict__ tcw,
-                                                        const float* __restrict__ twc,
-                                                        float* __restrict__ us, float* __restrict__ depths,
-                                                        float* __restrict__ cinv2ds,
-                                                        float* __restrict__ colors,
-                                                        int32_t* __restrict__ areas,
-                                                        float4* __restrict__ rec, BinParams bp, BinCountOut bo,
-                                                        uint8_t* __restrict__ visible,
-                                                        float* __restrict__ dcolor_dpws) {
-  constexpr bool AA = true;
-#include "egs_preprocess_fwd.inc"
+  // dcolor_dpws (nullable, [N][9]): dcolor/dpw of every Gaussian, for the backward pass -- the ONLY thing that pass
+  // needs the SH coefficients for (eq (7): dL/dpw += dL/dcolor . dcolor/dpw; dL/dsh needs the basis alone).  36 B
+  // written here save the 4K-byte SH row re-read there (192 B at SH degree 3).
+  constexpr int K = 3 * NC;
+  constexpr int KH = K - 3;   // width of high_shs
+  constexpr int STAGE_FLOATS = (RAW && KH > 0 && RowStage<KH>::LDS_FLOATS > RowStage<12>::LDS_FLOATS)
+                                   ? RowStage<KH>::LDS_FLOATS : RowStage<12>::LDS_FLOATS;
+  __shared__ float stage[STAGE_FLOATS];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (bo.cr)     // the superblock sums of the depth sort that follows must start from zero
+    for (uint32_t z = (uint32_t)i; z < bo.sort_sup_words; z += gridDim.x * 256u) bo.sort_sup[z] = 0u;
+  uint32_t dkey = 0u;
+  float sh[K];
+  if constexpr (RAW) {   // 180-B high_shs rows cannot be dwordx4-loaded per lane: the workgroup's span through LDS
+    if constexpr (KH > 0) {
+      if constexpr (KH % 2 == 1) stage_span_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
+      else stage_rows_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
+    }
+  }
+  float4 r[3] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+  float jw[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  uint4 crec = make_uint4(0u, 0u, 0u, 0u);
+  if (i < n) {
+    const f3 pw = ld3(pws + 3 * (size_t)i);
+#if EGS_PRE_EARLY_LOADS
+    // (requested with the position, not after the colour: one dependent round trip less per row)
+    float4 q_in = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
+    f3 sc_in = ld3(scales + 3 * (size_t)i);
+    const float alpha_in = (rec || bo.br) ? alphas[i] : 0.f;
+#endif
+    float col[3];
+    {  // colour has no depth test in the reference (kernel.cu:619-725)
+      if constexpr (RAW) {
+        sh[0] = shs[3 * (size_t)i]; sh[1] = shs[3 * (size_t)i + 1]; sh[2] = shs[3 * (size_t)i + 2];
+      } else {  // direct dwordx4 row loads: staging them through LDS measured 10 % slower here
+        load_sh_row<K>(shs + (size_t)K * i, sh);
+      }
+      const ShDir<NC> d = sh_basis_f<NC>(pw, twc);
+#if EGS_SH_FUSED_JAC_PRE
+      if constexpr (JW) sh_color_and_jac_dpw<NC>(d, sh, col, jw);
+      else sh_color_f<NC>(d, sh, col);
+      if (colors) st3(colors + 3 * (size_t)i, {col[0], col[1], col[2]});
+#else
+      sh_color_f<NC>(d, sh, col);
+      if (colors) st3(colors + 3 * (size_t)i, {col[0], col[1], col[2]});
+      if constexpr (JW) sh_jac_dpw<NC>(d, sh, jw);
+#endif
+    }
+    const Proj P = project_f(pw, Rcw, tcw, pp.fx, pp.fy, pp.cx, pp.cy);
+    float u0 = 0.f, u1 = 0.f, depth = EGS_BAD_MARKER, ci[3] = {0.f, 0.f, 0.f};
+    int rx = 0, ry = 0;
+    float aa_comp = 0.f;   // (AA: the opacity compensation; 0 for near-culled Gaussians)
+    if (!(pp.near_cull && P.pc.z < EGS_MIN_DEPTH)) {
+      u0 = P.u0; u1 = P.u1; depth = P.pc.z;
+#if EGS_PRE_EARLY_LOADS
+      float4 q = q_in;
+      f3 sc = sc_in;
+#else
+      float4 q = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
+      f3 sc = ld3(scales + 3 * (size_t)i);
+#endif
+      if constexpr (RAW) { float nrm; q = act_rot(q, nrm); sc = act_scale(sc); }
+      const Cov3 c3 = cov3d_f(q, sc);
+      const Cov2 c2 = cov2d_f(c3.c, P.pc, Rcw, pp.fx, pp.fy, pp.limx, pp.limy, pp.clamp_fov);
+      const float det_inv = inv_cov2d_f(c2.c, pp.det_eps, ci);
+      if constexpr (AA) aa_comp = aa_comp_f(c2.c);
+      if (pp.nan_cull && isnan(det_inv)) {
+        depth = EGS_BAD_MARKER; ci[0] = 0.f; ci[1] = 0.f; ci[2] = 0.f;
+      } else {
+        radius_f(c2.c, pp.radius_mode, rx, ry);
+      }
+    }
+#if EGS_PRE_EARLY_LOADS
+    float alpha_act = (rec || bo.br) ? (RAW ? act_alpha(alpha_in) : alpha_in) : 0.f;
+#else
+    float alpha_act = (rec || bo.br) ? (RAW ? act_alpha(alphas[i]) : alphas[i]) : 0.f;
+#endif
+    // AA: the Gaussian is binned and drawn with the compensated opacity alpha comp (the records carry it)
+    if constexpr (AA) alpha_act *= aa_comp;
+    if (bo.br) {  // getRects + depth key of the binning stage, straight from registers (no k_bin_count pass)
+      uint4 rect;
+      bool cull;
+      const uint32_t cnt = bin_count_one(bp, u0, u1, (float)rx, (float)ry, depth, rect, dkey, cull);
+      if (cull) { depth = EGS_BAD_MARKER; rx = 0; ry = 0; }  // in-place contract of splat (kernel.cu:114-119)
+      bo.ids[i] = (uint32_t)i;
+      // the footprint record of the binning stage and the number of tiles the Gaussian is emitted for: its rect
+      // (the reference's lists) or, bp.cull_lists, the tiles its footprint alpha' >= alpha_skip can reach
+      const BinRec brec = make_binrec(u0, u1, ci[0], ci[1], ci[2], alpha_act, pp.alpha_skip, bp.cull_lists != 0,
+                                      rect, cnt);
+      if (cnt) {
+        const uint32_t w = brec.wh & 0xFFFFu, h = brec.wh >> 16;
+        if (w <= 4u && h <= 4u) {          // the blocks the footprint reaches, as a bitmap: emission is bit arithmetic
+          const unsigned long long bits = foot_bitmap(brec);
+          crec = make_uint4(brec.xy, brec.wh, (uint32_t)bits, (uint32_t)(bits >> 32));
+        } else {                           // a bigger rect
+          const bool walk = brec.m < __int_as_float(0x7f800000);
+          if (walk && w <= 8u && h <= 8u) {   // its TILES as a bitmap; k_bin_emit evaluates the slabs of one tile
+            const unsigned long long bits = foot_tilemap(brec);
+            crec = make_uint4(brec.xy, brec.wh | EGS_CR_TILEMAP, (uint32_t)bits, (uint32_t)(bits >> 32));
+          } else {                            // counted here, walked row by row by k_bin_emit
+            crec = make_uint4(brec.xy, brec.wh | EGS_CR_BIG, walk ? foot_count(brec) : cnt, walk ? 1u : 0u);
+          }
+          if (walk) {
+            float4* o = reinterpret_cast<float4*>(bo.br + i);
+            o[0] = make_float4(brec.ux, brec.uy, brec.A, brec.Bh);
+            o[1] = make_float4(brec.C, brec.m, __uint_as_float(brec.xy), __uint_as_float(brec.wh));
+          }
+        }
+      }
+      bo.dkeys[i] = dkey;
+    }
+    // us / cinv2ds / colors / areas are only needed by callers that go on with the seven-op surface; the
+    // fused path draws from the packed records alone and passes NULL (40 B/Gaussian less to write)
+    if (us) { us[2 * (size_t)i] = u0; us[2 * (size_t)i + 1] = u1; }
+    depths[i] = depth;
+    if (visible) visible[i] = depth > 0.2f;  // the mask GSFunction returns (gsmodel.py:50)
+    if (cinv2ds) st3(cinv2ds + 3 * (size_t)i, {ci[0], ci[1], ci[2]});
+    if (areas) { areas[2 * (size_t)i] = rx; areas[2 * (size_t)i + 1] = ry; }
+    // the packed 2D record of the draw kernels, straight from registers (no k_pack_records pass)
+    if (rec)
+      make_record(u0, u1, ci[0], ci[1], ci[2], alpha_act, col[0], col[1], col[2], rx, ry,
+                  pp.W, pp.H, pp.footprint, pp.alpha_skip, r);
+  }
+  if (bo.br) {
+    __syncthreads();   // (RAW: every wave is done with the rows staged in)
+    block_max_key(dkey, bo.maxkey, reinterpret_cast<uint32_t*>(stage));
+    if (i < n) bo.cr[i] = crec;     // (16 B per lane, consecutive lanes: full lines)
+  }
+  // 48-B records leave as full lines (lane-strided 16-B pieces cost 3x the write requests)
+  if (rec) stage_rows_out<12>(reinterpret_cast<const float*>(r), reinterpret_cast<float*>(rec), n, blockIdx.x * 256, stage);
+  if constexpr (JW) rows_out<9>(jw, dcolor_dpws, n, blockIdx.x * 256, stage);
 }
 
 // backward.md eq (3)(4)(5)(7) == gsmodel.py:71-85 with every Jacobian re-derived in
@@ -619,7 +724,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
 // written by k_draw_bwd: {dalpha, dcolor[3], du[2], dcinv[3], pad[3]}.
 // RAW: parameters as in k_preprocess_fwd<.., true>; gradients come out with respect to the raw tensors
 // (dL_dsh = low_shs [N,3], dL_dsh_high = high_shs [N,K-3]); alphas = alphas_raw (only read when RAW)
-template <int NC, bool RAW, bool JW>
+// EXTRA (render extras): gpack[i][9] holds dL/dz of the Gaussian's camera-space depth
+// POSE (camera pose gradient): every other output as without it, plus one partial row {dL/dRcw [9],
+// dL/dtcw [3], dL/dtwc [3], 0} per workgroup in pose_ws (read by the POSE instances only), summed by k_pose_reduce
+// AA (anti-aliased rendering): the records were drawn with opacity alpha comp; reads alphas[i] also
+// without RAW (4 B per Gaussian)
+template <int NC, bool RAW, bool JW, bool EXTRA, bool POSE, bool AA>
 __global__ __launch_bounds__(256) void k_preprocess_bwd(
     int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
     const float* __restrict__ scales, const float* __restrict__ shs, const float* __restrict__ shs_high,
@@ -627,55 +737,212 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     const float* __restrict__ tcw, const float* __restrict__ twc, const float* __restrict__ depths,
     const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
     float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-    float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode) {
-  constexpr bool EXTRA = false, POSE = false, AA = false;
-  float* const pose_ws = nullptr;   // (POSE only)
-#include "egs_preprocess_bwd.inc"
-}
-// the EXTRA flavour (render extras): gpack[i][9] holds dL/dz of the Gaussian's camera-space depth
-template <int NC, bool RAW, bool JW>
-__global__ __launch_bounds__(256) void k_preprocess_bwd_extra(
-    int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
-    const float* __restrict__ scales, const float* __restrict__ shs, const float* __restrict__ shs_high,
-    const float* __restrict__ alphas, const float* __restrict__ Rcw,
-    const float* __restrict__ tcw, const float* __restrict__ twc, const float* __restrict__ depths,
-    const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
-    float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-    float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode) {
-  constexpr bool EXTRA = true, POSE = false, AA = false;
-  float* const pose_ws = nullptr;   // (POSE only)
-#include "egs_preprocess_bwd.inc"
-}
-// the POSE flavour (camera pose gradient, either EXTRA): every output of the plain / extra instance, plus one partial
-// row {dL/dRcw [9], dL/dtcw [3], dL/dtwc [3], 0} per workgroup in pose_ws, summed by k_pose_reduce
-template <int NC, bool RAW, bool JW, bool EXTRA>
-__global__ __launch_bounds__(256) void k_preprocess_bwd_pose(
-    int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
-    const float* __restrict__ scales, const float* __restrict__ shs, const float* __restrict__ shs_high,
-    const float* __restrict__ alphas, const float* __restrict__ Rcw,
-    const float* __restrict__ tcw, const float* __restrict__ twc, const float* __restrict__ depths,
-    const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
-    float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
     float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode, float* __restrict__ pose_ws) {
-  constexpr bool POSE = true, AA = false;
-#include "egs_preprocess_bwd.inc"
-}
-// the AA flavour of all three (anti-aliased rendering): the records were drawn with opacity alpha comp;
-// reads alphas[i] also without RAW (4 B per Gaussian).  pose_ws: POSE only
-template <int NC, bool RAW, bool JW, bool EXTRA, bool POSE>
-__global__ __launch_bounds__(256) void k_preprocess_bwd_aa(
-    int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
-    const float* __restrict__ scales, const float* __restrict__ shs, const float* __restrict__ shs_high,
-    const float* __restrict__ alphas, const float* __restrict__ Rcw,
-    const float* __restrict__ tcw, const float* __restrict__ twc, const float* __restrict__ depths,
-    const float4* __restrict__ gpack, float* __restrict__ dL_dpw, float* __restrict__ dL_dsh,
-    float* __restrict__ dL_dsh_high, float* __restrict__ dL_dalpha, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-    float* __restrict__ dL_du, const float* __restrict__ dcolor_dpws, int mode, float* __restrict__ pose_ws) {
-  constexpr bool AA = true;
-#include "egs_preprocess_bwd.inc"
+  // AA (anti-aliased rendering): the forward drew opacity alpha comp, so ga.x = dL/d(alpha comp):
+  // dL/dalpha = ga.x comp and dL/dcov2d gains ga.x alpha dcomp/dcov2d before it feeds J3, Jp and the pose W term
+  // dcolor_dpws (nullable): [N][9] left by k_preprocess_fwd; with it this kernel never reads the SH coefficients
+  // mode bit 1 (EGS_BWD_FACTORED_SH): the SH gradient stays in its factored form -- eq (5) is an outer product
+  // dL/dcolour (x) basis, so dL_dsh receives the THREE floats dL/dcolour per Gaussian ([N][3], always written, never
+  // accumulated) and the rows are formed once per step, for all views, by k_sh_grad_views; dL_dsh_high is not touched
+  const int accum = mode & 1;
+  const bool factored = (mode & 2) != 0;
+  // accum: the five (six) parameter-gradient outputs already hold the gradients of EARLIER views of the step and this
+  // view's are ADDED to them (dL_du is per view and always written): a rank that renders V views per step then needs
+  // no separate accumulation kernels (torch's `.grad += new`: 976 B per Gaussian and view against 488 here)
+  constexpr int K = 3 * NC;
+  constexpr int KH = K - 3;
+  constexpr int KS = RAW ? (KH > 0 ? KH : 1) : K;   // width of the rows that go through LDS
+  __shared__ float stage[RowStage<KS>::LDS_FLOATS];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  float sh[JW ? 1 : K], gsh[K];
+  if constexpr (!JW) {
+    if constexpr (RAW) {
+      if constexpr (KH > 0) {
+        if constexpr (KH % 2 == 1) stage_span_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
+        else stage_rows_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
+      }
+      if (i < n) { sh[0] = shs[3 * (size_t)i]; sh[1] = shs[3 * (size_t)i + 1]; sh[2] = shs[3 * (size_t)i + 2]; }
+    } else {
+      if (pp.stage_in) stage_rows_in<K>(shs, n, blockIdx.x * 256, stage, sh);
+      else if (i < n) load_sh_row<K>(shs + (size_t)K * i, sh);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) gsh[k] = 0.f;
+  f3 gcol_out = {0.f, 0.f, 0.f};
+  // POSE: this lane's share of the camera gradient, {dL/dRcw [3][3], dL/dtcw [3], dL/dtwc [3]}
+  float pg[POSE ? 15 : 1];
+  if constexpr (POSE) {
+#pragma unroll
+    for (int k = 0; k < 15; ++k) pg[k] = 0.f;
+  }
+  if (i < n) {
+    // Every input of the row is requested here, before anything is used: with the parameter loads behind the depth
+    // test, the Jacobian row at its use and the old gradients (accum) at theirs, a row went through four dependent
+    // round trips to memory (the ISA had a full wait after each group).
+    const float4 ga = gpack[3 * (size_t)i], gb = gpack[3 * (size_t)i + 1], gc = gpack[3 * (size_t)i + 2];
+    const float depth_i = depths[i];
+    const f3 pw = ld3(pws + 3 * (size_t)i);
+    float4 q = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
+    f3 s = ld3(scales + 3 * (size_t)i);
+    float W[9];
+    if constexpr (JW) load_row<9>(dcolor_dpws + 9 * (size_t)i, W);
+    float al_raw = 0.f;   // (AA without RAW: the activated alpha)
+    if constexpr (RAW || AA) al_raw = alphas[i];
+    float4 o_rot = make_float4(0.f, 0.f, 0.f, 0.f);
+    f3 o_scale = {0.f, 0.f, 0.f}, o_pw = {0.f, 0.f, 0.f};
+    float o_alpha = 0.f;
+    if (accum) {
+      o_rot = *reinterpret_cast<const float4*>(dL_drot + 4 * (size_t)i);
+      o_scale = ld3(dL_dscale + 3 * (size_t)i);
+      o_pw = ld3(dL_dpw + 3 * (size_t)i);
+      o_alpha = dL_dalpha[i];
+    }
+    const f3 gcol = {ga.y, ga.z, ga.w};
+    const float gu0 = gb.x, gu1 = gb.y;
+    const f3 gci = {gb.z, gb.w, gc.x};
+    if constexpr (AA) {
+      // (stored below, once comp is known; culled: comp = 0)
+    } else if constexpr (RAW) {
+      const float al = act_alpha(al_raw);
+      dL_dalpha[i] = ga.x * al * (1.f - al) + o_alpha;   // sigmoid'
+    } else {
+      dL_dalpha[i] = ga.x + o_alpha;
+    }
+    dL_du[2 * (size_t)i] = gu0; dL_du[2 * (size_t)i + 1] = gu1;
+    if (pp.near_cull && depth_i < EGS_MIN_DEPTH) {  // culled: never drawn, all gradients are zero
+      if constexpr (AA) dL_dalpha[i] = o_alpha;
+      if (!accum) {
+        st3(dL_dpw + 3 * (size_t)i, {0.f, 0.f, 0.f});
+        st3(dL_dscale + 3 * (size_t)i, {0.f, 0.f, 0.f});
+        st4(dL_drot + 4 * (size_t)i, {0.f, 0.f, 0.f, 0.f});
+      }
+    } else {
+      float qnorm = 1.f;
+      if constexpr (RAW) { q = act_rot(q, qnorm); s = act_scale(s); }
+      const Proj P = project_f(pw, Rcw, tcw, pp.fx, pp.fy, pp.cx, pp.cy);
+      const Cov3 c3 = cov3d_f(q, s);
+      const Cov2 c2 = cov2d_f(c3.c, P.pc, Rcw, pp.fx, pp.fy, pp.limx, pp.limy, pp.clamp_fov);
+      float ci[3];
+      const float det_inv = inv_cov2d_f(c2.c, pp.det_eps, ci);
+      float Ji[9];
+      inv_cov2d_jac(c2.c, det_inv, Ji);
+      // dL/dcov2d = dL/dcinv2d @ J  (row vector times 3x3)
+      float g2[3] = {gci.x * Ji[0] + gci.y * Ji[3] + gci.z * Ji[6],
+                     gci.x * Ji[1] + gci.y * Ji[4] + gci.z * Ji[7],
+                     gci.x * Ji[2] + gci.y * Ji[5] + gci.z * Ji[8]};
+      if constexpr (AA) {
+        const float al = RAW ? act_alpha(al_raw) : al_raw;
+        const float comp = aa_comp_vjp(c2.c, ga.x * al, g2);   // g2 += ga.x alpha dcomp/dcov2d
+        const float gal = ga.x * comp;
+        dL_dalpha[i] = (RAW ? gal * al * (1.f - al) : gal) + o_alpha;
+      }
+      float J3[18], Jp[9];
+      cov2d_jac(c2, P.pc.z, Rcw, pp.fx, pp.fy, J3, Jp);
+      float g3[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) g3[k] = g2[0] * J3[k] + g2[1] * J3[6 + k] + g2[2] * J3[12 + k];
+      q4 gq; f3 gs;
+      cov3d_vjp(c3, q, s, g3, gq, gs);
+      if constexpr (RAW) {   // through normalize: (g - q (q.g)) / |r|; through exp: g * scale
+        const float qg = q.x * gq.w + q.y * gq.x + q.z * gq.y + q.w * gq.z;
+        gq = {(gq.w - q.x * qg) / qnorm, (gq.x - q.y * qg) / qnorm, (gq.y - q.z * qg) / qnorm,
+              (gq.z - q.w * qg) / qnorm};
+        gs = {gs.x * s.x, gs.y * s.y, gs.z * s.z};
+      }
+      if (accum) {
+        gq = {gq.w + o_rot.x, gq.x + o_rot.y, gq.y + o_rot.z, gq.z + o_rot.w};
+        gs = {gs.x + o_scale.x, gs.y + o_scale.y, gs.z + o_scale.z};
+      }
+      st4(dL_drot + 4 * (size_t)i, gq);      // eq (3)
+      st3(dL_dscale + 3 * (size_t)i, gs);    // eq (4)
+      float j00, j02, j11, j12;
+      project_jac(P, pp.fx, pp.fy, j00, j02, j11, j12);
+      f3 gpc = {gu0 * j00 + g2[0] * Jp[0] + g2[1] * Jp[3] + g2[2] * Jp[6],
+                gu1 * j11 + g2[0] * Jp[1] + g2[1] * Jp[4] + g2[2] * Jp[7],
+                gu0 * j02 + gu1 * j12 + g2[0] * Jp[2] + g2[1] * Jp[5] + g2[2] * Jp[8]};
+      // render extras: depth blends z = (Rcw pw + tcw).z, so its gradient dz (gpack[i][9]) joins dL/dpc.z
+      if constexpr (EXTRA) gpc.z += gc.y;
+      const ShDir<NC> d = sh_basis_f<NC>(pw, twc);
+      // eq (5): dL/dsh[c, rgb] = dL/dcolor[rgb] * basis[c]
+      gcol_out = gcol;
+      if (!factored) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          gsh[3 * c] = gcol.x * d.B[c]; gsh[3 * c + 1] = gcol.y * d.B[c]; gsh[3 * c + 2] = gcol.z * d.B[c];
+        }
+      }
+      if constexpr (!JW) sh_jac_dpw<NC>(d, sh, W);
+      float* opw = dL_dpw + 3 * (size_t)i;  // eq (7)
+      const float opw_old[3] = {o_pw.x, o_pw.y, o_pw.z};
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        opw[k] = gpc.x * Rcw[k] + gpc.y * Rcw[3 + k] + gpc.z * Rcw[6 + k] + gcol.x * W[k] + gcol.y * W[3 + k] +
+                 gcol.z * W[6 + k] + opw_old[k];
+      if constexpr (POSE) {
+        // p_c = Rcw pw + tcw: dL/dtcw += gpc, dL/dRcw += gpc pw^T (projection, J(p_c) of cov2d, depth)
+        const float gp[3] = {gpc.x, gpc.y, gpc.z}, pwv[3] = {pw.x, pw.y, pw.z};
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          pg[9 + r] = gp[r];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) pg[3 * r + k] = gp[r] * pwv[k];
+        }
+        // the W = Rcw factor of cov2d = (J W) Sigma (J W)^T with J held (clamped x/z, y/z as cov2d_f):
+        // dL/dM0 = 2 g2[0] v0 + g2[1] v1, dL/dM1 = g2[1] v0 + 2 g2[2] v1;  dL/dRcw += J0^T dL/dM0 + J1^T dL/dM1
+        const f3 gM0 = (2.f * g2[0]) * c2.v0 + g2[1] * c2.v1;
+        const f3 gM1 = g2[1] * c2.v0 + (2.f * g2[2]) * c2.v1;
+        const float z = P.pc.z, z2 = z * z;
+        const float a00 = pp.fx / z, a02 = -(pp.fx * c2.x) / z2, a11 = pp.fy / z, a12 = -(pp.fy * c2.y) / z2;
+        pg[0] += a00 * gM0.x; pg[1] += a00 * gM0.y; pg[2] += a00 * gM0.z;
+        pg[3] += a11 * gM1.x; pg[4] += a11 * gM1.y; pg[5] += a11 * gM1.z;
+        pg[6] += a02 * gM0.x + a12 * gM1.x; pg[7] += a02 * gM0.y + a12 * gM1.y; pg[8] += a02 * gM0.z + a12 * gM1.z;
+        // the SH colour sees pw - twc: dL/dtwc = -gcol^T dcolor/dpw
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pg[12 + k] = -(gcol.x * W[k] + gcol.y * W[3 + k] + gcol.z * W[6 + k]);
+      }
+    }
+  }
+  if constexpr (POSE) {
+    // one partial row of 16 floats per workgroup: a fixed butterfly across the wave64, the 4 waves in order through
+    // LDS.  No atomics -- k_pose_reduce sums the rows in a fixed order, so the result is bitwise reproducible.
+    __shared__ float pose_part[4][16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 15; ++k) {
+      float v = pg[k];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      if (lane == 0) pose_part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16)
+      pose_ws[16 * (size_t)blockIdx.x + threadIdx.x] =
+          threadIdx.x < 15 ? ((pose_part[0][threadIdx.x] + pose_part[1][threadIdx.x]) + pose_part[2][threadIdx.x]) +
+                                 pose_part[3][threadIdx.x]
+                           : 0.f;
+  }
+  if (factored) {   // (a kernel argument: the whole workgroup leaves here)
+    if (i < n) st3(dL_dsh + 3 * (size_t)i, gcol_out);
+    // the view's camera centre behind the [N][3] block: the row format of egs_sh_grad_views (dL_dsh_high = its address)
+    if (dL_dsh_high && blockIdx.x == 0 && threadIdx.x < 3) dL_dsh_high[threadIdx.x] = twc[threadIdx.x];
+    return;
+  }
+  if constexpr (RAW) {
+    if (i < n) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) dL_dsh[3 * (size_t)i + k] = gsh[k] + (accum ? dL_dsh[3 * (size_t)i + k] : 0.f);
+    }
+    if constexpr (KH > 0) {
+      if constexpr (KH % 2 == 1) stage_span_out<KH>(gsh + 3, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
+      else stage_rows_out<KH>(gsh + 3, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
+    }
+  } else {
+    stage_rows_out<K>(gsh, dL_dsh, n, blockIdx.x * 256, stage, accum != 0);
+  }
 }
 
-// The camera pose gradient from the partial rows of k_preprocess_bwd_pose: ONE workgroup of 1024 threads, thread t sums
+// The camera pose gradient from the partial rows of k_preprocess_bwd<.., POSE>: ONE workgroup of 1024 threads, thread t sums
 // column t % 16 of rows t / 16, t / 16 + 64, ... in double (eight loads in flight, added in row order), the 64 partial
 // sums of a column are added in index order, then the camera centre twc = -Rcw^T tcw is folded back:
 // dL/dRcw[r][k] -= tcw[r] dL/dtwc[k],  dL/dtcw -= Rcw dL/dtwc.  Every sum has a fixed order: identical partial rows
@@ -838,12 +1105,9 @@ extern "C" int egs_sh2color(int n, int sh_dim, const float* shs, const float* pw
   EGS_CHECK_ARG((((uintptr_t)colors | (uintptr_t)dcolor_dshs | (uintptr_t)dcolor_dpws) & 15) == 0);
   dim3 g(div_up(n, 256)), b(256);
   hipStream_t s = (hipStream_t)stream;
-  switch (sh_dim) {
-    case 3: EGS_LAUNCH("k_sh2color", (k_sh2color<1>), g, b, s, n, shs, pws, twc, colors, dcolor_dshs, dcolor_dpws); break;
-    case 12: EGS_LAUNCH("k_sh2color", (k_sh2color<4>), g, b, s, n, shs, pws, twc, colors, dcolor_dshs, dcolor_dpws); break;
-    case 27: EGS_LAUNCH("k_sh2color", (k_sh2color<9>), g, b, s, n, shs, pws, twc, colors, dcolor_dshs, dcolor_dpws); break;
-    default: EGS_LAUNCH("k_sh2color", (k_sh2color<16>), g, b, s, n, shs, pws, twc, colors, dcolor_dshs, dcolor_dpws); break;
-  }
+  decltype(&k_sh2color<1>) kern = nullptr;
+  with_sh_dim(sh_dim, [&](auto nc) { kern = k_sh2color<nc.value>; });
+  EGS_LAUNCH("k_sh2color", kern, g, b, s, n, shs, pws, twc, colors, dcolor_dshs, dcolor_dpws);
   EGS_LAUNCH_OK();
   return 0;
 }
@@ -878,17 +1142,11 @@ extern "C" int egs_chain_rule(int n, int sh_dim, const float* dloss_dus, const f
   EGS_CHECK_ARG((((uintptr_t)dloss_dus | (uintptr_t)dcov2d_dcov3ds | (uintptr_t)dcov3d_dscales | (uintptr_t)du_dpcs) & 7) == 0);
   dim3 g(div_up(n, 256)), b(256);
   hipStream_t s = (hipStream_t)stream;
-#define EGS_CHAIN(NC)                                                                                        \
-  EGS_LAUNCH("k_chain_rule", (k_chain_rule<NC>), g, b, s, n, dloss_dus, dloss_dcinv2ds, dloss_dcolors, Rcw,          \
-                     dcinv2d_dcov2ds, dcov2d_dcov3ds, dcov3d_drots, dcov3d_dscales, dcolor_dshs, du_dpcs,     \
-                     dcov2d_dpcs, dcolor_dpws, dloss_dpws, dloss_dshs, dloss_dscales, dloss_drots)
-  switch (sh_dim) {
-    case 3: EGS_CHAIN(1); break;
-    case 12: EGS_CHAIN(4); break;
-    case 27: EGS_CHAIN(9); break;
-    default: EGS_CHAIN(16); break;
-  }
-#undef EGS_CHAIN
+  decltype(&k_chain_rule<1>) kern = nullptr;
+  with_sh_dim(sh_dim, [&](auto nc) { kern = k_chain_rule<nc.value>; });
+  EGS_LAUNCH("k_chain_rule", kern, g, b, s, n, dloss_dus, dloss_dcinv2ds, dloss_dcolors, Rcw, dcinv2d_dcov2ds,
+             dcov2d_dcov3ds, dcov3d_drots, dcov3d_dscales, dcolor_dshs, du_dpcs, dcov2d_dpcs, dcolor_dpws, dloss_dpws,
+             dloss_dshs, dloss_dscales, dloss_drots);
   EGS_LAUNCH_OK();
   return 0;
 }
@@ -949,28 +1207,14 @@ extern "C" int egs_fused_forward(int n, int sh_dim, const float* pws, const floa
   dim3 g(div_up(n, 256)), b(256);
   // EGS_PRE_LDS_PAD (bytes of dynamic LDS, experiment knob): caps the resident workgroups per CU of this kernel
   static const size_t lds_pad = [] { const char* e = getenv("EGS_PRE_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }();
-#define EGS_PRE_K(KERN, NC, RAW, JW)                                                                            \
-  EGS_LAUNCH_LDS(#KERN, (KERN<NC, RAW, JW>), g, b, lds_pad, s, n, pp, pws, rots, scales, shs, shs_high, alphas, Rcw, \
-                 tcw, twc, us, depths, cinv2ds, colors, areas, (float4*)rec, bp, bo, visible, dcolor_dpws)
-#define EGS_PRE(NC, RAW)                                                                                        \
-  do {                                                                                                          \
-    if (aa && dcolor_dpws) EGS_PRE_K(k_preprocess_fwd_aa, NC, RAW, true);                                      \
-    else if (aa) EGS_PRE_K(k_preprocess_fwd_aa, NC, RAW, false);                                               \
-    else if (dcolor_dpws) EGS_PRE_K(k_preprocess_fwd, NC, RAW, true);                                          \
-    else EGS_PRE_K(k_preprocess_fwd, NC, RAW, false);                                                          \
-  } while (0)
-  switch (sh_dim * 2 + (raw ? 1 : 0)) {
-    case 6: EGS_PRE(1, false); break;
-    case 7: EGS_PRE(1, true); break;
-    case 24: EGS_PRE(4, false); break;
-    case 25: EGS_PRE(4, true); break;
-    case 54: EGS_PRE(9, false); break;
-    case 55: EGS_PRE(9, true); break;
-    case 96: EGS_PRE(16, false); break;
-    default: EGS_PRE(16, true); break;
-  }
-#undef EGS_PRE
-#undef EGS_PRE_K
+  decltype(&k_preprocess_fwd<1, false, false, false>) kern = nullptr;   // flags -> template arguments
+  with_sh_dim(sh_dim, [&](auto nc) {
+    with_bools([&](auto raw_c, auto jw, auto aa_c) { kern = k_preprocess_fwd<nc.value, raw_c.value, jw.value, aa_c.value>; },
+               raw, dcolor_dpws != nullptr, aa);
+  });
+  EGS_LAUNCH_LDS(aa ? "k_preprocess_fwd_aa" : "k_preprocess_fwd", kern, g, b, lds_pad, s, n, pp, pws, rots, scales, shs,
+                 shs_high, alphas, Rcw, tcw, twc, us, depths, cinv2ds, colors, areas, (float4*)rec, bp, bo, visible,
+                 dcolor_dpws);
   EGS_LAUNCH_OK();
   // the kernel above already did getRects + depth keys (k_bin_count of egs_splat_bin)
   return splat_bin_after_count(n, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, stream, host_totals);
@@ -978,7 +1222,7 @@ extern "C" int egs_fused_forward(int n, int sh_dim, const float* pws, const floa
 
 extern "C" size_t egs_fused_backward_ws_bytes(int n) { return egs_splat_bwd_ws_bytes(n); }
 
-// one partial row of 16 floats per 256-Gaussian workgroup of k_preprocess_bwd_pose
+// one partial row of 16 floats per 256-Gaussian workgroup of k_preprocess_bwd<.., POSE>
 extern "C" size_t egs_pose_ws_bytes(int n) { return align_up((size_t)div_up(n > 0 ? n : 1, 256) * 16 * sizeof(float), 256); }
 
 extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
@@ -996,7 +1240,7 @@ extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width,
                                   const EgsExtras* extras, const EgsPoseGrad* pose) {
   // extras (nullable): the render had depth / opacity / background (egs_splat_draw_rec_seg with extras); the draw pass
   // takes their upstream gradients and leaves dL/dz in gpack[i][9], the chain rule adds it to dL/dpw
-  // (k_preprocess_bwd_extra)
+  // (k_preprocess_bwd<.., EXTRA>)
   // phase 0: everything; 1: only the draw pass (-> packed gradient records in ws); 2: only the per-Gaussian
   // chain rule, for rows [row_begin, row_begin + row_count) -- a data-parallel caller launches the rows in a
   // few chunks and starts exchanging a chunk's gradients while the next one is computed (dist_views)
@@ -1051,59 +1295,30 @@ extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width,
   const size_t r0 = (size_t)row_begin;
   dim3 g(div_up(row_count, 256)), b(256);
   hipStream_t s = (hipStream_t)stream;
-  // row_begin is a multiple of the workgroup's 256 rows: every offset pointer keeps its 16-B alignment
-#define EGS_PREB_ARGS(NC, RAW)                                                                                    \
-  row_count, pp, pws + 3 * r0, rots + 4 * r0, scales + 3 * r0, shs + (RAW ? 3 : sh_dim) * r0,                      \
-      (RAW && shs_high) ? shs_high + kh * r0 : shs_high, alphas + r0, Rcw, tcw, twc, depths + r0,                  \
-      (const float4*)gpack + 3 * r0, dloss_dpws + 3 * r0, dloss_dshs + (factored ? 3 : (RAW ? 3 : sh_dim)) * r0,   \
-      factored ? (row_begin == 0 ? dloss_dshs + 3 * (size_t)n : nullptr)                                           \
-               : ((RAW && dloss_dshs_high) ? dloss_dshs_high + kh * r0 : dloss_dshs_high), dloss_dalphas + r0,       \
-      dloss_dscales + 3 * r0, dloss_drots + 4 * r0, dloss_dus + 2 * r0, dcolor_dpws ? dcolor_dpws + 9 * r0 : dcolor_dpws, \
-      accum
   float* pose_ws = pose ? (float*)pose->ws : nullptr;
-#define EGS_PREB_POSE(NC, RAW, JW, EX) \
-  EGS_LAUNCH("k_preprocess_bwd_pose", (k_preprocess_bwd_pose<NC, RAW, JW, EX>), g, b, s, EGS_PREB_ARGS(NC, RAW), pose_ws)
-#define EGS_PREB_AA(NC, RAW, JW, EX, PO) \
-  EGS_LAUNCH("k_preprocess_bwd_aa", (k_preprocess_bwd_aa<NC, RAW, JW, EX, PO>), g, b, s, EGS_PREB_ARGS(NC, RAW), pose_ws)
-#define EGS_PREB_AA_JW(NC, RAW, EX, PO)                                                                           \
-  do {                                                                                                            \
-    if (dcolor_dpws) EGS_PREB_AA(NC, RAW, true, EX, PO);                                                          \
-    else EGS_PREB_AA(NC, RAW, false, EX, PO);                                                                     \
-  } while (0)
-#define EGS_PREB(NC, RAW)                                                                                         \
-  do {                                                                                                            \
-    if (aa) {                                                                                                     \
-      if (pose && extras) EGS_PREB_AA_JW(NC, RAW, true, true);                                                    \
-      else if (pose) EGS_PREB_AA_JW(NC, RAW, false, true);                                                        \
-      else if (extras) EGS_PREB_AA_JW(NC, RAW, true, false);                                                      \
-      else EGS_PREB_AA_JW(NC, RAW, false, false);                                                                 \
-    } else if (pose) {                                                                                            \
-      if (extras && dcolor_dpws) EGS_PREB_POSE(NC, RAW, true, true);                                              \
-      else if (extras) EGS_PREB_POSE(NC, RAW, false, true);                                                       \
-      else if (dcolor_dpws) EGS_PREB_POSE(NC, RAW, true, false);                                                  \
-      else EGS_PREB_POSE(NC, RAW, false, false);                                                                  \
-    } else if (extras && dcolor_dpws)                                                                             \
-      EGS_LAUNCH("k_preprocess_bwd_extra", (k_preprocess_bwd_extra<NC, RAW, true>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
-    else if (extras)                                                                                              \
-      EGS_LAUNCH("k_preprocess_bwd_extra", (k_preprocess_bwd_extra<NC, RAW, false>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
-    else if (dcolor_dpws) EGS_LAUNCH("k_preprocess_bwd", (k_preprocess_bwd<NC, RAW, true>), g, b, s, EGS_PREB_ARGS(NC, RAW)); \
-    else EGS_LAUNCH("k_preprocess_bwd", (k_preprocess_bwd<NC, RAW, false>), g, b, s, EGS_PREB_ARGS(NC, RAW));     \
-  } while (0)
-  switch (sh_dim * 2 + (raw ? 1 : 0)) {
-    case 6: EGS_PREB(1, false); break;
-    case 7: EGS_PREB(1, true); break;
-    case 24: EGS_PREB(4, false); break;
-    case 25: EGS_PREB(4, true); break;
-    case 54: EGS_PREB(9, false); break;
-    case 55: EGS_PREB(9, true); break;
-    case 96: EGS_PREB(16, false); break;
-    default: EGS_PREB(16, true); break;
-  }
-#undef EGS_PREB
-#undef EGS_PREB_AA_JW
-#undef EGS_PREB_AA
-#undef EGS_PREB_POSE
-#undef EGS_PREB_ARGS
+  // the profiler label names the flavour: AA over POSE over EXTRA
+  const char* label = aa       ? "k_preprocess_bwd_aa"
+                      : pose   ? "k_preprocess_bwd_pose"
+                      : extras ? "k_preprocess_bwd_extra"
+                               : "k_preprocess_bwd";
+  // the widths of the SH rows in (shs) and out (dloss_dshs): the low part alone for RAW / the factored gradient
+  const int sh_in = raw ? 3 : sh_dim, sh_out = (factored || raw) ? 3 : sh_dim;
+  // row_begin is a multiple of the workgroup's 256 rows: every offset pointer keeps its 16-B alignment
+  decltype(&k_preprocess_bwd<1, false, false, false, false, false>) kern = nullptr;   // flags -> template arguments
+  with_sh_dim(sh_dim, [&](auto nc) {
+    with_bools(
+        [&](auto raw_c, auto jw, auto extra, auto pose_c, auto aa_c) {
+          kern = k_preprocess_bwd<nc.value, raw_c.value, jw.value, extra.value, pose_c.value, aa_c.value>;
+        },
+        raw, dcolor_dpws != nullptr, extras != nullptr, pose != nullptr, aa);
+  });
+  EGS_LAUNCH(label, kern, g, b, s, row_count, pp, pws + 3 * r0, rots + 4 * r0, scales + 3 * r0, shs + sh_in * r0,
+             (raw && shs_high) ? shs_high + kh * r0 : shs_high, alphas + r0, Rcw, tcw, twc, depths + r0,
+             (const float4*)gpack + 3 * r0, dloss_dpws + 3 * r0, dloss_dshs + sh_out * r0,
+             factored ? (row_begin == 0 ? dloss_dshs + 3 * (size_t)n : nullptr)
+                      : ((raw && dloss_dshs_high) ? dloss_dshs_high + kh * r0 : dloss_dshs_high),
+             dloss_dalphas + r0, dloss_dscales + 3 * r0, dloss_drots + 4 * r0, dloss_dus + 2 * r0,
+             dcolor_dpws ? dcolor_dpws + 9 * r0 : dcolor_dpws, accum, pose_ws);
   EGS_LAUNCH_OK();
   if (pose) {
     EGS_LAUNCH("k_pose_reduce", k_pose_reduce, dim3(1), dim3(1024), s, (int)g.x, pose_ws, Rcw, tcw, pose->dloss_dRcw,
@@ -1124,19 +1339,13 @@ extern "C" int egs_sh_grad_views(int n, int sh_dim, int views, const float* pws,
   EGS_CHECK_ARG((((uintptr_t)dloss_dshs | (uintptr_t)dloss_dhigh_shs) & 15) == 0);
   dim3 g(div_up(n, 256)), b(256);
   hipStream_t s = (hipStream_t)stream;
-#define EGS_SHV(NC, RAW)                                                                                     \
-  EGS_LAUNCH("k_sh_grad_views", (k_sh_grad_views<NC, RAW>), g, b, s, n, views, pws, rows, row_stride, scale, \
-             dloss_dshs, dloss_dhigh_shs, accumulate ? 1 : 0)
-  switch (sh_dim * 2 + (raw ? 1 : 0)) {
-    case 6: case 7: EGS_SHV(1, false); break;   // degree 0: the row IS the low part ([N][3] either way)
-    case 24: EGS_SHV(4, false); break;
-    case 25: EGS_SHV(4, true); break;
-    case 54: EGS_SHV(9, false); break;
-    case 55: EGS_SHV(9, true); break;
-    case 96: EGS_SHV(16, false); break;
-    default: EGS_SHV(16, true); break;
-  }
-#undef EGS_SHV
+  decltype(&k_sh_grad_views<1, false>) kern = nullptr;
+  with_sh_dim(sh_dim, [&](auto nc) {
+    // degree 0: the row IS the low part ([N][3] either way) -- no RAW instance
+    with_bools([&](auto raw_c) { kern = k_sh_grad_views<nc.value, raw_c.value && nc.value != 1>; }, raw);
+  });
+  EGS_LAUNCH("k_sh_grad_views", kern, g, b, s, n, views, pws, rows, row_stride, scale, dloss_dshs, dloss_dhigh_shs,
+             accumulate ? 1 : 0);
   EGS_LAUNCH_OK();
   return 0;
 }

@@ -96,8 +96,8 @@ struct DrawParams {
   int masked;
 };
 DrawParams make_draw_params(int W, int H, const EgsPolicy* pol, bool backward = false);
-// the EXTRA flavour of the two draw kernels (render extras, egs_hip.h EgsExtras): a kernel argument of its own, so that
-// DrawParams and the plain instances stay as they are
+// what the EXTRA flavour of the two draw kernels takes (render extras, egs_hip.h EgsExtras): a kernel argument of its
+// own, so that DrawParams stays as it is
 struct DrawExtras {
   const float* depths;     // [N] camera-space z of every Gaussian
   float* depth_out;        // forward, nullable [H][W]: sum w z
@@ -106,12 +106,6 @@ struct DrawExtras {
   const float* dl_alpha;   // backward, nullable [H][W]: dL/dalpha (NULL: 0)
   float bg[3];             // image += T_final * bg
 };
-int launch_draw_extra(const DrawParams& dp, const EgsPolicy* pol, int32_t* ranges, const int32_t* gsid,
-                      const float4* rec, float* image, int32_t* contrib, float* final_tau, const DrawExtras& ex,
-                      hipStream_t s);
-int launch_draw_bwd_extra(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
-                          const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg,
-                          float* gpack, const DrawExtras& ex, hipStream_t s);
 int draw_grid(const DrawParams& p);
 // capacity of a dispatch-order buffer (the per-XCD modes pad every class to the largest one)
 int tile_order_len(int gx, int gy);
@@ -121,8 +115,9 @@ int tile_order_enqueue(DrawParams& p, int which, int32_t* buf, size_t buf_len, c
                        const int32_t* work = nullptr, const int32_t* walk = nullptr, uint32_t* hint = nullptr);
 // the per-tile work measure of k_draw rebuilt from `contrib` (work nullable: the walk alone)
 int tile_work_from_contrib(const DrawParams& p, const int32_t* contrib, int32_t* work, int32_t* walk, hipStream_t s);
+// ex (nullable): the render extras -- the EXTRA instance of the kernel, launch label "k_draw_extra"
 int launch_draw(const DrawParams& dp, const EgsPolicy* pol, int32_t* ranges, const int32_t* gsid, const float4* rec,
-                float* image, int32_t* contrib, float* final_tau, hipStream_t s);
+                float* image, int32_t* contrib, float* final_tau, const DrawExtras* ex, hipStream_t s);
 
 // ---- long lists split over several waves (egs_segments.hip) ----------------------------------------
 constexpr int SEG_HDR = 16;          // header words
@@ -168,9 +163,15 @@ int draw_segments_forward(DrawParams& dp, const EgsPolicy* pol, SegArgs& sga, co
                           bool plan_zeroed,
                           int32_t* ranges, const int32_t* gsid, const float4* rec, float* image, int32_t* contrib,
                           float* final_tau, hipStream_t s);
+// The last argument of k_draw_bwd belongs to the flavour: the segment path's SegArgs (zeros for unsplit lists) or,
+// EXTRA, the render extras.  The two never meet (EXTRA draws unsplit lists only), so they share the one kernel argument
+// and neither flavour's argument layout depends on the other's.
+template <bool EXTRA> struct DrawBwdFlavour { SegArgs sg; };
+template <> struct DrawBwdFlavour<true> { DrawExtras ex; };
+// ex (nullable): the render extras -- the EXTRA instance of the kernel, launch label "k_draw_bwd_extra"
 int launch_draw_bwd(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                     const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg, float* gpack,
-                    hipStream_t s);
+                    const DrawExtras* ex, hipStream_t s);
 // the same over the forward pass's work items (one wave per segment of a split tile)
 int launch_draw_bwd_seg(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                         const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg,

@@ -137,16 +137,15 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
                                       walk ? seg_hint : nullptr);
     if (rc) return rc;
   }
+  DrawExtras ex = {};
   if (extras) {
-    DrawExtras ex = {};
     ex.depths = extras->depths;
     ex.dl_depth = extras->dloss_ddepth;
     ex.dl_alpha = extras->dloss_dalpha;
     for (int c = 0; c < 3; ++c) ex.bg[c] = extras->background[c];
-    return launch_draw_bwd_extra(dp, pol, patch_range_per_tile, gsid_per_patch, rec, final_tau, contrib, dloss_dgammas,
-                                 gpack, ex, s);
   }
-  return launch_draw_bwd(dp, pol, patch_range_per_tile, gsid_per_patch, rec, final_tau, contrib, dloss_dgammas, gpack, s);
+  return launch_draw_bwd(dp, pol, patch_range_per_tile, gsid_per_patch, rec, final_tau, contrib, dloss_dgammas, gpack,
+                         extras ? &ex : nullptr, s);
 }
 }  // namespace egs
 
@@ -299,15 +298,15 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
     dp.zero_n4 = (uint32_t)(3 * (size_t)n);
     dp.zero_per = (dp.zero_n4 + (uint32_t)draw_grid(dp) - 1) / (uint32_t)draw_grid(dp);
   }
+  DrawExtras ex = {};
   if (extras) {
-    DrawExtras ex = {};
     ex.depths = extras->depths;
     ex.depth_out = extras->depth_out;
     ex.alpha_out = extras->alpha_out;
     for (int c = 0; c < 3; ++c) ex.bg[c] = extras->background[c];
-    return launch_draw_extra(dp, pol, patch_range_per_tile, gsid_per_patch, rec, image, contrib, final_tau, ex, s);
   }
-  return launch_draw(dp, pol, patch_range_per_tile, gsid_per_patch, rec, image, contrib, final_tau, s);
+  return launch_draw(dp, pol, patch_range_per_tile, gsid_per_patch, rec, image, contrib, final_tau,
+                     extras ? &ex : nullptr, s);
 }
 
 extern "C" int egs_splat_draw(int n, int64_t patches, int width, int height, const float* us,

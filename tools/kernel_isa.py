@@ -2,7 +2,7 @@
 """Per-kernel ISA digests of csrc/*.hip (gfx950), for refactors that must not change a kernel.
 
     python tools/kernel_isa.py dump  out.json     # {demangled kernel name: sha1 of its normalised instruction stream}
-    python tools/kernel_isa.py diff  a.json b.json
+    python tools/kernel_isa.py diff  a.json b.json  # kernel for kernel; flavour kernels under their folded name (FOLDED)
 
 Every .hip file is compiled device-only to assembly (`hipcc -S --cuda-device-only`, the Makefile's flags); a kernel's
 text is what lies between its label and its `.Lfunc_end`; local labels (`.LBB<function>_<block>`) are renumbered
@@ -67,8 +67,49 @@ def dump(out_path, sources=None):
     print("%d kernels -> %s" % (len(table), out_path))
 
 
+# A kernel flavour used to be a kernel NAME (k_draw_extra<..>), now it is a template argument (k_draw<.., true>):
+# old flavour name -> (folded name, template arguments it had, template arguments the fold appends)
+FOLDED = {
+    "k_preprocess_fwd": ("k_preprocess_fwd", 3, ["false"]),                         # <NC, RAW, JW> + AA
+    "k_preprocess_fwd_aa": ("k_preprocess_fwd", 3, ["true"]),
+    "k_preprocess_bwd": ("k_preprocess_bwd", 3, ["false", "false", "false"]),       # <NC, RAW, JW> + EXTRA, POSE, AA
+    "k_preprocess_bwd_extra": ("k_preprocess_bwd", 3, ["true", "false", "false"]),
+    "k_preprocess_bwd_pose": ("k_preprocess_bwd", 4, ["true", "false"]),            # <NC, RAW, JW, EXTRA>
+    "k_preprocess_bwd_aa": ("k_preprocess_bwd", 5, ["true"]),                       # <NC, RAW, JW, EXTRA, POSE>
+    "k_viewer_prep": ("k_viewer_prep", 1, ["false"]),                               # <NC> + AA
+    "k_viewer_prep_aa": ("k_viewer_prep", 1, ["true"]),
+    "k_draw": ("k_draw", 4, ["false"]),                                             # <BOX, FLOOR, CLAMP, SKIP> + EXTRA
+    "k_draw_extra": ("k_draw", 4, ["true"]),
+    "k_draw_bwd": ("k_draw_bwd", 5, ["false"]),                                     # <BOX, FLOOR, CLAMP, RED, SEG> + EXTRA
+    "k_draw_bwd_extra": ("k_draw_bwd", 4, ["false", "true"]),                       # <BOX, FLOOR, CLAMP, RED>
+}
+
+
+def canonical(name):
+    """The name a kernel is compared under: a flavour kernel of an older dump gets the name of the template instance
+    it was folded into, so that a dump from before the fold and one from after it compare kernel for kernel.  The
+    parameter list is dropped for these kernels (the fold gave every instance the flavours' trailing arguments); any
+    other name is returned as it is."""
+    m = re.match(r"void egs::(\w+)<(.*?)>\(", name)
+    if not m or m.group(1) not in FOLDED:
+        return name
+    base, args = m.group(1), [x.strip() for x in m.group(2).split(",")]
+    new_base, arity, appended = FOLDED[base]
+    if len(args) == arity:
+        base, args = new_base, args + appended
+    return "%s<%s>" % (base, ", ".join(args))
+
+
+def load(path):
+    table = {}
+    for k, v in json.load(open(path)).items():
+        assert canonical(k) not in table, "two kernels map to " + canonical(k)
+        table[canonical(k)] = v
+    return table
+
+
 def diff(a, b):
-    A, B = json.load(open(a)), json.load(open(b))
+    A, B = load(a), load(b)
     bad = 0
     for k in sorted(set(A) | set(B)):
         if k not in A: print("only in b:", k); bad += 1

@@ -1,18 +1,21 @@
-import os, subprocess, shutil
-C='/root/repo/easygaussiansplatting_amd/csrc/'
+"""Regenerates the *.patch files of this directory from the current csrc/: every probe is a list of search / replace
+pairs (each search text must occur exactly once).  Run it after an edit of the kernels moved a probe's anchor."""
+import os, re, subprocess, tempfile
+HERE=os.path.dirname(os.path.abspath(__file__))
+C=os.path.join(HERE,'..','..','..','easygaussiansplatting_amd','csrc','')
 def rep(s,a,b):
     assert s.count(a)==1,(s.count(a),a); return s.replace(a,b)
 def mkpatch(name, edits, desc):
-    tmp='/tmp/var/'+name; shutil.rmtree(tmp, ignore_errors=True); os.makedirs(tmp+'/a'); os.makedirs(tmp+'/b')
     out=desc
-    for f,fn in edits.items():
-        s=open(C+f).read(); open(tmp+'/a/'+f,'w').write(s); open(tmp+'/b/'+f,'w').write(fn(s))
-        r=subprocess.run(['diff','-u','a/'+f,'b/'+f],cwd=tmp,capture_output=True,text=True).stdout
-        r=r.replace('--- a/'+f,'--- a/easygaussiansplatting_amd/csrc/'+f).replace('+++ b/'+f,'+++ b/easygaussiansplatting_amd/csrc/'+f)
-        import re
-        r=re.sub(r'(^--- \S+)\t.*$', r'\1', r, flags=re.M); r=re.sub(r'(^\+\+\+ \S+)\t.*$', r'\1', r, flags=re.M)
-        out+=r
-    open('/root/repo/tools/lab/variants/'+name+'.patch','w').write(out)
+    with tempfile.TemporaryDirectory() as tmp:
+        os.makedirs(tmp+'/a'); os.makedirs(tmp+'/b')
+        for f,fn in edits.items():
+            s=open(C+f).read(); open(tmp+'/a/'+f,'w').write(s); open(tmp+'/b/'+f,'w').write(fn(s))
+            r=subprocess.run(['diff','-u','a/'+f,'b/'+f],cwd=tmp,capture_output=True,text=True).stdout
+            r=r.replace('--- a/'+f,'--- a/easygaussiansplatting_amd/csrc/'+f).replace('+++ b/'+f,'+++ b/easygaussiansplatting_amd/csrc/'+f)
+            r=re.sub(r'(^--- \S+)\t.*$', r'\1', r, flags=re.M); r=re.sub(r'(^\+\+\+ \S+)\t.*$', r'\1', r, flags=re.M)
+            out+=r
+    open(os.path.join(HERE,name+'.patch'),'w').write(out)
 
 # 1. issue-port probes of k_draw
 def draw_probes(s):
@@ -61,7 +64,7 @@ def draw_probes(s):
 #endif
   if (p.work_out) {   // what k_draw_bwd will walk: the largest contributor index of the tile and of its blocks''')
     return s
-mkpatch('draw_issue_probes', {'egs_draw_fwd.inc': draw_probes}, '''Issue-port probes of k_draw (round 4, DESIGN 3.3 / LAB 3.3): -DEGS_DRAW_DUMMY_SALU=N / -DEGS_DRAW_DUMMY_VALU=N add N scalar /
+mkpatch('draw_issue_probes', {'egs_draw.hip': draw_probes}, '''Issue-port probes of k_draw (round 4, DESIGN 3.3 / LAB 3.3): -DEGS_DRAW_DUMMY_SALU=N / -DEGS_DRAW_DUMMY_VALU=N add N scalar /
 vector instructions per (tile, entry); -DEGS_DRAW_PROBE_NOK reads two LDS pieces per entry instead of three and blends
 constant colours (timing only, the image is not the scene's).  Apply, build a variant library, time it with
 tools/lab/lab_issue_probe.sh.  Not part of the product sources.
@@ -120,7 +123,7 @@ def hdr_hit(s):
   // of its tile -- what a forward pass COULD leave behind; the backward pass then drops such entries before staging them
   const uint32_t* hit_bits;
 };''')
-mkpatch('draw_bwd_probes', {'egs_draw.hip': lambda s: bwd_params_probes(bwd_probes(s)), 'egs_draw_bwd.inc': bwd_body_probes,
+mkpatch('draw_bwd_probes', {'egs_draw.hip': lambda s: bwd_params_probes(bwd_body_probes(bwd_probes(s))),
                            'egs_raster.h': hdr_hit}, '''Probes of k_draw_bwd (rounds 3-4, LAB 3.4): -DEGS_PROBE_REDUCE=1|2 replaces the transposing wave reduction by plain adds
 (timing only); -DEGS_PROBE_HIT_BITS=1 + egs_probe_set_hit_bits() lets the kernel drop entries a forward pass could have
 marked as hitting nothing (prices the "hit bit" proposal; tools/lab/bwd_hit_stats.py binds the symbol itself).

@@ -23,18 +23,30 @@ src, sq, ub, dst = sys.argv[1:5]
 # static instruction mix of the draw kernels (tools/valu_mix.py on the ISA of THESE sources): the share of half-rate
 # instructions among the non-quarter-rate ones -- turns the band the counters leave into a point estimate
 mix = json.load(open(sys.argv[5])) if len(sys.argv) > 5 else {}
-MIX_OF = {"k_draw_bwd": "k_draw_bwdILb0ELb1ELb1ELi7ELb0", "k_draw": "k_drawILb0ELb1ELb1ELb1",
-          "k_draw_bwd_seg": "k_draw_bwdILb0ELb1ELb1ELi7ELb1", "k_draw_seg": "k_draw_segILb1ELb1ELi0"}
+# (mangled template-argument lists of the training instances, EXTRA = false included; matched against the symbol
+# valu_mix.py recorded)
+MIX_OF = {"k_draw_bwd": "k_draw_bwdILb0ELb1ELb1ELi7ELb0ELb0EE", "k_draw": "k_drawILb0ELb1ELb1ELb1ELb0EE",
+          "k_draw_bwd_seg": "k_draw_bwdILb0ELb1ELb1ELi7ELb1ELb0EE", "k_draw_seg": "k_draw_segILb1ELb1ELi0EE"}
 
 
 def kname(k):
-    """kernel name of the bench tables: the template instances of the segment path are kernels of their own"""
-    base = k.replace("egs::", "").split("<")[0]
+    """kernel name of the bench tables = the launch label of the instance (first argument of EGS_LAUNCH), from the
+    symbol rocprofv3 reports: a flavour is a template argument of the kernel, the tables keep one row per flavour"""
+    base = k.replace("void ", "").replace("egs::", "").split("<")[0]
     args = [x.strip() for x in k[k.find("<") + 1:k.rfind(">")].split(",")] if "<" in k else []
+    on = lambda i: len(args) > i and args[i] == "true"
     if base == "k_draw_seg" and args:
         return {"0": "k_draw_seg", "1": "k_draw_seg_fix", "2": "k_draw_seg_compose"}.get(args[-1], base)
-    if base == "k_draw_bwd" and len(args) >= 5 and args[4] == "true":
-        return "k_draw_bwd_seg"
+    if base == "k_draw":               # <BOX, FLOOR, CLAMP, SKIP, EXTRA>
+        return "k_draw_extra" if on(4) else base
+    if base == "k_draw_bwd":           # <BOX, FLOOR, CLAMP, RED, SEG, EXTRA>
+        return "k_draw_bwd_seg" if on(4) else "k_draw_bwd_extra" if on(5) else base
+    if base == "k_preprocess_fwd":     # <NC, RAW, JW, AA>
+        return "k_preprocess_fwd_aa" if on(3) else base
+    if base == "k_preprocess_bwd":     # <NC, RAW, JW, EXTRA, POSE, AA>: labelled AA over POSE over EXTRA
+        return base + ("_aa" if on(5) else "_pose" if on(4) else "_extra" if on(3) else "")
+    if base == "k_viewer_prep":        # <NC, AA>
+        return "k_viewer_prep_aa" if on(1) else base
     return base
 
 
@@ -79,7 +91,10 @@ if sq != "-":
         if "duration_ns" in c:       # the clock of the counter pass itself: cycles of one XCD over the kernel's duration
             e["duration_us_in_counter_pass"] = round(c["duration_ns"] / 1e3, 1)
             e["gui_clock_mhz"] = round(c["GRBM_GUI_ACTIVE"] / 8 / c["duration_ns"] * 1e3, 1)
-        m = next((v for k, v in mix.items() if MIX_OF.get(name) and MIX_OF[name] in k), None)
+        m = next((v for k, v in mix.items() if MIX_OF.get(name) and MIX_OF[name] in v.get("symbol", k)), None)
+        if mix and name in MIX_OF and m is None:   # a mix file of other sources: no silent table without valu_frac
+            sys.exit("%s: no entry for %s (symbol containing %s): regenerate it with tools/valu_mix.py from the ISA of "
+                     "these sources" % (sys.argv[5], name, MIX_OF[name]))
         if m:
             h = m["half_share_of_non_quarter"]
             cyc = (insts - q) * (2.5 + 1.8 * h) + q * 8.5
