@@ -121,6 +121,7 @@ SIGNATURES = {
     "egs_fused_backward_ws_bytes": (_sz, [_i]),
     "egs_fused_backward": (_i, [_i, _i, _i64, _i, _i] + [_P] * 9 + [_f] * 4 + [_PP] + [_P] * 11 + [_P, _sz]
                            + [_P] * 7 + [_P, _P, _P, _i, _i, _i, _P, _sz, _P, _PX, _PPose]),
+    "egs_grad_records_absgrad": (_i, [_i, _P, _P, _P]),
     "egs_gau_loss_ws_bytes": (_sz, [_i, _i]),
     "egs_gau_loss": (_i, [_i, _i, _P, _P, _f, _f, _P, _sz, _P, _P, _P]),
     "egs_density_accumulate": (_i, [_i, _P, _P, _i, _P, _P, _P]),

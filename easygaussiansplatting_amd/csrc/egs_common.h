@@ -183,7 +183,8 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
                      void* seg_ws = nullptr /* the segment workspace the forward draw filled (egs_splat_draw_rec_seg) */,
                      size_t seg_ws_bytes = 0, int rebuild = 0 /* seg_ws is fresh: rebuild the states from contrib first */,
                      uint32_t* seg_hint = nullptr /* page-locked words that learn the longest walk */,
-                     const EgsExtras* extras = nullptr /* render extras: the EXTRA draw kernel (unsplit lists only) */);
+                     const EgsExtras* extras = nullptr /* render extras: the EXTRA draw kernel (unsplit lists only) */,
+                     bool absgrad = false /* the ABS draw kernels: sum |dL/du| per pixel into gpack[i][10..11] */);
 
 // ---- device helpers ---------------------------------------------------------
 #ifdef __HIPCC__

@@ -18,6 +18,10 @@ namespace egs {
 #ifndef EGS_DRAWB_RED_DEFAULT
 #define EGS_DRAWB_RED_DEFAULT 7
 #endif
+// waves per SIMD the ABS instances of k_draw_bwd are compiled for (chosen by measurement)
+#ifndef EGS_DRAWB_ABS_WAVES
+#define EGS_DRAWB_ABS_WAVES 4
+#endif
 
 // Longest-list-first dispatch order of the tiles for the two draw kernels.  A tile is one wave whose run
 // time is proportional to its list length (0 ... ~2x the mean on the 1 M scene); workgroups are handed to
@@ -537,6 +541,12 @@ __device__ __forceinline__ float merge2(float a, float b, bool hi) {
   const float own = hi ? b : a, other = hi ? a : b;
   return own + dpp_get<CTRL>(other);
 }
+// out = a + a[mirror] everywhere, then b + b[mirror] on the banks of `bank_hi`
+#define EGS_MERGE_BANK(out, a, b, ctrl, bank_hi)                                                              \
+  do {                                                                                                        \
+    asm("v_add_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf" : "=v"(out) : "v"(a));                  \
+    asm("v_add_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:" bank_hi : "+v"(out) : "v"(b));            \
+  } while (0)
 // the nine row-wise totals of (q0..q8) in lanes {0, 8, 4, 12, 2, 10, 6, 14, odd} of every row.
 // NQ = 10 (render extras): q8 and a tenth q9 share the odd lanes -- both are reduced over the two mirror levels, then
 // split by lane bit 1 at the quad level: q8 lands in lanes {1, 5, 9, 13}, q9 in lanes {3, 7, 11, 15}
@@ -554,13 +564,28 @@ __device__ __forceinline__ float odd_lanes_tail(const float (&q)[NQ], float r, b
     return merge2<M1>(r, s8, h1);
   }
 }
+// NQ = 11 (absolute screen-space gradients, ABS): the odd lanes hold the 12-leaf tree without its dz leaf -- q8 keeps lanes
+// {1, 5, 9, 13}, and the lanes q9 had are split once more, by lane bit 2: leaf 10 (q[9], sum |t_x|) lands in lanes {3, 11},
+// leaf 11 (q[10], sum |t_y|) in lanes {7, 15}.  The bit-2 split is a bank-masked DPP add (banks 1 and 3), no select.
+__device__ __forceinline__ float odd_lanes_tail_abs(const float (&q)[11], float r, bool h2, bool h1) {
+  constexpr int M8 = 0x140, M4 = 0x141, M2 = 0x4E, M1 = 0xB1;
+  float s8 = q[8] + dpp_get<M8>(q[8]);
+  s8 += dpp_get<M4>(s8);
+  const float sx = q[9] + dpp_get<M8>(q[9]), sy = q[10] + dpp_get<M8>(q[10]);
+  float sa;
+  EGS_MERGE_BANK(sa, sx, sy, "row_half_mirror", "0xa");
+  return merge2<M1>(r, merge2<M2>(s8, sa, h2), h1);
+}
 template <int NQ>
 __device__ __forceinline__ float rows_to_lanes9(const float (&q)[NQ], int c16) {
   const bool h8 = (c16 & 8) != 0, h4 = (c16 & 4) != 0, h2 = (c16 & 2) != 0, h1 = (c16 & 1) != 0;
   constexpr int M8 = 0x140, M4 = 0x141, M2 = 0x4E, M1 = 0xB1;  // row_mirror, row_half_mirror, quad [2,3,0,1], [1,0,3,2]
   const float p01 = merge2<M8>(q[0], q[1], h8), p23 = merge2<M8>(q[2], q[3], h8);
   const float p45 = merge2<M8>(q[4], q[5], h8), p67 = merge2<M8>(q[6], q[7], h8);
-  if constexpr (NQ == 10) {
+  if constexpr (NQ == 11) {
+    const float a = merge2<M4>(p01, p23, h4), b = merge2<M4>(p45, p67, h4);
+    return odd_lanes_tail_abs(q, merge2<M2>(a, b, h2), h2, h1);
+  } else if constexpr (NQ == 10) {
     const float a = merge2<M4>(p01, p23, h4), b = merge2<M4>(p45, p67, h4);
     return odd_lanes_tail(q, merge2<M2>(a, b, h2), h2, h1);
   } else {
@@ -581,12 +606,6 @@ __device__ __forceinline__ float rows_to_lanes9(const float (&q)[NQ], int c16) {
 // merge2 above costs two v_cndmask and a DPP add.  The first two levels split the row by lane bits 3 and 2 --
 // exactly what DPP's bank mask addresses (a bank = four consecutive lanes of a row): one DPP add for everybody,
 // one bank-masked DPP add for the lanes that reduce the second register; no select.
-// out = a + a[mirror] everywhere, then b + b[mirror] on the banks of `bank_hi`
-#define EGS_MERGE_BANK(out, a, b, ctrl, bank_hi)                                                              \
-  do {                                                                                                        \
-    asm("v_add_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:0xf" : "=v"(out) : "v"(a));                  \
-    asm("v_add_f32_dpp %0, %1, %1 " ctrl " row_mask:0xf bank_mask:" bank_hi : "+v"(out) : "v"(b));            \
-  } while (0)
 // same result layout as rows_to_lanes9: totals in lanes {0, 8, 4, 12, 2, 10, 6, 14, odd} of every row
 template <int NQ>
 __device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c16) {
@@ -597,6 +616,11 @@ __device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c
   EGS_MERGE_BANK(p23, q[2], q[3], "row_mirror", "0xc");
   EGS_MERGE_BANK(p45, q[4], q[5], "row_mirror", "0xc");
   EGS_MERGE_BANK(p67, q[6], q[7], "row_mirror", "0xc");
+  if constexpr (NQ == 11) {
+    EGS_MERGE_BANK(a, p01, p23, "row_half_mirror", "0xa");
+    EGS_MERGE_BANK(b, p45, p67, "row_half_mirror", "0xa");
+    return odd_lanes_tail_abs(q, merge2<M2>(a, b, h2), h2, h1);
+  }
   if constexpr (NQ == 10) {
     EGS_MERGE_BANK(a, p01, p23, "row_half_mirror", "0xa");
     EGS_MERGE_BANK(b, p45, p67, "row_half_mirror", "0xa");
@@ -635,8 +659,15 @@ __device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c
 // the tenth partial and the per-pixel dL/ddepth spill 44-60 B per lane, and that is slower (bench scene: 531 against
 // 494 us).
 // fa: the flavour's own argument -- SegArgs fa.sg, or DrawExtras fa.ex for EXTRA (DrawBwdFlavour, egs_raster.h)
-template <bool BOX, bool FLOOR, bool CLAMP, int RED, bool SEG, bool EXTRA>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 5, 8))) void k_draw_bwd(DrawParams p, const int32_t* __restrict__ ranges,
+//
+// ABS (absolute screen-space gradients, AbsGS / gsplat's absgrad; with SEG, never with EXTRA): besides du = sum t the
+// walk also sums |t_x| and |t_y| of every hit, t = -w cinv (dx, dy) -- the densification statistic in which the pulls of
+// different pixels on a large Gaussian cannot cancel.  cinv is the entry's sD[j] (a broadcast read), the two sums are
+// leaves 10 and 11 of the reduction and go out with the other nine, in the same atomic instruction, to the pad slots
+// gpack[i][10] and gpack[i][11] (the chain rule never reads them; egs_grad_records_absgrad copies them out).  A
+// statistic, not a gradient.  Occupancy: EGS_DRAWB_ABS_WAVES.
+template <bool BOX, bool FLOOR, bool CLAMP, int RED, bool SEG, bool EXTRA, bool ABS = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : (ABS ? EGS_DRAWB_ABS_WAVES : 5), 8))) void k_draw_bwd(DrawParams p, const int32_t* __restrict__ ranges,
                                                  const int32_t* __restrict__ gsid,
                                                  const float4* __restrict__ rec,
                                                  const float* __restrict__ final_tau,
@@ -644,11 +675,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
                                                  const float* __restrict__ dLdg,
                                                  float* __restrict__ gpack, DrawBwdFlavour<EXTRA> fa) {
   static_assert(!(SEG && EXTRA), "the EXTRA flavour draws unsplit lists only");
+  static_assert(!(ABS && EXTRA), "the ABS flavour is not built for renders with extras");
   __shared__ float4 sA[64], sB[64], sC[64], sD[64];  // sD = {cinv.x, cinv.y, cinv.z, gsid}
   __shared__ float4 szero[3];                        // a line of zeros (see the accumulator reset below)
   __shared__ float sZ[EXTRA ? 64 : 1];               // (never touched by the other instances: no LDS there)
   constexpr bool ZLDS = (RED & 2) != 0, LAZY = (RED & 4) != 0;
-  constexpr int NQ = EXTRA ? 10 : 9;
+  constexpr int NQ = EXTRA ? 10 : (ABS ? 11 : 9);
   if (ZLDS && threadIdx.x < 3) szero[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
   const uint32_t zaddr = (uint32_t)(uintptr_t)szero;   // LDS byte offset of the zero line
   int tile, seg_lo = 0, seg_hi = 0x7fffffff;   // SEG: the entries [seg_lo, seg_hi) of the tile's list are this wave's
@@ -755,6 +787,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
   if (c16 & 1) {
     if (c16 == 1) { qoff = 8; kscale = -0.5f; }                         // M2yy -> dcinv.z
     else if (EXTRA && c16 == 3) qoff = 9;                               // dz   -> the first pad slot
+    else if (ABS && c16 == 3) qoff = 10;                                // sum |t_x| -> the second pad slot
+    else if (ABS && c16 == 7) qoff = 11;                                // sum |t_y| -> the third
   }
   else if (c16 == 0) { qoff = 4; kind = 1; }                            // M1x  -> du.x
   else if (c16 == 2) { qoff = 5; kind = 2; }                            // M1y  -> du.y
@@ -837,6 +871,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
           acc[e][8] = 0.f;
         }
         if constexpr (EXTRA) acc[e][NQ - 1] = 0.f;
+        if constexpr (ABS) { acc[e][9] = 0.f; acc[e][10] = 0.f; }
         while (todo != 0ull) {
         const int j = 63 - __clzll((long long)todo);
         todo &= ~(1ull << j);
@@ -846,6 +881,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
         const float4 A = sA[j], B = sB[j], C = sC[j];
         float zj = 0.f;
         if constexpr (EXTRA) zj = sZ[j];
+        float4 Dj = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (ABS) Dj = sD[j];   // cinv of this entry
         bool inx[2] = {true, true}, iny[2] = {true, true};
         if (BOX) {
           const uint32_t bx = __float_as_uint(C.y), by = __float_as_uint(C.z);
@@ -907,6 +944,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
             const float wx = w * dx[bx], wy = w * dy[by];
             acc[e][4] += wx; acc[e][5] += wy;
             acc[e][6] += wx * dx[bx]; acc[e][7] += wx * dy[by]; acc[e][8] += wy * dy[by];
+            if constexpr (ABS) {   // |t_x|, |t_y| of this pixel (abs is a source modifier of the add)
+              acc[e][9] += fabsf(fmaf(Dj.x, wx, Dj.y * wy));
+              acc[e][10] += fabsf(fmaf(Dj.y, wx, Dj.z * wy));
+            }
             lq[k] += ap * dq;  // gamma_cur2last <- a' color + (1 - a') gamma_cur2last, dotted with dL/dgamma
             any_e = true;
           }
@@ -922,7 +963,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
         // quantity order chosen so that the two first moments meet in one quad (lanes 0 and 2):
         //   lane 0: M1x  2: M1y  4: dalpha  6,8,10: dcolor  12: M2xx  14: M2xy  odd: M2yy
         float rows[NQ];
-        constexpr int ORDER[10] = {4, 2, 0, 6, 5, 3, 1, 7, 8, 9};   // acc index feeding leaf q0..q8 (EXTRA: q9)
+        // acc index feeding leaf q0..q8 (EXTRA: q9; ABS: q9, q10)
+        constexpr int ORDER[11] = {4, 2, 0, 6, 5, 3, 1, 7, 8, 9, 10};
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
           rows[q] = rows_of4(acc[0][ORDER[q]], acc[1][ORDER[q]], acc[2][ORDER[q]], acc[3][ORDER[q]]);
@@ -959,6 +1001,15 @@ __global__ __launch_bounds__(256) void k_unpack_grads(int n, const float4* __res
   dcolor[3 * (size_t)i] = a.y; dcolor[3 * (size_t)i + 1] = a.z; dcolor[3 * (size_t)i + 2] = a.w;
   dus[2 * (size_t)i] = b.x; dus[2 * (size_t)i + 1] = b.y;
   dcinv[3 * (size_t)i] = b.z; dcinv[3 * (size_t)i + 1] = b.w; dcinv[3 * (size_t)i + 2] = c.x;
+}
+
+// slots 10 and 11 of the packed [N][12] gradient records (what the ABS draw instances left there) -> [N][2]
+__global__ __launch_bounds__(256) void k_records_absgrad(int n, const float4* __restrict__ gpack,
+                                                         float2* __restrict__ dus_abs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float4 c = gpack[3 * (size_t)i + 2];
+  dus_abs[i] = make_float2(c.z, c.w);
 }
 
 // ============================================================================
@@ -1047,7 +1098,7 @@ int launch_draw(const DrawParams& dp, const EgsPolicy* pol, int32_t* ranges, con
 // (EGS_DRAWB_RED is an A/B knob of the plain kernel)
 int launch_draw_bwd(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                     const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg, float* gpack,
-                    const DrawExtras* ex, hipStream_t s) {
+                    const DrawExtras* ex, hipStream_t s, bool absgrad) {
   // variants of the backward kernel (bit 0: in-row merges of the wave reduction with bank-masked DPP adds instead
   // of selects; bit 1: accumulator zeros loaded from LDS instead of moved; bit 2: exponent per evaluated block);
   // EGS_DRAWB_RED = 0 | 3 | 7 overrides
@@ -1059,6 +1110,12 @@ int launch_draw_bwd(const DrawParams& dp, const EgsPolicy* pol, const int32_t* r
                box, flr, clamp);
     EGS_LAUNCH_LDS("k_draw_bwd_extra", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), s, dp, ranges, gsid, rec,
                    final_tau, contrib, dLdg, gpack, DrawBwdFlavour<true>{*ex});
+  } else if (absgrad) {   // (the default reduction variant only, as EXTRA)
+    decltype(&k_draw_bwd<false, false, false, EGS_DRAWB_RED_DEFAULT, false, false, true>) kern = nullptr;
+    with_bools([&](auto b, auto f, auto c) { kern = k_draw_bwd<b.value, f.value, c.value, EGS_DRAWB_RED_DEFAULT, false, false, true>; },
+               box, flr, clamp);
+    EGS_LAUNCH_LDS("k_draw_bwd_abs", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), s, dp, ranges, gsid, rec,
+                   final_tau, contrib, dLdg, gpack, DrawBwdFlavour<false>{});
   } else {
     decltype(&k_draw_bwd<false, false, false, 0, false, false>) kern = nullptr;
     with_bools(
@@ -1077,8 +1134,16 @@ int launch_draw_bwd(const DrawParams& dp, const EgsPolicy* pol, const int32_t* r
 
 int launch_draw_bwd_seg(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                         const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg,
-                        float* gpack, const SegArgs& sga, int grid, hipStream_t s) {
+                        float* gpack, const SegArgs& sga, int grid, hipStream_t s, bool absgrad) {
   decltype(&k_draw_bwd<false, false, false, 7, true, false>) kern = nullptr;
+  if (absgrad) {
+    with_bools([&](auto flr, auto clamp) { kern = k_draw_bwd<false, flr.value, clamp.value, 7, true, false, true>; },
+               pol->maha_floor != 0, pol->alpha_clamp != 0);
+    EGS_LAUNCH("k_draw_bwd_seg_abs", kern, dim3(grid), dim3(64), s, dp, ranges, gsid, rec, final_tau, contrib, dLdg,
+               gpack, DrawBwdFlavour<false>{sga});
+    EGS_LAUNCH_OK();
+    return 0;
+  }
   with_bools([&](auto flr, auto clamp) { kern = k_draw_bwd<false, flr.value, clamp.value, 7, true, false>; },
              pol->maha_floor != 0, pol->alpha_clamp != 0);
   EGS_LAUNCH("k_draw_bwd_seg", kern, dim3(grid), dim3(64), s, dp, ranges, gsid, rec, final_tau, contrib, dLdg, gpack,
@@ -1095,6 +1160,18 @@ int unpack_grads(int n, const float* gpack, float* dus, float* dcinv, float* dal
 }
 
 }  // namespace egs
+
+extern "C" int egs_grad_records_absgrad(int n, const float* grad_records, float* dloss_dus_abs, void* stream) {
+  using namespace egs;
+  EGS_CHECK_ARG(n >= 0);
+  if (n == 0) return 0;
+  EGS_CHECK_ARG(grad_records && dloss_dus_abs);
+  EGS_CHECK_ARG((((uintptr_t)grad_records & 15) | ((uintptr_t)dloss_dus_abs & 7)) == 0);
+  EGS_LAUNCH("k_records_absgrad", k_records_absgrad, dim3(div_up(n, 256)), dim3(256), (hipStream_t)stream, n,
+             (const float4*)grad_records, (float2*)dloss_dus_abs);
+  EGS_LAUNCH_OK();
+  return 0;
+}
 
 // a caller-held tile_order buffer: [dispatch order of the forward draw | per-tile work it measured | walk (T ints each)]
 extern "C" size_t egs_tile_order_len(int width, int height) {

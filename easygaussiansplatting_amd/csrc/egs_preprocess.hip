@@ -1253,9 +1253,13 @@ extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width,
   // the render was anti-aliased: the chain rule takes the AA instances
   const bool aa = (phase & EGS_FUSED_ANTIALIASED) != 0;
   const bool raw = (phase & EGS_FUSED_RAW) != 0;
+  // the draw pass also sums |dL/du| per pixel into the records' slots 10 and 11 (the ABS instances of k_draw_bwd)
+  const bool absgrad = (phase & EGS_BWD_ABSGRAD) != 0;
   phase &= ~(EGS_BWD_KEEP_FORWARD_ORDER | EGS_BWD_ACCUMULATE | EGS_BWD_FACTORED_SH | EGS_FUSED_CULLED_LISTS |
-             EGS_FUSED_ANTIALIASED | EGS_FUSED_RAW);
+             EGS_FUSED_ANTIALIASED | EGS_FUSED_RAW | EGS_BWD_ABSGRAD);
   EGS_CHECK_ARG(phase >= 0 && phase <= 2);
+  // (the caller reads the records afterwards: they must be its own; no ABS + EXTRA instance of the draw kernel)
+  EGS_CHECK_ARG(!absgrad || ((grad_records || n == 0) && !extras));
   EGS_CHECK_ARG(raw || (!shs_high && !dloss_dshs_high));
   // pose (nullable): the camera gradient needs every row in one launch (k_pose_reduce sums all partial rows)
   if (pose) {
@@ -1285,7 +1289,8 @@ extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width,
   if (phase != 2) {
     int rc = splat_bwd_packed(n, patches, width, height, us, cinv2ds, alphas, colors, areas, pol, contrib, final_tau,
                               patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes, &gpack, stream, rec,
-                              tile_order, grad_records, keep_order, masked, seg_ws, seg_ws_bytes, 0, nullptr, extras);
+                              tile_order, grad_records, keep_order, masked, seg_ws, seg_ws_bytes, 0, nullptr, extras,
+                              absgrad);
     if (rc) return rc;
     if (phase == 1) return 0;
   }

@@ -169,13 +169,15 @@ int draw_segments_forward(DrawParams& dp, const EgsPolicy* pol, SegArgs& sga, co
 template <bool EXTRA> struct DrawBwdFlavour { SegArgs sg; };
 template <> struct DrawBwdFlavour<true> { DrawExtras ex; };
 // ex (nullable): the render extras -- the EXTRA instance of the kernel, launch label "k_draw_bwd_extra"
+// absgrad (never with ex): the ABS instance -- also sum |dL/du| per pixel into gpack[i][10..11]; launch labels
+// "k_draw_bwd_abs" / "k_draw_bwd_seg_abs"
 int launch_draw_bwd(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                     const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg, float* gpack,
-                    const DrawExtras* ex, hipStream_t s);
+                    const DrawExtras* ex, hipStream_t s, bool absgrad = false);
 // the same over the forward pass's work items (one wave per segment of a split tile)
 int launch_draw_bwd_seg(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                         const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg,
-                        float* gpack, const SegArgs& sga, int grid, hipStream_t s);
+                        float* gpack, const SegArgs& sga, int grid, hipStream_t s, bool absgrad = false);
 int unpack_grads(int n, const float* gpack, float* dus, float* dcinv, float* dalpha, float* dcolor, hipStream_t s);
 
 }  // namespace egs

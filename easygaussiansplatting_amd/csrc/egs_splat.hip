@@ -45,7 +45,7 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
                      const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
                      float** gpack_out, void* stream, const void* rec_in, const int32_t* tile_order,
                      float* grad_records, bool keep_forward_order, bool masked_lists, void* seg_ws,
-                     size_t seg_ws_bytes, int rebuild, uint32_t* seg_hint, const EgsExtras* extras) {
+                     size_t seg_ws_bytes, int rebuild, uint32_t* seg_hint, const EgsExtras* extras, bool absgrad) {
   // rebuild != 0 (with seg_ws of egs_seg_rebuild_ws_bytes): no forward pass left its segment states here -- the public
   // splatB is handed tensors only -- so they are REBUILT first: every tile's walk from `contrib`, then the forward
   // segment launches over [0, walk) with their pixels going to scratch.  seg_hint (nullable): the page-locked words
@@ -60,6 +60,7 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
   if (patches == 0) return 0;
   EGS_CHECK_ARG(contrib && final_tau && patch_range_per_tile && gsid_per_patch && dloss_dgammas);
   EGS_CHECK_ARG(!extras || (extras->depths && !seg_ws));   // (render extras: the unsplit kernels only)
+  EGS_CHECK_ARG(!(absgrad && extras));                     // (no ABS + EXTRA instance)
   EGS_CHECK_ARG(rec_in || (us && cinv2ds && alphas && colors && (areas || pol->footprint != 1)));
   EGS_CHECK_ARG(rec_in || (us && alphas && colors && (pol->footprint == 0 || areas)));
   DrawParams dp = make_draw_params(width, height, pol, true);
@@ -97,7 +98,7 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
       if (rc) return rc;
     }
     return launch_draw_bwd_seg(dp, pol, patch_range_per_tile, gsid_per_patch, rec, final_tau, contrib, dloss_dgammas,
-                               gpack, sga, grid, s);
+                               gpack, sga, grid, s, absgrad);
   }
   static const int by_work = [] { const char* e = getenv("EGS_DRAWB_BY_WORK"); return e ? atoi(e) : 1; }();
   const bool same_mode = tile_order_mode(0) == tile_order_mode(1) && tile_order_mode(1) > 0;
@@ -145,7 +146,7 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const float*
     for (int c = 0; c < 3; ++c) ex.bg[c] = extras->background[c];
   }
   return launch_draw_bwd(dp, pol, patch_range_per_tile, gsid_per_patch, rec, final_tau, contrib, dloss_dgammas, gpack,
-                         extras ? &ex : nullptr, s);
+                         extras ? &ex : nullptr, s, absgrad);
 }
 }  // namespace egs
 

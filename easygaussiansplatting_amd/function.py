@@ -62,6 +62,11 @@ class RenderOptions:
     # anti-aliased rendering (fused path only): the Mip-Splatting 2D filter -- the +0.3 px^2 dilation stays
     # and every Gaussian is drawn with opacity alpha sqrt(det(Sigma) / det(Sigma + 0.3 I)); differentiable
     antialiased: bool = False
+    # absolute screen-space gradients (fused path only; AbsGS, gsplat's ``absgrad``): after ``backward`` the
+    # ``us`` tensor handed to ``apply`` carries ``us.absgrad`` [N,2] = sum over pixels of |dL/du| of THIS view -- overwritten
+    # by each backward, never accumulated, a densification statistic and not a gradient.  Not with depth / alpha /
+    # background
+    absgrad: bool = False
 
     def __post_init__(self):
         if self.mode not in ("fused", "ops"):
@@ -83,6 +88,15 @@ class RenderOptions:
         if self.mode == "ops" and self.antialiased:
             raise ValueError("RenderOptions: antialiased needs mode='fused' (the seven-op structure mirrors the reference, "
                              "which has no opacity compensation)")
+        if not isinstance(self.absgrad, (bool, int)) or self.absgrad not in (0, 1):
+            raise ValueError("RenderOptions.absgrad must be a bool, got %r" % (self.absgrad,))
+        object.__setattr__(self, "absgrad", bool(self.absgrad))
+        if self.mode == "ops" and self.absgrad:
+            raise ValueError("RenderOptions: absgrad needs mode='fused' (the seven-op structure mirrors the reference, "
+                             "whose splatB returns the signed gradient only)")
+        if self.absgrad and self.has_extras():
+            raise ValueError("RenderOptions: absgrad does not combine with depth / alpha / background (the draw kernel "
+                             "has no instance for both)")
         if self.mode == "ops" and self.has_extras():
             raise ValueError("RenderOptions: depth / alpha / background need mode='fused' (the seven-op structure mirrors "
                              "the reference, which renders the image only)")
@@ -117,12 +131,19 @@ def _extra_grads(ctx, dloss_dgammas, rest):
     return dloss_dgammas, dd, da
 
 
-def _fused_forward(ctx, leaves, cam):
+def _fused_forward(ctx, leaves, cam, us=None):
     """The fused-path forward of a node (``ctx.opts`` set): renders ``leaves`` -- the node's Gaussian inputs in its
     argument order, (pws, shs, alphas, scales, rots) or the raw (pws, low_shs, high_shs, alphas_raw, scales_raw,
-    rots_raw) -- through ``cam``, saves them for ``_fused_backward`` and returns the node's outputs"""
+    rots_raw) -- through ``cam``, saves them for ``_fused_backward`` and returns the node's outputs.  ``us``: the
+    node's ``us`` input, on which ``RenderOptions.absgrad`` delivers its statistic"""
     o = ctx.opts
     ctx.extras = None if o is None else o.extras()
+    ctx.us_ref = None
+    if o is not None and o.absgrad:
+        if not isinstance(us, torch.Tensor):
+            raise ValueError("RenderOptions.absgrad needs a tensor as `us` (us.absgrad is where the statistic is left), "
+                             "got %s" % type(us).__name__)
+        ctx.us_ref = us
     pws, shs, *rest = leaves
     high_shs = rest.pop(0) if len(leaves) == 6 else None
     res = _fused.forward(pws, shs, *rest, cam, high_shs=high_shs, need_grad=True, extras=ctx.extras,
@@ -160,7 +181,9 @@ def _fused_backward(ctx, dloss_dgammas, rest, pose=False):
         pws, sh[0], *others, cam, ctx.state, dloss_dgammas.contiguous(), high_shs=sh[1] if len(sh) == 2 else None,
         accumulate=acc, sh_sink=sink, exchange=None if pose else (_fused.DEFAULT if o is None else o.exchange),
         dloss_ddepth=None if dd is None else dd.contiguous(), dloss_dalpha=None if da is None else da.contiguous(),
-        pose=(cam.Rcw, cam.tcw) if pose else None)
+        pose=(cam.Rcw, cam.tcw) if pose else None, absgrad=ctx.us_ref is not None)
+    if ctx.us_ref is not None:      # this view's statistic, overwritten by each backward (gsplat's means2d.absgrad)
+        ctx.us_ref.absgrad = res[-1]
     # acc: added to the leaves' .grad inside the kernel, nothing for autograd to accumulate
     grads = res[:k + 1] if acc is None else (None,) * k + (res[k],)
     tail = [None] * (ctx.n_inputs - k - 1)      # us's gradient is the last of `grads`; then Rcw, tcw, cam, opts
@@ -187,7 +210,7 @@ class GSFunction(torch.autograd.Function):
         # the mask output never carries a gradient: do not let autograd zero-fill one per step
         ctx.set_materialize_grads(False)
         if ctx.mode == "fused":
-            return _fused_forward(ctx, (pws, shs, alphas, scales, rots), cam)
+            return _fused_forward(ctx, (pws, shs, alphas, scales, rots), cam, us)
         # forward.md steps 1-5 == gsmodel.py:21-39
         us, pcs, depths, du_dpcs = gsc.project(pws, cam.Rcw, cam.tcw, cam.fx, cam.fy, cam.cx, cam.cy, True)
         cov3ds, dcov3d_drots, dcov3d_dscales = gsc.computeCov3D(rots, scales, depths, True)
@@ -247,7 +270,7 @@ class GSRawFunction(torch.autograd.Function):
         ctx.opts = opts            # (``mode`` does not apply: this node IS the fused path)
         ctx.n_inputs = 9     # (as GSFunction: the maximal tuple)
         ctx.set_materialize_grads(False)
-        return _fused_forward(ctx, (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw), cam)
+        return _fused_forward(ctx, (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw), cam, us)
 
     @staticmethod
     def backward(ctx, dloss_dgammas, _, *rest):
@@ -297,7 +320,7 @@ class GSPoseFunction(torch.autograd.Function):
     def forward(ctx, pws, shs, alphas, scales, rots, us, Rcw, tcw, cam, opts=None):
         pcam = _pose_setup(ctx, opts, Rcw, tcw, cam, pws)
         ctx.n_inputs = 10
-        return _fused_forward(ctx, (pws, shs, alphas, scales, rots), pcam)
+        return _fused_forward(ctx, (pws, shs, alphas, scales, rots), pcam, us)
 
     @staticmethod
     def backward(ctx, dloss_dgammas, _, *rest):
@@ -313,7 +336,7 @@ class GSRawPoseFunction(torch.autograd.Function):
     def forward(ctx, pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw, us, Rcw, tcw, cam, opts=None):
         pcam = _pose_setup(ctx, opts, Rcw, tcw, cam, pws)
         ctx.n_inputs = 11
-        return _fused_forward(ctx, (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw), pcam)
+        return _fused_forward(ctx, (pws, low_shs, high_shs, alphas_raw, scales_raw, rots_raw), pcam, us)
 
     @staticmethod
     def backward(ctx, dloss_dgammas, _, *rest):

@@ -50,6 +50,7 @@ SEG_SPECULATE_FLAG = 8    # include/egs_hip.h EGS_DRAW_SEG_SPECULATE
 SEG_SPECULATE = os.environ.get("EGS_SEG_SPECULATE", "auto")
 ACCUMULATE = 64           # include/egs_hip.h EGS_BWD_ACCUMULATE
 FACTORED_SH = 128         # include/egs_hip.h EGS_BWD_FACTORED_SH
+ABSGRAD = 1024            # include/egs_hip.h EGS_BWD_ABSGRAD
 # the render's flags (FusedState.flags): egs_fused_forward's `flags`, OR-ed into every egs_fused_backward phase
 CULLED_LISTS = 32         # include/egs_hip.h EGS_FUSED_CULLED_LISTS
 ANTIALIASED = 256         # include/egs_hip.h EGS_FUSED_ANTIALIASED
@@ -398,7 +399,7 @@ def accumulation_targets(leaves, node_ctx=None, count=None, explicit=None):
 
 
 def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, high_shs=None, accumulate=None,
-             sh_sink=None, exchange=DEFAULT, dloss_ddepth=None, dloss_dalpha=None, pose=None):
+             sh_sink=None, exchange=DEFAULT, dloss_ddepth=None, dloss_dalpha=None, pose=None, absgrad=False):
     """-> (dloss_dpws[N,3], dloss_dshs[N,K], dloss_dalphas[N,1], dloss_dscales[N,3],
            dloss_drots[N,4], dloss_dus[N,2])  -- the gradient tuple of gsmodel.py:87-93.
     With ``high_shs`` (raw tensors, see ``forward``): -> (dpws, dlow_shs[N,3], dhigh_shs[N,K-3],
@@ -413,7 +414,10 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     ``pose`` = (Rcw [3,3], tcw [3]), float32 on the device: the camera of the forward call (``cam.twc`` must be
     -Rcw^T tcw), whose gradient is also formed -> the usual tuple followed by (dloss_dRcw [3,3], dloss_dtcw [3]).  The
     pose gradient belongs to this view: always written, never added to ``accumulate``.  Excludes ``exchange``.
-    An anti-aliased render (``forward(..., antialiased=True)``, recorded in ``S.flags``) takes the AA chain rule."""
+    An anti-aliased render (``forward(..., antialiased=True)``, recorded in ``S.flags``) takes the AA chain rule.
+    ``absgrad``: the draw pass also sums the ABSOLUTE per-pixel terms of dloss_dus (``EGS_BWD_ABSGRAD``, DESIGN §3.10:
+    AbsGS / gsplat's ``absgrad``) and ``dloss_dus_abs`` [N,2] -- this view's, never accumulated, a statistic and not a
+    gradient -- is appended to the result.  Not for a render with extras."""
     raw = high_shs is not None
     pws = _chk(pws, "pws", torch.float32, (None, 3))
     n = pws.shape[0]
@@ -438,6 +442,8 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
         ex = _egs_extras(S.depths, rx.background_rgb(), dloss_ddepth=dd, dloss_dalpha=da)
     elif dloss_ddepth is not None or dloss_dalpha is not None:
         raise ValueError("fused.backward: depth / alpha gradients for a render without extras")
+    if absgrad and rx is not None:
+        raise ValueError("fused.backward: absgrad is not available for a render with extras (depth / alpha / background)")
     lib = _lib_on(pws)
     dev = pws.device
     f32 = torch.float32
@@ -497,6 +503,11 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     st = _stream()
     gpack, S.gpack = S.gpack, None      # zeroed by the forward draw kernel: good for ONE backward pass
+    dus_abs = None
+    if absgrad:
+        dus_abs = torch.empty((n, 2), dtype=f32, device=dev)
+        if gpack is None and n > 0:     # (the records are read back below: they must be the caller's)
+            gpack = torch.zeros((n, 12), dtype=f32, device=dev)
     seg = getattr(S, "seg", None)       # the forward pass split its long lists: the backward pass walks its segments
     seg_bytes = seg.numel() if seg is not None else 0
     # every phase and chunk carries the render's flags (culled lists, anti-aliased, raw inputs) from the forward's state
@@ -514,6 +525,8 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
         keep |= ACCUMULATE            # the outputs hold earlier views' gradients: add to them
     if sh_sink is not None:
         keep |= FACTORED_SH
+    if absgrad:
+        keep |= ABSGRAD               # (a bit of the draw pass: phases 0 and 1)
     if hook is not None and sh_sink is not None:
         raise RuntimeError("fused.backward: sh_sink and an attached ChunkedExchange exclude each other")
     chunks = hook.chunks if hook is not None else 1
@@ -535,6 +548,9 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
             launch(2 | (keep & (ACCUMULATE | FACTORED_SH)), b, c)
             hook.on_chunk([p[b:b + c] for p in parts])
     tail = () if pg is None else (dRcw, dtcw)
+    if absgrad:
+        _lib.check(lib.egs_grad_records_absgrad(n, _ptr(gpack), _ptr(dus_abs), st))
+        tail = tail + (dus_abs,)
     if sh_sink is not None:
         return ((dpws, None, None, dalphas, dscales, drots, dus) if raw else (dpws, None, dalphas, dscales, drots, dus)) \
             + tail

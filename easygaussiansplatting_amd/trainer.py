@@ -77,7 +77,7 @@ class Trainer:
     def __init__(self, scene, cameras: Sequence, gt_images: Sequence[torch.Tensor], max_steps: int,
                  scene_size: float = 1.0, device="cuda", fused_adam: bool = True, seed: int = 0,
                  fused_activations: bool = True, view_streams: int = 4, factored_sh: bool = True, mode: str = "fused",
-                 antialiased: bool = False):
+                 antialiased: bool = False, absgrad: bool = False, grad_threshold: float = None):
         self.device = device
         # how THIS trainer's renders are evaluated (function.RenderOptions.mode; "ops" needs fused_activations=False):
         # carried by every call, never by a process-wide switch -- two trainers in one process may differ
@@ -86,7 +86,12 @@ class Trainer:
             raise ValueError("Trainer(mode=%r) needs fused_activations=False (GSRawFunction is the fused path)" % (mode,))
         # anti-aliased training (RenderOptions.antialiased; fused path only): every render of a step
         self.antialiased = bool(antialiased)
-        RenderOptions(mode=mode, antialiased=self.antialiased)        # (raises ValueError for mode="ops")
+        # densify on the ABSOLUTE screen-space gradient (RenderOptions.absgrad; fused path only): the
+        # statistic gathered per step is ||sum over pixels |dL/du| || instead of ||dL/du||, in which the pulls of
+        # different pixels on a large Gaussian cannot cancel.  It is larger than the signed one (DESIGN §3.10 has the
+        # measured ratio): set ``grad_threshold`` with it -- None keeps DensityControl's (the reference's 4e-7)
+        self.absgrad = bool(absgrad)
+        RenderOptions(mode=mode, antialiased=self.antialiased, absgrad=self.absgrad)   # (raises ValueError for mode="ops")
         # a rank's views of a step go round-robin to this many HIP streams (dist_views.ViewStreams); 1 = one after
         # the other on the caller's stream
         self.view_streams = max(1, int(view_streams))
@@ -100,6 +105,8 @@ class Trainer:
         self.params = raw_params_from_scene(scene, device)
         self.opt = make_optimizer(self.params, fused_adam)
         self.density = DensityControl(scene_size, max_steps, seed)
+        if grad_threshold is not None:
+            self.density.grad_threshold = float(grad_threshold)
         self.cams = [c if isinstance(c, Camera) else Camera.from_scene(c, device) for c in cameras]
         self.gts = list(gt_images)
         self.max_steps = max_steps
@@ -158,7 +165,7 @@ class Trainer:
                 image.backward(dimage)
                 loss_sum[k] += stats[0]
                 with torch.no_grad():                       # per-view ||dL/du|| (undo the 1/len scaling)
-                    g = torch.norm(us.grad * n_views, dim=-1)
+                    g = torch.norm((us.absgrad if self.absgrad else us.grad) * n_views, dim=-1)
                     gnorm[k] += torch.where(mask, g, torch.zeros_like(g))
                     count[k] += mask.to(torch.int32)
         if vs is not None:
@@ -201,7 +208,8 @@ class Trainer:
             fx = self._fx
         # every render of the step carries its own options (no process-wide switch): gradients of further views are
         # added inside the chain-rule kernel, the SH gradient goes to this trainer's own FactoredShGrad
-        opts = RenderOptions(mode=self.mode, accumulate=True, sh_sink=fx, antialiased=self.antialiased)
+        opts = RenderOptions(mode=self.mode, accumulate=True, sh_sink=fx, antialiased=self.antialiased,
+                             absgrad=self.absgrad)
         if fx is not None:     # (rows allocated here, on the caller's stream, before the views fork onto their lanes)
             fx.begin_step(self.params["pws"].shape[0], self.params["pws"].device)
         with _fused.deferred() as d:

@@ -25,6 +25,11 @@ def main():
     ap.add_argument("--out", default="data")
     ap.add_argument("--antialiased", action="store_true",
                     help="anti-aliased rendering: opacity compensation of the 2D filter (DESIGN §3.9)")
+    ap.add_argument("--absgrad", action="store_true",
+                    help="densify on the absolute screen-space gradient (AbsGS, DESIGN §3.10); the statistic is larger "
+                         "than the signed one: set --grad-threshold with it")
+    ap.add_argument("--grad-threshold", type=float, default=None,
+                    help="densification threshold on the accumulated screen-space gradient norm (default: 4e-7)")
     a = ap.parse_args()
 
     import torch
@@ -46,7 +51,8 @@ def main():
                     None)
     views_per_step = world
     steps = (len(ds) // views_per_step) * a.epochs
-    tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size, antialiased=a.antialiased)
+    tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size, antialiased=a.antialiased,
+                 absgrad=a.absgrad, grad_threshold=a.grad_threshold)
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]

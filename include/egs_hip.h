@@ -471,6 +471,20 @@ size_t egs_fused_backward_ws_bytes(int n);
  * a data-parallel host all-gathers 12 bytes per Gaussian and VIEW instead of all-reducing 4 sh_dim per Gaussian
  * (192 of the 236 bytes of SURVEY 8e's exchange at degree 3). */
 #define EGS_BWD_FACTORED_SH 128
+/* OR-ed into `phase` of egs_fused_backward: absolute screen-space gradients (AbsGS; gsplat's absgrad).  The draw pass
+ * (phase 0 or 1) also forms, per Gaussian g,
+ *     dloss_dus_abs[g] = sum over every pixel p of every tile that blends g of (|t_x|, |t_y|),
+ *     t = dL/dalpha'(p) alpha'(p) (-cinv (u_g - p))        (the per-pixel term whose signed sum is dloss_dus[g])
+ * -- per view, not normalised, carrying the scale of dloss_dgammas -- in slots 10 and 11 of the packed gradient records
+ * ([N][12] floats: 0 dalpha, 1-3 dcolor, 4-5 du, 6-8 dcinv, 9 dz of render extras, 10-11 this); read them back with
+ * egs_grad_records_absgrad.  A densification statistic, not a gradient: the chain rule never reads it and every other
+ * output is what it is without the bit.  Needs grad_records != NULL (the caller reads them afterwards) and
+ * extras == NULL (EGS_ERR_BAD_ARG otherwise); composes with every EGS_FUSED_* bit, pose, EGS_BWD_ACCUMULATE,
+ * EGS_BWD_FACTORED_SH, the segment workspace and the chunked phases.  Without the bit the two slots stay zero. */
+#define EGS_BWD_ABSGRAD 1024
+/* dloss_dus_abs[i] = grad_records[i][10..11] for all n records, after an egs_fused_backward with EGS_BWD_ABSGRAD
+ * (zeros for a Gaussian no tile lists).  dloss_dus_abs: [N][2] floats, 8-B aligned. */
+int egs_grad_records_absgrad(int n, const float* grad_records, float* dloss_dus_abs /*[N][2]*/, void* stream);
 /* flags of egs_splat_draw_rec*: the lists are the footprint-culled ones of EGS_FUSED_CULLED_LISTS */
 #define EGS_DRAW_CULLED_LISTS 1
 /* flags of egs_splat_draw_rec* / egs_splat_bwd_rec_lists: the lists are the REFERENCE's complete lists (every tile of

@@ -68,7 +68,8 @@ def dump(out_path, sources=None):
 
 
 # A kernel flavour used to be a kernel NAME (k_draw_extra<..>), now it is a template argument (k_draw<.., true>):
-# old flavour name -> (folded name, template arguments it had, template arguments the fold appends)
+# old flavour name -> (folded name, template arguments it had, template arguments the fold appends).  A kernel that
+# gained a trailing template argument later has one more rule in FOLDED_AGAIN, applied to the name the first gave.
 FOLDED = {
     "k_preprocess_fwd": ("k_preprocess_fwd", 3, ["false"]),                         # <NC, RAW, JW> + AA
     "k_preprocess_fwd_aa": ("k_preprocess_fwd", 3, ["true"]),
@@ -82,6 +83,9 @@ FOLDED = {
     "k_draw_extra": ("k_draw", 4, ["true"]),
     "k_draw_bwd": ("k_draw_bwd", 5, ["false"]),                                     # <BOX, FLOOR, CLAMP, RED, SEG> + EXTRA
     "k_draw_bwd_extra": ("k_draw_bwd", 4, ["false", "true"]),                       # <BOX, FLOOR, CLAMP, RED>
+}
+FOLDED_AGAIN = {
+    "k_draw_bwd": (6, ["false"]),                                    # <BOX, FLOOR, CLAMP, RED, SEG, EXTRA> + ABS
 }
 
 
@@ -97,6 +101,8 @@ def canonical(name):
     new_base, arity, appended = FOLDED[base]
     if len(args) == arity:
         base, args = new_base, args + appended
+    if base in FOLDED_AGAIN and len(args) == FOLDED_AGAIN[base][0]:
+        args = args + FOLDED_AGAIN[base][1]
     return "%s<%s>" % (base, ", ".join(args))
 
 
@@ -110,13 +116,13 @@ def load(path):
 
 def diff(a, b):
     A, B = load(a), load(b)
-    bad = 0
+    bad = added = 0
     for k in sorted(set(A) | set(B)):
-        if k not in A: print("only in b:", k); bad += 1
+        if k not in A: print("only in b:", k); added += 1     # (a feature adds kernels: reported, not an error)
         elif k not in B: print("only in a:", k); bad += 1
         elif A[k]["sha1"] != B[k]["sha1"]:
             print("DIFFERENT (%d vs %d lines): %s" % (A[k]["lines"], B[k]["lines"], k)); bad += 1
-    print("%d kernels compared, %d differ" % (len(set(A) | set(B)), bad))
+    print("%d kernels compared, %d differ, %d only in b" % (len(set(A) & set(B)), bad, added))
     return 1 if bad else 0
 
 

@@ -25,8 +25,10 @@ src, sq, ub, dst = sys.argv[1:5]
 mix = json.load(open(sys.argv[5])) if len(sys.argv) > 5 else {}
 # (mangled template-argument lists of the training instances, EXTRA = false included; matched against the symbol
 # valu_mix.py recorded)
-MIX_OF = {"k_draw_bwd": "k_draw_bwdILb0ELb1ELb1ELi7ELb0ELb0EE", "k_draw": "k_drawILb0ELb1ELb1ELb1ELb0EE",
-          "k_draw_bwd_seg": "k_draw_bwdILb0ELb1ELb1ELi7ELb1ELb0EE", "k_draw_seg": "k_draw_segILb1ELb1ELi0EE"}
+MIX_OF = {"k_draw_bwd": "k_draw_bwdILb0ELb1ELb1ELi7ELb0ELb0ELb0EE", "k_draw": "k_drawILb0ELb1ELb1ELb1ELb0EE",
+          "k_draw_bwd_seg": "k_draw_bwdILb0ELb1ELb1ELi7ELb1ELb0ELb0EE", "k_draw_seg": "k_draw_segILb1ELb1ELi0EE",
+          "k_draw_bwd_abs": "k_draw_bwdILb0ELb1ELb1ELi7ELb0ELb0ELb1EE",
+          "k_draw_bwd_seg_abs": "k_draw_bwdILb0ELb1ELb1ELi7ELb1ELb0ELb1EE"}
 
 
 def kname(k):
@@ -39,8 +41,8 @@ def kname(k):
         return {"0": "k_draw_seg", "1": "k_draw_seg_fix", "2": "k_draw_seg_compose"}.get(args[-1], base)
     if base == "k_draw":               # <BOX, FLOOR, CLAMP, SKIP, EXTRA>
         return "k_draw_extra" if on(4) else base
-    if base == "k_draw_bwd":           # <BOX, FLOOR, CLAMP, RED, SEG, EXTRA>
-        return "k_draw_bwd_seg" if on(4) else "k_draw_bwd_extra" if on(5) else base
+    if base == "k_draw_bwd":           # <BOX, FLOOR, CLAMP, RED, SEG, EXTRA, ABS>
+        return ("k_draw_bwd_seg" if on(4) else "k_draw_bwd_extra" if on(5) else base) + ("_abs" if on(6) else "")
     if base == "k_preprocess_fwd":     # <NC, RAW, JW, AA>
         return "k_preprocess_fwd_aa" if on(3) else base
     if base == "k_preprocess_bwd":     # <NC, RAW, JW, EXTRA, POSE, AA>: labelled AA over POSE over EXTRA
