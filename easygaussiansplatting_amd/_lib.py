@@ -13,7 +13,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libegs_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class EgsPolicy(C.Structure):
@@ -73,21 +73,13 @@ SIGNATURES = {
     "egs_splat_bin": (_i, [_i, _i, _i, _P, _P, _P, _PP, _i, _P, _sz, _P, _P]),
     "egs_splat_draw": (_i, [_i, _i64, _i, _i, _P, _P, _P, _P, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P]),
     "egs_splat_bin_mb": (_i, [_i, _i, _i, _P, _P, _P, _PP, _i, _P, _sz, _P, _P, _P]),
-    "egs_splat_draw_dev": (_i, [_i, _i64, _P, _i, _i, _P, _P, _P, _P, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P]),
     "egs_splat_bwd_ws_bytes": (_sz, [_i]),
     "egs_splat_bwd": (_i, [_i, _i64, _i, _i, _P, _P, _P, _P, _P, _PP, _P, _P, _P, _P, _P, _P, _sz,
                            _P, _P, _P, _P, _P]),
     "egs_pack_records": (_i, [_i, _i, _i, _P, _P, _P, _P, _P, _PP, _P, _P]),
-    "egs_splat_bwd_rec": (_i, [_i, _i64, _i, _i, _P, _PP, _P, _P, _P, _P, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P]),
-    "egs_splat_bwd_rec_lists": (_i, [_i, _i64, _i, _i, _P, _PP, _P, _P, _P, _P, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _i,
-                                     _P]),
     "egs_splat_bin_pack": (_i, [_i, _i, _i, _P, _P, _P, _P, _P, _P, _PP, _i, _P, _sz, _P, _P, _P, _P, _P, _P]),
-    "egs_splat_draw_rec_plain": (_i, [_i, _i64, _i, _i, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P]),
-    "egs_splat_draw_rec_dev_plain": (_i, [_i, _i64, _P, _i, _i, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P, _P, _i,
-                                          _P]),
     "egs_pair_stamp_words": (_sz, [_i]),
     "egs_pack_records_validate": (_i, [_i, _i, _i, _P, _P, _P, _P, _PP, _P, _P, _P, _i64, _P, _P, _P]),
-    "egs_strip_list_masks": (_i, [_i64, _P, _P, _P, _P]),
     "egs_sort_pairs_ws_bytes": (_sz, [_i64]),
     "egs_sort_pairs": (_i, [_i64, _P, _P, _P, _P, _i, _i, _P, _sz, C.POINTER(C.c_int), _P]),
     "egs_scan_ws_bytes": (_sz, [_i64]),
@@ -107,9 +99,6 @@ SIGNATURES = {
     "egs_mailbox_clear": (_i, [_P, _i]),
     "egs_sh_grad_views": (_i, [_i, _i, _i, _P, _P, _i64, _f, _P, _P, _i, _P]),
     "egs_tile_order_len": (_sz, [_i, _i]),
-    "egs_splat_draw_rec": (_i, [_i, _i64, _i, _i, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P]),
-    "egs_splat_draw_rec_dev": (_i, [_i, _i64, _P, _P, _i, _i, _P, _PP, _P, _P, _sz, _P, _P, _P, _P, _P, _P, _P, _P,
-                                    _i, _i, _P]),
     "egs_hbm_copy_probe": (_i, [_P, _P, _sz, _P]),
     "egs_clock_probe": (_i, [_P, _i, _P]),
     "egs_mailbox_create": (_P, [_i]),

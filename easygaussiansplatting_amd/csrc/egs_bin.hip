@@ -369,7 +369,7 @@ __global__ __launch_bounds__(256) void k_bin_emit(int n, int gx, const uint32_t*
     } else {                                        // big cullable rect: emitted row by row by its wave, below
       continue;
     }
-    if (first + s0 >= cap) break;   // (only when the buffers were sized from an earlier call: see egs_splat_draw_rec_dev)
+    if (first + s0 >= cap) break;   // (only when the buffers were sized from an earlier call: see total_patches of egs_splat_draw_rec_seg)
     tkeys[first + s0] = tile;
     gsid[first + s0] = with_masks ? (s_g[lo] | (mask << EGS_GSID_BITS)) : s_g[lo];
   }
@@ -441,7 +441,7 @@ __global__ __launch_bounds__(256) void k_tile_ranges(int64_t P, const uint32_t* 
   }
   // masked / plain (nullable pair, seven-op surface): gsid_per_patch as the reference returns it -- the sorted list
   // values without their block masks -- written on the way (this kernel is a chain of latencies: the 8 bytes per
-  // patch ride along; as a launch of its own, k_strip_masks, they cost 6-8 us)
+  // patch ride along; as a launch of their own they cost 6-8 us)
   if (n_dev) P = min(P, (int64_t)*n_dev);
   const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;   // four keys per thread: one dwordx4
   if (p0 >= P) return;
@@ -475,21 +475,6 @@ __global__ __launch_bounds__(256) void k_tile_ranges(int64_t P, const uint32_t* 
       }
       if (p == P - 1) ranges[2 * (size_t)cur + 1] = (int32_t)P;
     }
-  }
-}
-
-// gsid_per_patch as the reference returns it: the list values without their block masks
-__global__ __launch_bounds__(256) void k_strip_masks(int64_t P, const uint32_t* __restrict__ n_dev,
-                                                     const uint32_t* __restrict__ masked, int32_t* __restrict__ plain) {
-  if (n_dev) P = min(P, (int64_t)*n_dev);
-  const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (p0 >= P) return;
-  if (p0 + 4 <= P) {
-    uint4 v = *reinterpret_cast<const uint4*>(masked + p0);
-    v.x &= EGS_GSID_MASK; v.y &= EGS_GSID_MASK; v.z &= EGS_GSID_MASK; v.w &= EGS_GSID_MASK;
-    *reinterpret_cast<uint4*>(plain + p0) = v;
-  } else {
-    for (int64_t q = p0; q < P; ++q) plain[q] = (int32_t)(masked[q] & EGS_GSID_MASK);
   }
 }
 
@@ -654,7 +639,7 @@ extern "C" int egs_splat_bin_mb(int n, int width, int height, const float* us, i
 }
 
 // egs_pack_records + egs_splat_bin(_mb) in one pass over the 2D Gaussians (k_pack_bin), tile-footprint policies with a
-// skip threshold only: the lists that egs_splat_draw_rec* then emits (flags = EGS_DRAW_MASKED_LISTS) are the
+// skip threshold only: the lists that egs_splat_draw_rec_seg then emits (flags = EGS_DRAW_MASKED_LISTS) are the
 // reference's, their values carry exact block masks.
 extern "C" int egs_splat_bin_pack(int n, int width, int height, const float* us, const float* cinv2ds,
                                   const float* alphas, const float* colors, int32_t* areas, float* depths,
@@ -686,18 +671,6 @@ extern "C" int egs_splat_bin_pack(int n, int width, int height, const float* us,
              (uint32_t)L.sort.sup_words, stamp, visible);
   EGS_LAUNCH_OK();
   return splat_bin_after_count(n, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, stream, host_totals);
-}
-
-// plain[i] = masked[i] & EGS_GSID_MASK for the first min(count, *count_dev) list values (count_dev nullable)
-extern "C" int egs_strip_list_masks(int64_t count, const uint32_t* count_dev, const void* masked, int32_t* plain,
-                                    void* stream) {
-  EGS_CHECK_ARG(count >= 0);
-  if (count == 0) return 0;
-  EGS_CHECK_ARG(masked && plain && (((uintptr_t)masked | (uintptr_t)plain) & 15) == 0);
-  EGS_LAUNCH("k_strip_masks", k_strip_masks, dim3(div_up(count, 1024)), dim3(256), (hipStream_t)stream, count,
-             count_dev, (const uint32_t*)masked, plain);
-  EGS_LAUNCH_OK();
-  return 0;
 }
 
 static int splat_bin_impl(int n, int width, int height, const float* us, int32_t* areas, float* depths,
@@ -778,7 +751,7 @@ int splat_bin_after_count(int n, int key_bits_hint, void* ws_bin, size_t ws_bin_
 }  // namespace egs
 
 // The packed 2D records of the draw kernels as a caller-held buffer: gsplatcu.splat packs them ONCE, draws from them
-// (egs_splat_draw_rec*) and keeps them for the splatB call that follows with the same tensors (egs_splat_bwd_rec) --
+// (egs_splat_draw_rec_seg) and keeps them for the splatB call that follows with the same tensors (egs_splat_bwd_seg) --
 // the seven-op surface otherwise packs twice per training step (2 x 20 us at 1 M Gaussians).
 extern "C" int egs_pack_records(int n, int width, int height, const float* us, const float* cinv2ds,
                                 const float* alphas, const float* colors, const int32_t* areas, const EgsPolicy* pol,

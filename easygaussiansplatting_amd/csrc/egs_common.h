@@ -169,22 +169,42 @@ bool bin_count_outputs(void* ws_bin, size_t ws_bin_bytes, int n, BinCountOut* ou
 int splat_bin_after_count(int n, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes, uint32_t* total_patches,
                           void* stream, uint32_t* host_totals);
 
-// splatB's draw pass into the packed [N][12] gradient records (egs_splat.hip); *gpack
-// points into `ws`.  Shared by egs_splat_bwd (+unpack) and egs_fused_backward.
-int splat_bwd_packed(int n, int64_t patches, int width, int height, const float* us, const float* cinv2ds,
-                     const float* alphas, const float* colors, const int32_t* areas, const EgsPolicy* pol,
-                     const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
-                     const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
-                     float** gpack, void* stream, const void* rec_in /* packed records or NULL */,
-                     const int32_t* tile_order /* dispatch order left by the forward pass, or NULL */,
-                     float* grad_records /* [N][12] records ALREADY ZEROED (by the forward draw kernel), or NULL */,
-                     bool keep_forward_order = false /* dispatch the tiles exactly as tile_order says */,
-                     bool masked_lists = false /* gsid_per_patch carries block masks (culled lists, fused path) */,
-                     void* seg_ws = nullptr /* the segment workspace the forward draw filled (egs_splat_draw_rec_seg) */,
-                     size_t seg_ws_bytes = 0, int rebuild = 0 /* seg_ws is fresh: rebuild the states from contrib first */,
-                     uint32_t* seg_hint = nullptr /* page-locked words that learn the longest walk */,
-                     const EgsExtras* extras = nullptr /* render extras: the EXTRA draw kernel (unsplit lists only) */,
-                     bool absgrad = false /* the ABS draw kernels: sum |dL/du| per pixel into gpack[i][10..11] */);
+// ---- the arguments of the splat stage (egs_splat.hip), grouped by what travels together ----------------------------
+// The 2D Gaussians of a draw / backward draw: the packed 48-B records, or the tensors they are packed from.
+struct SplatSource {
+  const void* rec;       // [N][12] packed records (egs_pack_records / egs_fused_forward); NULL: packed from the tensors
+  const float *us, *cinv2ds, *alphas, *colors;   // the op surface's tensors (needed when rec == NULL)
+  const int32_t* areas;  // pixel boxes: the pixel-box policy packs from them (always, for the literal egs_splat_draw)
+};
+// What the forward draw wrote and the backward draw reads (required whenever there are patches).
+struct SplatForward {
+  const int32_t* contrib;
+  const float* final_tau;
+  const int32_t* ranges;   // patch_range_per_tile [T][2]
+  const int32_t* gsid;     // gsid_per_patch [P]; with masked_lists: the list WITH block masks the forward draw walked
+};
+// What a host may have carried over from the forward pass to splat_bwd_packed; every field may be 0 / NULL.
+struct SplatCarry {
+  const int32_t* tile_order;   // the [order | work | walk] buffer the forward draw left: no pass over `contrib`
+  float* grad_records;         // [N][12] records ALREADY ZEROED (by the forward draw kernel); NULL: a piece of ws
+  bool keep_forward_order;     // dispatch the tiles exactly as tile_order says (EGS_BWD_KEEP_FORWARD_ORDER)
+  bool masked_lists;           // gsid carries block masks (culled lists of the fused path, EGS_DRAW_MASKED_LISTS)
+  void* seg_ws;                // the segment workspace the forward draw filled (egs_splat_draw_rec_seg), or, with
+  size_t seg_ws_bytes;         // rebuild, a fresh one of egs_seg_rebuild_ws_bytes
+  int rebuild;                 // != 0: no forward pass left its segment states in seg_ws -- the public splatB is handed
+                               // tensors only -- so they are REBUILT first: every tile's walk from `contrib`, then the
+                               // forward segment launches over [0, walk) with their pixels going to scratch
+  uint32_t* seg_hint;          // page-locked words that learn the longest walk (both paths report it: a host decides
+                               // the path of its NEXT call from it)
+  const EgsExtras* extras;     // render extras: the EXTRA draw kernel (unsplit lists only)
+  bool absgrad;                // the ABS draw kernels: sum |dL/du| per pixel into gpack[i][10..11]
+};
+// splatB's draw pass into the packed [N][12] gradient records (egs_splat.hip); *gpack is carry.grad_records or points
+// into `ws` (egs_splat_bwd_ws_bytes(n), checked by the caller).  Shared by egs_splat_bwd / _seg (+unpack) and
+// egs_fused_backward.
+int splat_bwd_packed(int n, int64_t patches, int width, int height, const EgsPolicy* pol, const SplatSource& src,
+                     const SplatForward& fwd, const float* dloss_dgammas, void* ws, const SplatCarry& carry,
+                     float** gpack, void* stream);
 
 // ---- device helpers ---------------------------------------------------------
 #ifdef __HIPCC__

@@ -1287,10 +1287,15 @@ extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width,
   // where splat_bwd_packed puts the records
   float* gpack = grad_records ? grad_records : (float*)((char*)ws + align_up((size_t)n * 48, 256));
   if (phase != 2) {
-    int rc = splat_bwd_packed(n, patches, width, height, us, cinv2ds, alphas, colors, areas, pol, contrib, final_tau,
-                              patch_range_per_tile, gsid_per_patch, dloss_dgammas, ws, ws_bytes, &gpack, stream, rec,
-                              tile_order, grad_records, keep_order, masked, seg_ws, seg_ws_bytes, 0, nullptr, extras,
-                              absgrad);
+    // (the forward's own segment workspace, never a rebuild; no hint words: the forward draw reports the walks)
+    int rc = splat_bwd_packed(
+        n, patches, width, height, pol,
+        {.rec = rec, .us = us, .cinv2ds = cinv2ds, .alphas = alphas, .colors = colors, .areas = areas},
+        {.contrib = contrib, .final_tau = final_tau, .ranges = patch_range_per_tile, .gsid = gsid_per_patch},
+        dloss_dgammas, ws,
+        {.tile_order = tile_order, .grad_records = grad_records, .keep_forward_order = keep_order, .masked_lists = masked,
+         .seg_ws = seg_ws, .seg_ws_bytes = seg_ws_bytes, .extras = extras, .absgrad = absgrad},
+        &gpack, stream);
     if (rc) return rc;
     if (phase == 1) return 0;
   }

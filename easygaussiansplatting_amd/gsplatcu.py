@@ -426,12 +426,9 @@ def _splat(height, width, us, cinv2ds, alphas, depths, colors, areas, keep):
             _lib.check(lib.egs_splat_bin_pack(n, width, height, _ptr(us), _ptr(cinv2ds), _ptr(alphas), _ptr(colors),
                                               _ptr(areas), _ptr(depths), pol, hint, _ptr(ws_bin), ws_bin_bytes,
                                               _ptr(total), host_slot, _ptr(rec), _ptr(stamp), _ptr(visible), st))
-        elif host_slot is not None:
+        else:       # (host_slot None: exactly egs_splat_bin)
             _lib.check(lib.egs_splat_bin_mb(n, width, height, _ptr(us), _ptr(areas), _ptr(depths), pol, hint,
                                             _ptr(ws_bin), ws_bin_bytes, _ptr(total), host_slot, st))
-        else:
-            _lib.check(lib.egs_splat_bin(n, width, height, _ptr(us), _ptr(areas), _ptr(depths), pol, hint,
-                                         _ptr(ws_bin), ws_bin_bytes, _ptr(total), st))
 
     def draw(rows, total, redo):
         # buffers for ``rows`` patches, the count from the device words ``total`` if given; ``redo``: see _ahead.render

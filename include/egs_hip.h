@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define EGS_ABI_VERSION 11
+#define EGS_ABI_VERSION 12
 
 #define EGS_ERR_BAD_ARG 10001
 #define EGS_ERR_WORKSPACE 10002
@@ -139,32 +139,41 @@ int egs_splat_draw(int n, int64_t patches, int width, int height, const float* u
                    float* image, int32_t* contrib, float* final_tau, int32_t* patch_range_per_tile,
                    int32_t* gsid_per_patch, void* stream);
 
-/* The same two stages for a host that does not want the GPU to wait for its read of total_patches (the reference
- * idles around cudaMemcpy(&P), gausplat.cu:67): egs_splat_bin_mb also stores {P, max depth key} into host_totals
- * (a page-locked mailbox slot, egs_mailbox_slot / _arm / _fetch below), and egs_splat_draw_dev is enqueued right
- * behind it with buffers sized by patch_capacity (gsid_per_patch, egs_splat_draw_ws_bytes(n, patch_capacity, ..))
- * and the real count taken from total_patches[0] on the device.  The host then reads the slot: if the count
- * exceeds patch_capacity (nothing was written out of bounds) or the depth keys outgrew the hint, the stages are
- * redone the synchronous way.  gsplatcu.splat works like this from the second call of a problem size on. */
+/* gsplatcu.splatB  (ext.cpp:20-32, gausplat.cu:114-159, kernel.cu:809-950), the literal op: tensors in, nothing kept
+ * of the forward pass.  Gradient outputs (fully written): dloss_dus[N,2], dloss_dcinv2ds[N,3], dloss_dalphas[N],
+ * dloss_dcolors[N,3].  ws: egs_splat_bwd_ws_bytes(n).  areas: the pixel-box policy only. */
+size_t egs_splat_bwd_ws_bytes(int n);
+int egs_splat_bwd(int n, int64_t patches, int width, int height, const float* us, const float* cinv2ds,
+                  const float* alphas, const float* colors, const int32_t* areas, const EgsPolicy* pol,
+                  const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
+                  const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
+                  float* dloss_dus, float* dloss_dcinv2ds, float* dloss_dalphas, float* dloss_dcolors,
+                  void* stream);
+
+/* ---- the same stages from packed records, with what a host may keep between them ----------------------------------
+ * (ABI 12: one tensor-form call -- above -- and one records-form call -- below -- per stage.)
+ *
+ * egs_splat_bin_mb is egs_splat_bin for a host that does not want the GPU to wait for its read of total_patches (the
+ * reference idles around cudaMemcpy(&P), gausplat.cu:67): the kernels also store {P, max depth key} into host_totals (a
+ * page-locked mailbox slot, egs_mailbox_slot / _arm / _fetch below; NULL: exactly egs_splat_bin), and the draw stage is
+ * enqueued right behind it with buffers sized by a capacity and the count taken on the device (egs_splat_draw_rec_seg
+ * with total_patches).  The host then reads the slot: if the count exceeds the capacity (nothing was written out of
+ * bounds) or the depth keys outgrew the hint, the stages are redone the synchronous way.  gsplatcu.splat works like
+ * this from the second call of a problem size on. */
 int egs_splat_bin_mb(int n, int width, int height, const float* us, int32_t* areas, float* depths,
                      const EgsPolicy* pol, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
                      uint32_t* total_patches, uint32_t* host_totals /*nullable*/, void* stream);
-int egs_splat_draw_dev(int n, int64_t patch_capacity, const uint32_t* total_patches, int width, int height,
-                       const float* us, const float* cinv2ds, const float* alphas, const float* colors,
-                       const int32_t* areas, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
-                       size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
-                       int32_t* patch_range_per_tile, int32_t* gsid_per_patch, void* stream);
 
 /* The packed 48-byte 2D records the draw kernels gather (one aligned record per list entry instead of the
  * reference's four gathers, fetch2shared kernel.cu:13-44) as a CALLER-HELD buffer rec[N][12]: gsplatcu.splat packs
- * once, draws with egs_splat_draw_rec / _rec_dev and keeps the buffer for the splatB that follows with the same
- * tensors (egs_splat_bwd_rec; tile_order nullable = the [order | work] buffer of that draw). */
+ * once, draws with egs_splat_draw_rec_seg and keeps the buffer for the splatB that follows with the same tensors
+ * (egs_splat_bwd_seg). */
 int egs_pack_records(int n, int width, int height, const float* us, const float* cinv2ds, const float* alphas,
                      const float* colors, const int32_t* areas /*pixel-box policy only*/, const EgsPolicy* pol,
                      void* rec, void* stream);
 /* splat (ext.cpp:10-18, gausplat.cu:24-112), tile-footprint policies with a skip threshold (pol->footprint == 0,
  * pol->alpha_skip > 0): egs_pack_records and egs_splat_bin(_mb) as ONE pass over the 2D Gaussians.  `rec` receives the
- * packed records; the binning state left in ws_bin makes egs_splat_draw_rec* (flags = EGS_DRAW_MASKED_LISTS) emit the
+ * packed records; the binning state left in ws_bin makes egs_splat_draw_rec_seg (flags = EGS_DRAW_MASKED_LISTS) emit the
  * reference's lists with exact block masks in their values.  depths / areas are updated in place as by egs_splat_bin
  * (kernel.cu:114-119).  host_totals nullable (page-locked mailbox slot, see egs_splat_bin_mb). */
 int egs_splat_bin_pack(int n, int width, int height, const float* us, const float* cinv2ds, const float* alphas,
@@ -173,26 +182,12 @@ int egs_splat_bin_pack(int n, int width, int height, const float* us, const floa
                        uint32_t* stamp /* nullable: egs_pair_stamp_words(n) words, content stamps */,
                        uint8_t* visible /* nullable: n bytes, depths > 0.2 after the in-place cull (gsmodel.py:50) */,
                        void* stream);
-/* egs_splat_draw_rec / egs_splat_draw_rec_dev for the seven-op surface (flags = EGS_DRAW_MASKED_LISTS): gsid_per_patch
- * receives the list the draw kernels walk (with masks), gsid_plain (nullable) the list splat's caller gets
- * (gausplat.cu:108-111), written by the range kernel on its way: no egs_strip_list_masks launch. */
-int egs_splat_draw_rec_plain(int n, int64_t patches, int width, int height, const void* rec, const EgsPolicy* pol,
-                             const void* ws_bin, void* ws_draw, size_t ws_draw_bytes, float* image, int32_t* contrib,
-                             float* final_tau, int32_t* patch_range_per_tile, int32_t* gsid_per_patch,
-                             int32_t* gsid_plain, int32_t* tile_order /*nullable*/, float* grad_records /*nullable*/,
-                             int flags, void* stream);
-int egs_splat_draw_rec_dev_plain(int n, int64_t patch_capacity, const uint32_t* total_patches, int width, int height,
-                                 const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
-                                 size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
-                                 int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* gsid_plain,
-                                 int32_t* tile_order /*nullable*/, float* grad_records /*nullable*/, int flags,
-                                 void* stream);
 /* Content-validated pairing of the reference's two independent calls splat and splatB.  splat keeps the list with
  * masks and a STAMP of the us / cinv2ds / alphas values it was built from (two position-dependent 32-bit sums per 256
  * Gaussians, written by egs_splat_bin_pack).  splatB calls egs_pack_records_validate: it packs the records from the
  * tensors splatB was given (always fresh), stamps them (stamp_b), and REPAIRS the kept list on the device: an entry
  * that is not the caller's own (plain[i] differs) or whose Gaussian lies in a block of 256 with a different stamp
- * becomes the caller's entry with all four blocks set (valid for any data).  egs_splat_bwd_rec_lists(.., kept, flags =
+ * becomes the caller's entry with all four blocks set (valid for any data).  egs_splat_bwd_seg(.., rec, kept, flags =
  * EGS_DRAW_MASKED_LISTS) then walks a list that IS the caller's: no pointer or version comparison is involved, a write
  * through tensor.data or another library's kernel between the two calls is seen. */
 size_t egs_pair_stamp_words(int n);
@@ -205,32 +200,131 @@ int egs_pack_records_validate(int n, int width, int height, const float* us, con
  * bytes per lane.  The host layer's content check of the public splat / splatB pair (ext.cpp:10-32 are two independent
  * calls; what splat keeps for splatB is used only if splatB is handed the same VALUES): ABI 9. */
 int egs_words_differ(const void* a, const void* b, int64_t n_words, int32_t* flag, void* stream);
-/* plain[i] = masked[i] & 0x0FFFFFFF for i < min(count, *count_dev) (count_dev nullable: a device-side patch count
- * the host has not read yet): gsid_per_patch as the reference returns it (gausplat.cu:108-111). */
-int egs_strip_list_masks(int64_t count, const uint32_t* count_dev, const void* masked, int32_t* plain, void* stream);
-/* egs_splat_bwd_rec with flags = EGS_DRAW_MASKED_LISTS: gsid_per_patch is the masked list the forward draw walked. */
-int egs_splat_bwd_rec_lists(int n, int64_t patches, int width, int height, const void* rec, const EgsPolicy* pol,
-                            const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
-                            const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
-                            const int32_t* tile_order, float* grad_records, float* dloss_dus, float* dloss_dcinv2ds,
-                            float* dloss_dalphas, float* dloss_dcolors, int flags, void* stream);
-int egs_splat_bwd_rec(int n, int64_t patches, int width, int height, const void* rec, const EgsPolicy* pol,
+
+/* `flags` of egs_splat_draw_rec_seg (the first two also of egs_splat_bwd_seg):
+ *   EGS_DRAW_CULLED_LISTS   the lists are the footprint-culled ones of EGS_FUSED_CULLED_LISTS (fused path).
+ *   EGS_DRAW_MASKED_LISTS   the lists are the REFERENCE's complete lists (every tile of every rect, kernel.cu:46-80)
+ *     whose values carry the same 4-bit block masks above the Gaussian index -- what egs_splat_bin_pack prepares.  The
+ *     draw kernels take the masks instead of testing the record's certain-miss box per entry (1.95 instead of 2.35 block
+ *     evaluations per entry, entries with an empty mask cost a list read); images and gradients are unchanged (the
+ *     pixels skipped are pixels the reference `continue`s on, kernel.cu:246).  The caller hands gsid_per_patch back to
+ *     ITS caller without the masks: `gsid_plain`.
+ *   EGS_DRAW_SEG_HISTORY    (with seg_ws) the walk part of tile_order holds what this camera's previous render measured:
+ *     a wave per segment where that predicts the walk.
+ *   EGS_DRAW_SEG_SPECULATE  (with seg_ws) take a tile's list length as its predicted walk (all its segments get a wave at
+ *     once) -- for a camera WITHOUT a walk on record, and (ABI 8) for tiles whose recorded walk is less than a quarter of
+ *     their list: a record from before reset_alpha.  For scenes the host knows to be walked to (nearly) their ends -- the
+ *     longest walk a recent render of the scene reported is a good part of its longest list, as right after reset_alpha
+ *     -- where the alternative (one wave continuing from segment 1) is the serial tail this path exists to remove.  On a
+ *     saturating scene it would blend segments nobody looks at: exact either way, the balance is the host's call. */
+#define EGS_DRAW_CULLED_LISTS 1
+#define EGS_DRAW_MASKED_LISTS 2
+#define EGS_DRAW_SEG_HISTORY 4
+#define EGS_DRAW_SEG_SPECULATE 8
+size_t egs_tile_order_len(int width, int height);   /* ints: [forward dispatch order | per-tile work measured by the
+                                                      * draw | per-tile walk length (segment path only)] */
+/* Long lists split over several waves (reference: 256 threads per tile, kernel.cu:152-271 launched (16, 16) at
+ * gausplat.cu:94; here a tile is ONE wave64 whose run time is the length of its walk, so a heavy-tailed scene -- a few
+ * tiles with 10 000 entries, nothing saturating after reset_alpha, gsmodel.py:320-324 -- ends when its longest tile
+ * ends).  With a workspace of egs_seg_ws_bytes(patch capacity, ..) bytes (`seg_ws`), tiles of more than `split_min`
+ * entries are walked in segments of `segment_len` entries -- front-to-back blending is associative on (colour, tau)
+ * pairs -- by one wave each where the walk is predicted (EGS_DRAW_SEG_HISTORY / _SPECULATE), sequentially otherwise;
+ * either way the workspace then holds, per segment end and pixel, the transmittance and the colour of everything behind
+ * it, and a backward pass given the SAME workspace walks every segment with a wave of its own (no sequential dependence
+ * is left in the backward pass).  Tile-footprint policies with alpha_skip > 0 and tau_stop > 0 only.  Images / contrib /
+ * final_tau equal the unsplit kernels' up to the rounding of  sum_s T_s C_s  against one running sum. */
+size_t egs_seg_ws_bytes(int64_t patch_capacity, int width, int height);
+/* segment_len (a power of two >= 64) / split_min: 0 keeps the current value; out2 (nullable) receives the values BEFORE the
+ * call.  Process-wide default (256 / 1024, or EGS_SEG_L / EGS_SEG_MIN from the environment), one atomic word: a render
+ * reads it ONCE, when its forward pass plans; the plan leaves L in the workspace header and every later launch -- the
+ * backward pass included -- takes it from there and sizes its grid by the workspace (ABI 8: a change between a forward
+ * and its backward call no longer matters).  A workspace sized under a larger setting than the one planned with simply
+ * has fewer slots than tiles could use: tiles that do not fit stay unsplit. */
+int egs_seg_config(int segment_len, int split_min, int* out2);
+/* Render extras (ABI 10): per pixel, with w_i = T_i alpha'_i the blend weight of the draw kernel (same skip / stop / clamp
+ * rules),  depth = sum w_i z_i  (z_i = depths[i], camera-space z; NOT normalised: depth / alpha is the expected depth),
+ * alpha = sum w_i = 1 - T_final  (0 on tiles without patches), and  image_c = sum w_i c_i + T_final bg_c.  final_tau keeps
+ * its reference value (0 on tiles without patches).  Forward: depth_out / alpha_out are nullable [H][W] outputs.
+ * Backward: dloss_ddepth / dloss_dalpha are nullable [H][W] upstream gradients (NULL: 0); the background is a constant.
+ * Only the unsplit draw kernels have the extras: seg_ws must be NULL. */
+typedef struct EgsExtras {
+  const float* depths;         /* [N] camera-space z per Gaussian (egs_fused_forward's `depths`) */
+  float* depth_out;            /* nullable [H][W] */
+  float* alpha_out;            /* nullable [H][W] */
+  float background[3];
+  const float* dloss_ddepth;   /* nullable [H][W] */
+  const float* dloss_dalpha;   /* nullable [H][W] */
+} EgsExtras;
+/* The draw stage of egs_splat_draw from the packed records `rec` (required unless n == 0; egs_pack_records,
+ * egs_splat_bin_pack or egs_fused_forward), after any of the binning calls.  Outputs as egs_splat_draw.  Every argument
+ * below may be NULL / 0, and with all of them so the call is egs_splat_draw without its packing pass:
+ *   total_patches   the device words of the binning call: the stage is enqueued BEFORE the host has read them (no GPU
+ *     idle time around the read-back).  `patches` (> 0) is then the CAPACITY that sizes gsid_per_patch, gsid_plain and
+ *     ws_draw (egs_splat_draw_ws_bytes(n, patches, ..)); the real count is taken from total_patches[0] on the device.
+ *     The caller checks afterwards (egs_mailbox_post, or the host_totals of the binning call): if the count exceeds the
+ *     capacity the outputs are incomplete (nothing is written out of bounds) and the stage must be redone with the
+ *     exact count.  NULL: `patches` is exact.
+ *   tile_order      egs_tile_order_len(width, height) ints.  The draw kernels hand the tiles to the SIMDs longest list
+ *     first (k_tile_order, one workgroup, after the tile ranges are known); the buffer receives that dispatch order, the
+ *     work the draw measured per tile and (segment path) the walks, so that a backward pass given the same pointer
+ *     reuses them instead of computing its own.
+ *   grad_records    [N][12] floats: the packed per-Gaussian gradient records of the COMING backward pass; the draw
+ *     kernel zeroes them on the side (it is VALU-bound, the memory system idles) and egs_fused_backward /
+ *     egs_splat_bwd_seg, given the same pointer, skip their own 48 N-byte fill.  Valid for ONE backward pass.
+ *   prev_tile_work  T ints: the work part of the tile_order buffer an EARLIER render of the same camera left behind; the
+ *     forward dispatch order then sorts by it instead of by the list lengths.  Any values are legal (every permutation
+ *     of the tiles gives the same image), good ones balance the launch.  It may be the work part of tile_order itself
+ *     (a caller that keeps ONE buffer per camera: the order is refreshed in place).
+ *   order_ready     != 0: tile_order already holds a dispatch order from an earlier render through the same buffer; the
+ *     draw uses it as it stands (no k_tile_order launch, 10 us) and only rewrites the work part.  The work pattern of a
+ *     camera drifts slowly, so a caller refreshes every few renders, not every time.  prev_tile_work / order_ready are
+ *     ignored when the lists are split (the work items are re-planned per render, by k_seg_plan).
+ *   flags           EGS_DRAW_* bits, above.
+ *   seg_ws, seg_ws_bytes   the segment workspace, above.  NULL: the unsplit draw stage.
+ *   seg_hint        page-locked host memory, e.g. a mailbox slot, two words: [0] receives the longest list, [1] the
+ *     longest WALK of a recent render.
+ *   walk_word       (ABI 8) a PERSISTENT device word of the caller's, one per problem size and stream, holding -1 before
+ *     its first use: the draw items of this call gather the render's longest walk in it, and the range kernel at the
+ *     start of the NEXT call's draw stage on the stream publishes it into seg_hint[1] and resets it -- the host word only
+ *     ever holds the maximum of a completed render, from every render, split or not -- a host that finds it below
+ *     split_min may drop the workspace for later renders of the scene (the unsplit kernels are then the same work with
+ *     two launches less).
+ *   gsid_plain      (with EGS_DRAW_MASKED_LISTS; 16-B aligned, like gsid_per_patch then) receives the list without its
+ *     masks -- gsid_per_patch as the caller of `splat` gets it (gausplat.cu:108-111) -- written by the range kernel on
+ *     its way over the sorted keys, while gsid_per_patch receives the list the draw kernels walk.
+ *   extras          render extras; the lists are then never split: seg_ws must be NULL (EGS_ERR_BAD_ARG). */
+int egs_splat_draw_rec_seg(int n, int64_t patches, const uint32_t* total_patches, int width, int height,
+                           const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
+                           size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
+                           int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order,
+                           float* grad_records, const int32_t* prev_tile_work, int order_ready, int flags, void* seg_ws,
+                           size_t seg_ws_bytes, uint32_t* seg_hint, int32_t* walk_word, int32_t* gsid_plain,
+                           void* stream, const EgsExtras* extras);
+/* splatB for a host that may or may not have kept what its forward pass left (the seven-op surface: `splatB` is handed
+ * tensors).  Outputs and ws as egs_splat_bwd; n == 0 returns 0.
+ *   rec             the packed records; NULL: packed here from us / cinv2ds / alphas / colors (tile-footprint policies
+ *     only: there is no `areas`).  With rec the four tensors may be NULL.
+ *   gsid_per_patch, flags   the caller's list and 0, or the list WITH block masks the forward draw walked
+ *     (egs_splat_bin_pack + egs_splat_draw_rec_seg) and EGS_DRAW_MASKED_LISTS (EGS_DRAW_CULLED_LISTS: the fused path's).
+ *   tile_order      nullable: the forward draw's [order | work | walk] buffer -- the tiles are dispatched by the work that
+ *     draw MEASURED, no k_tile_work pass over `contrib`.
+ *   grad_records    nullable: the records that draw cleared, ALREADY ZERO: no 48 N-byte fill in front of the backward draw.
+ *   seg_ws          NULL: the unsplit kernel (as egs_splat_bwd).  With rebuild == 0: the workspace the forward's
+ *     egs_splat_draw_rec_seg filled.  With rebuild != 0: a fresh one of egs_seg_rebuild_ws_bytes(patches, ..) -- nothing
+ *     was kept: every tile's walk is read off `contrib`, the forward segment launches run once more over [0, walk) with
+ *     their pixels going to scratch (they only rebuild the segment-end states: about the cost of a forward draw), then
+ *     every segment is walked backward by a wave of its own: on scene.skewed_scene after reset_alpha 3.4 ms of one-wave-
+ *     per-tile backward draw become ~1.2 ms.
+ *   seg_hint        nullable: page-locked words that learn the longest walk from either path -- a host decides from them
+ *     whether its next call brings a workspace. */
+size_t egs_seg_rebuild_ws_bytes(int64_t patch_capacity, int width, int height);
+int egs_splat_bwd_seg(int n, int64_t patches, int width, int height, const float* us, const float* cinv2ds,
+                      const float* alphas, const float* colors, const void* rec, const EgsPolicy* pol,
                       const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
                       const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
-                      const int32_t* tile_order /*nullable*/, float* grad_records /*nullable: zeroed by that draw*/,
-                      float* dloss_dus, float* dloss_dcinv2ds, float* dloss_dalphas, float* dloss_dcolors,
-                      void* stream);
-
-/* gsplatcu.splatB  (ext.cpp:20-32, gausplat.cu:114-159, kernel.cu:809-950).
- * Gradient outputs (fully written): dloss_dus[N,2], dloss_dcinv2ds[N,3],
- * dloss_dalphas[N], dloss_dcolors[N,3].  ws: egs_splat_bwd_ws_bytes(n). */
-size_t egs_splat_bwd_ws_bytes(int n);
-int egs_splat_bwd(int n, int64_t patches, int width, int height, const float* us, const float* cinv2ds,
-                  const float* alphas, const float* colors, const int32_t* areas, const EgsPolicy* pol,
-                  const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
-                  const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
-                  float* dloss_dus, float* dloss_dcinv2ds, float* dloss_dalphas, float* dloss_dcolors,
-                  void* stream);
+                      const int32_t* tile_order, float* grad_records, float* dloss_dus, float* dloss_dcinv2ds,
+                      float* dloss_dalphas, float* dloss_dcolors, int flags, void* seg_ws, size_t seg_ws_bytes,
+                      int rebuild, uint32_t* seg_hint, void* stream);
 
 /* ---- building blocks, exported for the parity tests ---------------------- */
 
@@ -292,13 +386,17 @@ int egs_chain_rule(int n, int sh_dim, const float* dloss_dus, const float* dloss
  * records).  Without it the inputs are activated: shs is [N][sh_dim] and high_shs must be NULL (EGS_ERR_BAD_ARG). */
 #define EGS_FUSED_RAW 512
 /* rec (nullable): 48 N bytes; receives the packed 2D records of the draw kernels so that
- * egs_splat_draw_rec / egs_fused_backward skip their own packing pass.  With rec given, each of
+ * egs_splat_draw_rec_seg / egs_fused_backward skip their own packing pass.  With rec given, each of
  * us / cinv2ds / colors / areas may be NULL (they are only needed to continue on the seven-op surface)
  * and egs_fused_backward accepts NULL for them too.
  * visible (nullable): N bytes; receives depths[i] > 0.2 AFTER the in-place culling of splat, i.e. the
  * mask GSFunction.forward returns (gsmodel.py:50).
  * host_totals (nullable): device-visible address of a page-locked host uint32[2] (egs_mailbox_slot) that the
- * binning kernels write {P, max depth key} into as well -- the enqueue-ahead path then needs no copy. */
+ * binning kernels write {P, max depth key} into as well -- the enqueue-ahead path then needs no copy.
+ * dcolor_dpws (nullable, [N][9] floats, 16-B aligned): dcolor/dpw of every Gaussian (what sh2Color's calc_J hands
+ * back as dcolor_dpws, gausplat.cu:298-338), kept for the backward pass: egs_fused_backward given the same pointer
+ * never reads the SH coefficients again -- eq (7)'s colour term is the only thing it needs them for, dL/dsh needs
+ * the basis alone -- i.e. 36 B written here for 4 sh_dim bytes (192 at SH degree 3) not re-read there. */
 int egs_fused_forward(int n, int sh_dim, const float* pws, const float* rots, const float* scales,
                       const float* shs, const float* high_shs /*EGS_FUSED_RAW only*/, const float* alphas,
                       const float* Rcw, const float* tcw, const float* twc, float fx, float fy, float cx, float cy,
@@ -306,123 +404,6 @@ int egs_fused_forward(int n, int sh_dim, const float* pws, const float* rots, co
                       float* colors, int32_t* areas, void* rec, uint8_t* visible, float* dcolor_dpws /*nullable*/,
                       int flags /*EGS_FUSED_* bits*/, int key_bits_hint, void* ws_bin, size_t ws_bin_bytes,
                       uint32_t* total_patches, uint32_t* host_totals, void* stream);
-/* dcolor_dpws (nullable, [N][9] floats, 16-B aligned): dcolor/dpw of every Gaussian (what sh2Color's calc_J hands
- * back as dcolor_dpws, gausplat.cu:298-338), kept for the backward pass: egs_fused_backward given the same pointer
- * never reads the SH coefficients again -- eq (7)'s colour term is the only thing it needs them for, dL/dsh needs
- * the basis alone -- i.e. 36 B written here for 4 sh_dim bytes (192 at SH degree 3) not re-read there. */
-int egs_splat_draw_rec(int n, int64_t patches, int width, int height, const void* rec, const EgsPolicy* pol,
-                       const void* ws_bin, void* ws_draw, size_t ws_draw_bytes, float* image,
-                       int32_t* contrib, float* final_tau, int32_t* patch_range_per_tile,
-                       int32_t* gsid_per_patch, int32_t* tile_order /*nullable*/,
-                       float* grad_records /*nullable*/, const int32_t* prev_tile_work /*nullable*/,
-                       int order_ready, int flags /* EGS_DRAW_CULLED_LISTS or 0 */, void* stream);
-/* prev_tile_work (nullable, T ints): the work part of the tile_order buffer an EARLIER render of the same camera
- * left behind; the forward dispatch order then sorts by it instead of by the list lengths.  Any values are
- * legal (every permutation of the tiles gives the same image), good ones balance the launch.  It may be the work
- * part of tile_order itself (a caller that keeps ONE buffer per camera: the order is refreshed in place).
- * order_ready != 0: tile_order already holds a dispatch order from an earlier render through the same buffer;
- * the draw uses it as it stands (no k_tile_order launch, 10 us) and only rewrites the work part.  The work
- * pattern of a camera drifts slowly, so a caller refreshes every few renders, not every time. */
-/* grad_records (nullable, [N][12] floats): the packed per-Gaussian gradient records of the COMING backward pass;
- * the draw kernel zeroes them on the side (it is VALU-bound, the memory system idles) and egs_fused_backward,
- * given the same pointer, skips its own 48 N-byte fill.  Valid for ONE backward pass.
- * The draw kernels hand the tiles to the SIMDs longest list first (k_tile_order, one workgroup, after the
- * tile ranges are known).  tile_order (nullable, egs_tile_order_len(width, height) ints) receives that dispatch
- * order so that egs_fused_backward can reuse it instead of computing its own. */
-size_t egs_tile_order_len(int width, int height);   /* ints: [forward dispatch order | per-tile work measured by the
-                                                      * draw | per-tile walk length (segment path only)] */
-/* Long lists split over several waves (reference: 256 threads per tile, kernel.cu:152-271 launched (16, 16) at
- * gausplat.cu:94; here a tile is ONE wave64 whose run time is the length of its walk, so a heavy-tailed scene -- a few
- * tiles with 10 000 entries, nothing saturating after reset_alpha, gsmodel.py:320-324 -- ends when its longest tile
- * ends).  egs_splat_draw_rec_seg is egs_splat_draw_rec (total_patches == NULL: `patches` exact) / egs_splat_draw_rec_dev
- * (total_patches on the device, `patches` the capacity) with a workspace of egs_seg_ws_bytes(patch capacity, ..) bytes:
- * tiles of more than `split_min` entries are walked in segments of `segment_len` entries -- front-to-back blending is
- * associative on (colour, tau) pairs -- by one wave each where this camera's previous render predicts the walk
- * (flags & EGS_DRAW_SEG_HISTORY: the walk part of tile_order is that render's), sequentially otherwise; either way the
- * workspace then holds, per segment end and pixel, the transmittance and the colour of everything behind it, and
- * egs_fused_backward given the SAME workspace walks every segment with a wave of its own (no sequential
- * dependence is left in the backward pass).  Tile-footprint policies with alpha_skip > 0 and tau_stop > 0 only.
- * Images / contrib / final_tau equal the unsplit kernels' up to the rounding of  sum_s T_s C_s  against one running sum.
- * seg_hint (nullable, page-locked host memory, e.g. a mailbox slot, two words): [0] receives the longest list, [1] the
- * longest WALK of a recent render.  ABI 8: walk_word (nullable) is a PERSISTENT device word of the caller's, one per
- * problem size and stream, holding -1 before its first use: the draw items of this call gather the render's longest walk
- * in it, and the range kernel at the start of the NEXT call's draw stage on the stream publishes it into seg_hint[1] and
- * resets it -- the host word only ever holds the maximum of a completed render, from every render, split or not -- a
- * host that finds it below split_min may drop the workspace for later renders of the scene (the unsplit kernels are
- * then the same work with two launches less).  prev_tile_work / order_ready are ignored when the lists are split
- * (the work items are re-planned per render, by k_seg_plan). */
-#define EGS_DRAW_SEG_HISTORY 4
-/* flags of egs_splat_draw_rec_seg: take a tile's list length as its predicted walk (all its segments get a wave at once)
- * -- for a camera WITHOUT a walk on record, and (ABI 8) for tiles whose recorded walk is less than a quarter of their
- * list: a record from before reset_alpha.  For scenes the host knows to be walked to (nearly) their ends -- the
- * longest walk a recent render of the scene reported is a good part of its longest list, as right after reset_alpha --
- * where the alternative (one wave continuing from segment 1) is the serial tail this path exists to remove.  On a
- * saturating scene it would blend segments nobody looks at: exact either way, the balance is the host's call. */
-#define EGS_DRAW_SEG_SPECULATE 8
-size_t egs_seg_ws_bytes(int64_t patch_capacity, int width, int height);
-/* segment_len (a power of two >= 64) / split_min: 0 keeps the current value; out2 (nullable) receives the values BEFORE the
- * call.  Process-wide default (256 / 1024, or EGS_SEG_L / EGS_SEG_MIN from the environment), one atomic word: a render
- * reads it ONCE, when its forward pass plans; the plan leaves L in the workspace header and every later launch -- the
- * backward pass included -- takes it from there and sizes its grid by the workspace (ABI 8: a change between a forward
- * and its backward call no longer matters).  A workspace sized under a larger setting than the one planned with simply
- * has fewer slots than tiles could use: tiles that do not fit stay unsplit. */
-int egs_seg_config(int segment_len, int split_min, int* out2);
-/* Render extras (ABI 10): per pixel, with w_i = T_i alpha'_i the blend weight of the draw kernel (same skip / stop / clamp
- * rules),  depth = sum w_i z_i  (z_i = depths[i], camera-space z; NOT normalised: depth / alpha is the expected depth),
- * alpha = sum w_i = 1 - T_final  (0 on tiles without patches), and  image_c = sum w_i c_i + T_final bg_c.  final_tau keeps
- * its reference value (0 on tiles without patches).  Forward: depth_out / alpha_out are nullable [H][W] outputs.
- * Backward: dloss_ddepth / dloss_dalpha are nullable [H][W] upstream gradients (NULL: 0); the background is a constant.
- * Only the unsplit draw kernels have the extras: seg_ws must be NULL. */
-typedef struct EgsExtras {
-  const float* depths;         /* [N] camera-space z per Gaussian (egs_fused_forward's `depths`) */
-  float* depth_out;            /* nullable [H][W] */
-  float* alpha_out;            /* nullable [H][W] */
-  float background[3];
-  const float* dloss_ddepth;   /* nullable [H][W] */
-  const float* dloss_dalpha;   /* nullable [H][W] */
-} EgsExtras;
-int egs_splat_draw_rec_seg(int n, int64_t patches, const uint32_t* total_patches /*nullable*/, int width, int height,
-                           const void* rec, const EgsPolicy* pol, const void* ws_bin, void* ws_draw,
-                           size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
-                           int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order /*nullable*/,
-                           float* grad_records /*nullable*/, const int32_t* prev_tile_work /*nullable*/, int order_ready,
-                           int flags, void* seg_ws /*nullable: the unsplit draw stage*/, size_t seg_ws_bytes,
-                           uint32_t* seg_hint /*nullable*/, int32_t* walk_word /*nullable*/,
-                           int32_t* gsid_plain /*nullable; with EGS_DRAW_MASKED_LISTS: the list without its masks, what
-                                                 the caller of `splat` gets (as egs_splat_draw_rec_plain)*/,
-                           void* stream, const EgsExtras* extras /*nullable; with extras seg_ws must be NULL*/);
-/* splatB for a host that may or may not have kept what its forward pass left (the seven-op surface: `splatB` is handed
- * tensors).  rec (nullable: packed here from us / cinv2ds / alphas / colors), tile_order / grad_records (nullable: the
- * forward draw's [order | work | walk] buffer and cleared gradient records), flags as egs_splat_bwd_rec_lists.
- * seg_ws == NULL: the unsplit kernel (egs_splat_bwd / egs_splat_bwd_rec_lists).  seg_ws + rebuild == 0: the workspace the
- * forward's egs_splat_draw_rec_seg filled.  seg_ws of egs_seg_rebuild_ws_bytes(patches, ..) + rebuild != 0: nothing
- * was kept -- every tile's walk is read off `contrib`, the forward segment launches run once more over [0, walk) with
- * their pixels going to scratch (they only rebuild the segment-end states: about the cost of a forward draw), then
- * every segment is walked backward by a wave of its own: on scene.skewed_scene after reset_alpha 3.4 ms of one-wave-
- * per-tile backward draw become ~1.2 ms.  seg_hint (nullable): page-locked words that learn the longest walk from
- * either path -- a host decides from them whether its next call brings a workspace. */
-size_t egs_seg_rebuild_ws_bytes(int64_t patch_capacity, int width, int height);
-int egs_splat_bwd_seg(int n, int64_t patches, int width, int height, const float* us, const float* cinv2ds,
-                      const float* alphas, const float* colors, const void* rec /*nullable*/, const EgsPolicy* pol,
-                      const int32_t* contrib, const float* final_tau, const int32_t* patch_range_per_tile,
-                      const int32_t* gsid_per_patch, const float* dloss_dgammas, void* ws, size_t ws_bytes,
-                      const int32_t* tile_order /*nullable*/, float* grad_records /*nullable*/, float* dloss_dus,
-                      float* dloss_dcinv2ds, float* dloss_dalphas, float* dloss_dcolors, int flags,
-                      void* seg_ws /*nullable*/, size_t seg_ws_bytes, int rebuild, uint32_t* seg_hint /*nullable*/,
-                      void* stream);
-/* As egs_splat_draw_rec, for a host that enqueues the draw stage BEFORE it has read total_patches (no GPU
- * idle time around the read-back): patch_capacity sizes gsid_per_patch and ws_draw
- * (egs_splat_draw_ws_bytes(n, patch_capacity, ..)), the real patch count is taken from total_patches[0] on
- * the device.  host_totals (nullable, page-locked host uint32[2]) receives total_patches[0..1] by an
- * asynchronous copy enqueued in front of the draw stage.  The caller checks afterwards: if the count exceeds
- * patch_capacity the outputs are incomplete (nothing is written out of bounds) and the stage must be redone
- * with the exact count (egs_splat_draw_rec). */
-int egs_splat_draw_rec_dev(int n, int64_t patch_capacity, const uint32_t* total_patches, uint32_t* host_totals,
-                           int width, int height, const void* rec, const EgsPolicy* pol, const void* ws_bin,
-                           void* ws_draw, size_t ws_draw_bytes, float* image, int32_t* contrib, float* final_tau,
-                           int32_t* patch_range_per_tile, int32_t* gsid_per_patch, int32_t* tile_order /*nullable*/,
-                           float* grad_records /*nullable*/, const int32_t* prev_tile_work /*nullable*/,
-                           int order_ready, int flags, void* stream);
 /* Measurement helper (bench.py): one device-to-device float4 copy of `bytes` (multiple of 16, both pointers
  * 16-B aligned) -- the achievable-HBM-bandwidth probe SURVEY 8(d) asks the roofline to be quoted against. */
 int egs_hbm_copy_probe(void* dst, const void* src, size_t bytes, void* stream);
@@ -431,7 +412,7 @@ int egs_hbm_copy_probe(void* dst, const void* src, size_t bytes, void* stream);
  * device memory; once the stream has run it, MHz = (out[1] - out[0]) / (out[3] - out[2]) * 100.  What a VALU-bound
  * kernel's roofline is priced against: 1024 SIMDs x this clock. */
 int egs_clock_probe(void* out8, int iters, void* stream);
-/* Mailbox for that read-back: `slots` page-locked landing zones, each with a HIP event.  egs_mailbox_post
+/* Mailbox for the read-back of total_patches: `slots` page-locked landing zones, each with a HIP event.  egs_mailbox_post
  * enqueues the asynchronous 8-byte copy of total_patches[0..1] into a slot on `stream` and records the
  * slot's event behind it; egs_mailbox_fetch returns 1 and the two words once the copy has landed, 0 when it
  * has not (blocking == 0), or waits for it on the slot's event (blocking != 0): ONE C-side wait where the
@@ -485,15 +466,6 @@ size_t egs_fused_backward_ws_bytes(int n);
 /* dloss_dus_abs[i] = grad_records[i][10..11] for all n records, after an egs_fused_backward with EGS_BWD_ABSGRAD
  * (zeros for a Gaussian no tile lists).  dloss_dus_abs: [N][2] floats, 8-B aligned. */
 int egs_grad_records_absgrad(int n, const float* grad_records, float* dloss_dus_abs /*[N][2]*/, void* stream);
-/* flags of egs_splat_draw_rec*: the lists are the footprint-culled ones of EGS_FUSED_CULLED_LISTS */
-#define EGS_DRAW_CULLED_LISTS 1
-/* flags of egs_splat_draw_rec* / egs_splat_bwd_rec_lists: the lists are the REFERENCE's complete lists (every tile of
- * every rect, kernel.cu:46-80) whose values carry the same 4-bit block masks above the Gaussian index -- what
- * egs_splat_bin_pack prepares.  The draw kernels take the masks instead of testing the record's certain-miss box per
- * entry (1.95 instead of 2.35 block evaluations per entry, entries with an empty mask cost a list read); images and
- * gradients are unchanged (the pixels skipped are pixels the reference `continue`s on, kernel.cu:246).  The caller
- * hands gsid_per_patch back to ITS caller without the masks (egs_splat_draw_rec_plain, or egs_strip_list_masks). */
-#define EGS_DRAW_MASKED_LISTS 2
 /* Camera pose gradients (`pose` of egs_fused_backward, nullable): dL/dRcw [3][3] (row-major) and dL/dtcw [3] of this
  * view -- always written, never added to, whatever EGS_BWD_ACCUMULATE says of the per-Gaussian outputs.  The camera
  * centre is treated as twc = -Rcw^T tcw (the rotation convention; equal to -inv(Rcw) tcw on a true rotation): the caller

@@ -108,8 +108,8 @@ def lib():
 def test_absgrad_abi_is_additive(lib):
     from easygaussiansplatting_amd import _lib, fused
     hdr = open(os.path.join(REPO, "include", "egs_hip.h")).read()
-    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 11
-    assert lib.egs_abi_version() == 11
+    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 12
+    assert lib.egs_abi_version() == 12
     bits = {k: int(v) for k, v in re.findall(r"#define (EGS_(?:BWD|FUSED)_\w+) (\d+)", hdr)}
     ab = bits.pop("EGS_BWD_ABSGRAD")
     assert ab == fused.ABSGRAD and ab & (ab - 1) == 0 and ab & 3 == 0          # one bit, clear of the base phase
@@ -126,6 +126,9 @@ def test_absgrad_abi_is_additive(lib):
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
     assert "egs_grad_records_absgrad" in exported and "egs_fused_backward" in exported
+    from tests.test_cabi_and_host import REMOVED_IN_ABI_12, egs_names
+    for name in REMOVED_IN_ABI_12:      # ABI 12 only removed: the splat-stage variants nothing called
+        assert name not in exported and name not in _lib.SIGNATURES and name not in egs_names(hdr), name
 
 
 def test_absgrad_refusals_before_the_device(lib):

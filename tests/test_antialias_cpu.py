@@ -11,6 +11,7 @@ import pytest
 from easygaussiansplatting_amd import scene as S
 from oracle import gs_oracle as O
 from tests import aa_ref
+from tests.test_cabi_and_host import REMOVED_IN_ABI_12, egs_names
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ABI 11 folded the anti-aliased entry points into egs_fused_forward / egs_viewer_prep (flag EGS_FUSED_ANTIALIASED)
@@ -139,9 +140,11 @@ def test_trainer_refuses_antialiased_ops_mode():
 def test_antialiased_flag_abi():
     from easygaussiansplatting_amd import _lib, fused
     hdr = open(os.path.join(REPO, "include", "egs_hip.h")).read()
-    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 11
+    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 12
     for name in REMOVED_SYMBOLS:
         assert name not in hdr and name not in _lib.SIGNATURES, name
+    for name in REMOVED_IN_ABI_12:      # (whole identifiers: egs_splat_draw_rec is a prefix of the call that stays)
+        assert name not in egs_names(hdr) and name not in _lib.SIGNATURES, name
     # the flag rides on the one forward entry point (`flags`) and the viewer's (`flags`, in front of the stream)
     assert "int egs_fused_forward(" in hdr and "int egs_viewer_prep(" in hdr
     assert _lib.SIGNATURES["egs_viewer_prep"][1][-2:] == [C.c_int, C.c_void_p]
@@ -168,10 +171,10 @@ def test_antialiased_variants_folded_in_exports(lib):
     from easygaussiansplatting_amd import _lib
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    for name in REMOVED_SYMBOLS:
+    for name in REMOVED_SYMBOLS + REMOVED_IN_ABI_12:
         assert name not in exported, name
     assert "egs_fused_forward" in exported and "egs_viewer_prep" in exported
-    assert lib.egs_abi_version() == 11
+    assert lib.egs_abi_version() == 12
 
 
 def _forward(lib, n, flags, high, rec):

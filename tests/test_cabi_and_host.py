@@ -237,3 +237,101 @@ def test_variant_patches_apply():
         for knob in ("EGS_DRAW_PROBE_NOK", "EGS_PROBE_REDUCE", "EGS_DRAW_DUMMY_", "EGS_PLAN_STAMPS", "EGS_PROBE_HIT_BITS",
                      "WRONG"):
             assert knob not in src, "%s still holds %s" % (os.path.basename(f), knob)
+
+
+# ---- ABI 12: one tensor-form and one records-form call per stage of splat / splatB -------------------------------------
+# (shared with the four test files that pin the ABI version: the names join their "removed" lists)
+REMOVED_IN_ABI_12 = ("egs_splat_draw_dev", "egs_splat_draw_rec", "egs_splat_draw_rec_dev", "egs_splat_draw_rec_plain",
+                     "egs_splat_draw_rec_dev_plain", "egs_splat_bwd_rec", "egs_splat_bwd_rec_lists",
+                     "egs_strip_list_masks")
+EXPORTED_IN_ABI_11 = 72      # `nm -D --defined-only libegs_hip.so | grep -c ' egs_'` on the ABI 11 library
+BAD_ARG, WORKSPACE = 10001, 10002
+
+
+def egs_names(text):
+    """every whole egs_* identifier in ``text`` (egs_splat_draw_rec is a prefix of a call that stays)"""
+    return set(re.findall(r"\begs_[a-z0-9_]+", text))
+
+
+def exported_egs_symbols():
+    from easygaussiansplatting_amd import _lib
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
+    return {ln.split()[-1] for ln in out.splitlines() if ln.strip() and ln.split()[-1].startswith("egs_")}
+
+
+def test_abi12_removed_splat_variants_are_gone(lib):
+    from easygaussiansplatting_amd import _lib
+    hdr = open(HEADER).read()           # comments included: nothing points a reader at a call that is gone
+    exported = exported_egs_symbols()
+    for name in REMOVED_IN_ABI_12:
+        assert name not in egs_names(hdr), name
+        assert name not in _lib.SIGNATURES and name not in exported, name
+    assert len(exported) == EXPORTED_IN_ABI_11 - len(REMOVED_IN_ABI_12) == 64
+    assert lib.egs_abi_version() == _lib.ABI_VERSION == 12
+    for kept in ("egs_splat_bin", "egs_splat_bin_mb", "egs_splat_bin_pack", "egs_pack_records",
+                 "egs_pack_records_validate", "egs_splat_draw", "egs_splat_draw_rec_seg", "egs_splat_bwd",
+                 "egs_splat_bwd_seg"):
+        assert kept in exported and kept in _lib.SIGNATURES and kept in declared_functions(), kept
+
+
+_FAKE = C.c_void_p(4096)        # a pointer nobody dereferences: every call below is refused before any HIP call
+
+
+def _draw_rec_seg(lib, n=1000, patches=100, total=None, rec=_FAKE, gsid=_FAKE, gsid_plain=None, seg_ws=None,
+                  extras=None):
+    from easygaussiansplatting_amd import _lib
+    pol = _lib.EgsPolicy()
+    lib.egs_policy_gsplatcu(C.byref(pol))
+    return lib.egs_splat_draw_rec_seg(n, patches, total, 150, 70, rec, C.byref(pol), _FAKE, _FAKE, 1 << 20, _FAKE, _FAKE,
+                                      _FAKE, _FAKE, gsid, None, None, None, 0, 0, seg_ws, (1 << 20) if seg_ws else 0,
+                                      None, None, gsid_plain, None, extras)
+
+
+def test_records_form_draw_refuses_before_the_device(lib):
+    """the argument checks of the removed draw variants, all made by egs_splat_draw_rec_seg (same codes as ABI 11)"""
+    from easygaussiansplatting_amd import _lib
+    err = lib.egs_last_error_string
+    assert _draw_rec_seg(lib, rec=None) == BAD_ARG and b"rec || n == 0" in err()
+    assert _draw_rec_seg(lib, patches=0, total=_FAKE) == BAD_ARG and b"total_patches" in err()
+    assert _draw_rec_seg(lib, gsid_plain=C.c_void_p(4096 + 4)) == BAD_ARG and b"gsid_plain" in err()
+    assert _draw_rec_seg(lib, gsid=C.c_void_p(4096 + 8), gsid_plain=_FAKE) == BAD_ARG and b"gsid_plain" in err()
+    ex = _lib.EgsExtras()
+    ex.depths = 4096
+    assert _draw_rec_seg(lib, seg_ws=_FAKE, extras=C.byref(ex)) == BAD_ARG and b"extras" in err()
+
+
+def _bwd_seg(lib, n=1000, tensors=True, rec=None, ws=_FAKE, ws_bytes=None, grads=True, footprint=0):
+    from easygaussiansplatting_amd import _lib
+    pol = _lib.EgsPolicy()
+    lib.egs_policy_gsplatcu(C.byref(pol))
+    pol.footprint = footprint
+    t = _FAKE if tensors else None
+    g = _FAKE if grads else None
+    if ws_bytes is None:
+        ws_bytes = lib.egs_splat_bwd_ws_bytes(n)
+    return lib.egs_splat_bwd_seg(n, 100, 150, 70, t, t, t, t, rec, C.byref(pol), _FAKE, _FAKE, _FAKE, _FAKE, _FAKE, ws,
+                                 ws_bytes, None, None, g, g, g, g, 0, None, 0, 0, None, None)
+
+
+def test_records_form_backward_refuses_before_the_device(lib):
+    """the shared prologue of the two splatB entry points: same order and codes as ABI 11"""
+    err = lib.egs_last_error_string
+    assert _bwd_seg(lib, n=0, tensors=False, ws=None, ws_bytes=0, grads=False) == 0      # nothing to do, nothing read
+    assert _bwd_seg(lib, n=-1) == BAD_ARG
+    assert _bwd_seg(lib, ws=None) == BAD_ARG and b"ws &&" in err()
+    assert _bwd_seg(lib, grads=False) == BAD_ARG and b"dloss_dus" in err()
+    assert _bwd_seg(lib, tensors=False) == BAD_ARG and b"rec ||" in err()               # neither records nor tensors
+    assert _bwd_seg(lib, tensors=True, footprint=1) == BAD_ARG and b"rec ||" in err()   # pixel boxes need `areas`
+    assert _bwd_seg(lib, tensors=False, ws_bytes=16) == BAD_ARG                          # ... refused before the size
+    n = 1000
+    assert _bwd_seg(lib, ws_bytes=lib.egs_splat_bwd_ws_bytes(n) - 1) == WORKSPACE and b"workspace" in err()
+    assert _bwd_seg(lib, tensors=False, rec=_FAKE, ws_bytes=16) == WORKSPACE
+    # the literal op shares the prologue
+    from easygaussiansplatting_amd import _lib
+    pol = _lib.EgsPolicy()
+    lib.egs_policy_gsplatcu(C.byref(pol))
+    bwd = lambda n_, ws_, nbytes, g: lib.egs_splat_bwd(n_, 100, 150, 70, _FAKE, _FAKE, _FAKE, _FAKE, None, C.byref(pol),
+                                                      _FAKE, _FAKE, _FAKE, _FAKE, _FAKE, ws_, nbytes, g, g, g, g, None)
+    assert bwd(0, None, 0, None) == 0
+    assert bwd(n, None, 0, _FAKE) == BAD_ARG and bwd(n, _FAKE, 1 << 30, None) == BAD_ARG
+    assert bwd(n, _FAKE, 16, _FAKE) == WORKSPACE

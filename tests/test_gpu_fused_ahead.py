@@ -1,5 +1,5 @@
 """Fused forward with the draw stage enqueued ahead of the read-back of the patch count
-(egs_splat_draw_rec_dev): same results as the synchronous path, safe on capacity / hint overflow."""
+(egs_splat_draw_rec_seg with total_patches): same results as the synchronous path, safe on capacity / hint overflow."""
 import numpy as np
 import pytest
 import torch
@@ -266,8 +266,9 @@ def test_backward_in_the_forward_dispatch_order(monkeypatch):
 
 def test_seven_op_splat_enqueues_ahead_too():
     """``gsplatcu.splat``: from the second call of a problem size on the draw stage is enqueued before P has been
-    read (egs_splat_bin_mb / egs_splat_draw_dev); same five outputs as the synchronous sequence, also when the
-    learnt capacity or the depth-key hint turn out too small, and the in-place cull of depths / areas is kept."""
+    read (egs_splat_bin_mb / egs_splat_draw_rec_seg with total_patches); same five outputs as the synchronous sequence,
+    also when the learnt capacity or the depth-key hint turn out too small, and the in-place cull of depths / areas is
+    kept."""
     from easygaussiansplatting_amd import fused, scene as S
     from easygaussiansplatting_amd import gsplatcu as gsc
     from easygaussiansplatting_amd.function import Camera

@@ -138,13 +138,14 @@ def test_pose_argument_of_fused_backward(lib):
     for name in ("egs_pose_ws_bytes", "egs_fused_backward"):
         assert name in exported and name in _lib.SIGNATURES, name
     # ABI 11: the pose is the last, nullable argument of egs_fused_backward, behind the EgsExtras
-    for name in ("egs_fused_backward_pose", "egs_fused_backward_raw_pose"):
+    from tests.test_cabi_and_host import REMOVED_IN_ABI_12
+    for name in ("egs_fused_backward_pose", "egs_fused_backward_raw_pose") + REMOVED_IN_ABI_12:
         assert name not in exported and name not in _lib.SIGNATURES, name
     assert _lib.SIGNATURES["egs_fused_backward"][1][-2:] == [C.POINTER(_lib.EgsExtras), C.POINTER(_lib.EgsPoseGrad)]
     assert _lib.SIGNATURES["egs_fused_backward"][0] is C.c_int
     assert C.sizeof(_lib.EgsPoseGrad) == 32
     assert [f for f, _ in _lib.EgsPoseGrad._fields_] == ["dloss_dRcw", "dloss_dtcw", "ws", "ws_bytes"]
-    assert lib.egs_abi_version() == 11 and C.sizeof(_lib.EgsExtras) == 56
+    assert lib.egs_abi_version() == 12 and C.sizeof(_lib.EgsExtras) == 56
 
 
 def test_pose_ws_bytes_is_monotone(lib):

@@ -32,11 +32,14 @@ def test_render_options_extras_validation():
 def test_extras_arguments_and_abi_version():
     from easygaussiansplatting_amd import _lib
     hdr = open(os.path.join(REPO, "include", "egs_hip.h")).read()
-    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 11
+    assert int(re.search(r"#define EGS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 12
     # ABI 11: the EgsExtras* is a nullable argument of the draw and backward entry points, not separate _ex ones
     removed = ("egs_splat_draw_rec_seg_ex", "egs_fused_backward_ex", "egs_fused_backward_raw_ex")
     for name in removed:
         assert name not in _lib.SIGNATURES and name not in hdr
+    from tests.test_cabi_and_host import REMOVED_IN_ABI_12, egs_names
+    for name in REMOVED_IN_ABI_12:      # (whole identifiers: egs_splat_draw_rec is a prefix of the call that stays)
+        assert name not in _lib.SIGNATURES and name not in egs_names(hdr), name
     assert _lib.SIGNATURES["egs_splat_draw_rec_seg"][1][-1] is C.POINTER(_lib.EgsExtras)
     assert _lib.SIGNATURES["egs_fused_backward"][1][-2] is C.POINTER(_lib.EgsExtras)
     # the ctypes mirror has the C layout: 3 pointers, 3 floats (+4 padding), 2 pointers
@@ -46,7 +49,7 @@ def test_extras_arguments_and_abi_version():
         out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
         exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
         assert "egs_splat_draw_rec_seg" in exported and "egs_fused_backward" in exported
-        for name in removed:
+        for name in removed + REMOVED_IN_ABI_12:
             assert name not in exported
 
 
