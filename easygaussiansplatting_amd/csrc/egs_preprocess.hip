@@ -729,7 +729,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
 // dL/dtcw [3], dL/dtwc [3], 0} per workgroup in pose_ws (read by the POSE instances only), summed by k_pose_reduce
 // AA (anti-aliased rendering): the records were drawn with opacity alpha comp; reads alphas[i] also
 // without RAW (4 B per Gaussian)
-template <int NC, bool RAW, bool JW, bool EXTRA, bool POSE, bool AA>
+// POSE_ONLY (with POSE; EGS_BWD_POSE_ONLY): the partial row in pose_ws is the ONLY output -- the same 15 per-lane
+// terms and the same reduction as the POSE instance, but no old gradients, no cov3d_vjp, no J3 product, no gsh rows, and
+// the seven dL_d* pointers (NULL or not) are never dereferenced; `mode` is ignored.  With JW the SH rows are never
+// touched; without it they are still staged in (W needs them)
+template <int NC, bool RAW, bool JW, bool EXTRA, bool POSE, bool AA, bool POSE_ONLY>
 __global__ __launch_bounds__(256) void k_preprocess_bwd(
     int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
     const float* __restrict__ scales, const float* __restrict__ shs, const float* __restrict__ shs_high,
@@ -744,8 +748,9 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
   // mode bit 1 (EGS_BWD_FACTORED_SH): the SH gradient stays in its factored form -- eq (5) is an outer product
   // dL/dcolour (x) basis, so dL_dsh receives the THREE floats dL/dcolour per Gaussian ([N][3], always written, never
   // accumulated) and the rows are formed once per step, for all views, by k_sh_grad_views; dL_dsh_high is not touched
-  const int accum = mode & 1;
-  const bool factored = (mode & 2) != 0;
+  static_assert(POSE || !POSE_ONLY, "POSE_ONLY is a flavour of the POSE instances");
+  const int accum = POSE_ONLY ? 0 : (mode & 1);
+  const bool factored = !POSE_ONLY && (mode & 2) != 0;
   // accum: the five (six) parameter-gradient outputs already hold the gradients of EARLIER views of the step and this
   // view's are ADDED to them (dL_du is per view and always written): a rank that renders V views per step then needs
   // no separate accumulation kernels (torch's `.grad += new`: 976 B per Gaussian and view against 488 here)
@@ -754,7 +759,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
   constexpr int KS = RAW ? (KH > 0 ? KH : 1) : K;   // width of the rows that go through LDS
   __shared__ float stage[RowStage<KS>::LDS_FLOATS];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  float sh[JW ? 1 : K], gsh[K];
+  float sh[JW ? 1 : K], gsh[POSE_ONLY ? 1 : K];
   if constexpr (!JW) {
     if constexpr (RAW) {
       if constexpr (KH > 0) {
@@ -767,8 +772,10 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
       else if (i < n) load_sh_row<K>(shs + (size_t)K * i, sh);
     }
   }
+  if constexpr (!POSE_ONLY) {
 #pragma unroll
-  for (int k = 0; k < K; ++k) gsh[k] = 0.f;
+    for (int k = 0; k < K; ++k) gsh[k] = 0.f;
+  }
   f3 gcol_out = {0.f, 0.f, 0.f};
   // POSE: this lane's share of the camera gradient, {dL/dRcw [3][3], dL/dtcw [3], dL/dtwc [3]}
   float pg[POSE ? 15 : 1];
@@ -788,11 +795,11 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     float W[9];
     if constexpr (JW) load_row<9>(dcolor_dpws + 9 * (size_t)i, W);
     float al_raw = 0.f;   // (AA without RAW: the activated alpha)
-    if constexpr (RAW || AA) al_raw = alphas[i];
+    if constexpr ((RAW && !POSE_ONLY) || AA) al_raw = alphas[i];
     float4 o_rot = make_float4(0.f, 0.f, 0.f, 0.f);
     f3 o_scale = {0.f, 0.f, 0.f}, o_pw = {0.f, 0.f, 0.f};
     float o_alpha = 0.f;
-    if (accum) {
+    if (!POSE_ONLY && accum) {
       o_rot = *reinterpret_cast<const float4*>(dL_drot + 4 * (size_t)i);
       o_scale = ld3(dL_dscale + 3 * (size_t)i);
       o_pw = ld3(dL_dpw + 3 * (size_t)i);
@@ -801,18 +808,18 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     const f3 gcol = {ga.y, ga.z, ga.w};
     const float gu0 = gb.x, gu1 = gb.y;
     const f3 gci = {gb.z, gb.w, gc.x};
-    if constexpr (AA) {
-      // (stored below, once comp is known; culled: comp = 0)
+    if constexpr (AA || POSE_ONLY) {
+      // (AA: stored below, once comp is known; culled: comp = 0)
     } else if constexpr (RAW) {
       const float al = act_alpha(al_raw);
       dL_dalpha[i] = ga.x * al * (1.f - al) + o_alpha;   // sigmoid'
     } else {
       dL_dalpha[i] = ga.x + o_alpha;
     }
-    dL_du[2 * (size_t)i] = gu0; dL_du[2 * (size_t)i + 1] = gu1;
+    if constexpr (!POSE_ONLY) { dL_du[2 * (size_t)i] = gu0; dL_du[2 * (size_t)i + 1] = gu1; }
     if (pp.near_cull && depth_i < EGS_MIN_DEPTH) {  // culled: never drawn, all gradients are zero
-      if constexpr (AA) dL_dalpha[i] = o_alpha;
-      if (!accum) {
+      if constexpr (AA && !POSE_ONLY) dL_dalpha[i] = o_alpha;
+      if (!POSE_ONLY && !accum) {   // (POSE_ONLY: pg stays zero, nothing else to write)
         st3(dL_dpw + 3 * (size_t)i, {0.f, 0.f, 0.f});
         st3(dL_dscale + 3 * (size_t)i, {0.f, 0.f, 0.f});
         st4(dL_drot + 4 * (size_t)i, {0.f, 0.f, 0.f, 0.f});
@@ -834,28 +841,32 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
       if constexpr (AA) {
         const float al = RAW ? act_alpha(al_raw) : al_raw;
         const float comp = aa_comp_vjp(c2.c, ga.x * al, g2);   // g2 += ga.x alpha dcomp/dcov2d
-        const float gal = ga.x * comp;
-        dL_dalpha[i] = (RAW ? gal * al * (1.f - al) : gal) + o_alpha;
+        if constexpr (!POSE_ONLY) {
+          const float gal = ga.x * comp;
+          dL_dalpha[i] = (RAW ? gal * al * (1.f - al) : gal) + o_alpha;
+        }
       }
       float J3[18], Jp[9];
       cov2d_jac(c2, P.pc.z, Rcw, pp.fx, pp.fy, J3, Jp);
-      float g3[6];
+      if constexpr (!POSE_ONLY) {   // (POSE_ONLY: only Jp of the line above is used, J3 is dead code)
+        float g3[6];
 #pragma unroll
-      for (int k = 0; k < 6; ++k) g3[k] = g2[0] * J3[k] + g2[1] * J3[6 + k] + g2[2] * J3[12 + k];
-      q4 gq; f3 gs;
-      cov3d_vjp(c3, q, s, g3, gq, gs);
-      if constexpr (RAW) {   // through normalize: (g - q (q.g)) / |r|; through exp: g * scale
-        const float qg = q.x * gq.w + q.y * gq.x + q.z * gq.y + q.w * gq.z;
-        gq = {(gq.w - q.x * qg) / qnorm, (gq.x - q.y * qg) / qnorm, (gq.y - q.z * qg) / qnorm,
-              (gq.z - q.w * qg) / qnorm};
-        gs = {gs.x * s.x, gs.y * s.y, gs.z * s.z};
+        for (int k = 0; k < 6; ++k) g3[k] = g2[0] * J3[k] + g2[1] * J3[6 + k] + g2[2] * J3[12 + k];
+        q4 gq; f3 gs;
+        cov3d_vjp(c3, q, s, g3, gq, gs);
+        if constexpr (RAW) {   // through normalize: (g - q (q.g)) / |r|; through exp: g * scale
+          const float qg = q.x * gq.w + q.y * gq.x + q.z * gq.y + q.w * gq.z;
+          gq = {(gq.w - q.x * qg) / qnorm, (gq.x - q.y * qg) / qnorm, (gq.y - q.z * qg) / qnorm,
+                (gq.z - q.w * qg) / qnorm};
+          gs = {gs.x * s.x, gs.y * s.y, gs.z * s.z};
+        }
+        if (accum) {
+          gq = {gq.w + o_rot.x, gq.x + o_rot.y, gq.y + o_rot.z, gq.z + o_rot.w};
+          gs = {gs.x + o_scale.x, gs.y + o_scale.y, gs.z + o_scale.z};
+        }
+        st4(dL_drot + 4 * (size_t)i, gq);      // eq (3)
+        st3(dL_dscale + 3 * (size_t)i, gs);    // eq (4)
       }
-      if (accum) {
-        gq = {gq.w + o_rot.x, gq.x + o_rot.y, gq.y + o_rot.z, gq.z + o_rot.w};
-        gs = {gs.x + o_scale.x, gs.y + o_scale.y, gs.z + o_scale.z};
-      }
-      st4(dL_drot + 4 * (size_t)i, gq);      // eq (3)
-      st3(dL_dscale + 3 * (size_t)i, gs);    // eq (4)
       float j00, j02, j11, j12;
       project_jac(P, pp.fx, pp.fy, j00, j02, j11, j12);
       f3 gpc = {gu0 * j00 + g2[0] * Jp[0] + g2[1] * Jp[3] + g2[2] * Jp[6],
@@ -866,19 +877,23 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
       const ShDir<NC> d = sh_basis_f<NC>(pw, twc);
       // eq (5): dL/dsh[c, rgb] = dL/dcolor[rgb] * basis[c]
       gcol_out = gcol;
-      if (!factored) {
+      if constexpr (!POSE_ONLY) {
+        if (!factored) {
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          gsh[3 * c] = gcol.x * d.B[c]; gsh[3 * c + 1] = gcol.y * d.B[c]; gsh[3 * c + 2] = gcol.z * d.B[c];
+          for (int c = 0; c < NC; ++c) {
+            gsh[3 * c] = gcol.x * d.B[c]; gsh[3 * c + 1] = gcol.y * d.B[c]; gsh[3 * c + 2] = gcol.z * d.B[c];
+          }
         }
       }
-      if constexpr (!JW) sh_jac_dpw<NC>(d, sh, W);
-      float* opw = dL_dpw + 3 * (size_t)i;  // eq (7)
-      const float opw_old[3] = {o_pw.x, o_pw.y, o_pw.z};
+      if constexpr (!JW) sh_jac_dpw<NC>(d, sh, W);   // (POSE_ONLY with JW: the basis d is never used)
+      if constexpr (!POSE_ONLY) {
+        float* opw = dL_dpw + 3 * (size_t)i;  // eq (7)
+        const float opw_old[3] = {o_pw.x, o_pw.y, o_pw.z};
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
-        opw[k] = gpc.x * Rcw[k] + gpc.y * Rcw[3 + k] + gpc.z * Rcw[6 + k] + gcol.x * W[k] + gcol.y * W[3 + k] +
-                 gcol.z * W[6 + k] + opw_old[k];
+        for (int k = 0; k < 3; ++k)
+          opw[k] = gpc.x * Rcw[k] + gpc.y * Rcw[3 + k] + gpc.z * Rcw[6 + k] + gcol.x * W[k] + gcol.y * W[3 + k] +
+                   gcol.z * W[6 + k] + opw_old[k];
+      }
       if constexpr (POSE) {
         // p_c = Rcw pw + tcw: dL/dtcw += gpc, dL/dRcw += gpc pw^T (projection, J(p_c) of cov2d, depth)
         const float gp[3] = {gpc.x, gpc.y, gpc.z}, pwv[3] = {pw.x, pw.y, pw.z};
@@ -922,6 +937,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
                                  pose_part[3][threadIdx.x]
                            : 0.f;
   }
+  if constexpr (POSE_ONLY) return;   // the partial row above is the instance's only output
   if (factored) {   // (a kernel argument: the whole workgroup leaves here)
     if (i < n) st3(dL_dsh + 3 * (size_t)i, gcol_out);
     // the view's camera centre behind the [N][3] block: the row format of egs_sh_grad_views (dL_dsh_high = its address)
@@ -1255,9 +1271,13 @@ extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width,
   const bool raw = (phase & EGS_FUSED_RAW) != 0;
   // the draw pass also sums |dL/du| per pixel into the records' slots 10 and 11 (the ABS instances of k_draw_bwd)
   const bool absgrad = (phase & EGS_BWD_ABSGRAD) != 0;
+  // only the camera gradient is wanted: the chain rule takes the POSE_ONLY instances, the seven per-Gaussian outputs
+  // may be NULL and are never written
+  const bool pose_only = (phase & EGS_BWD_POSE_ONLY) != 0;
   phase &= ~(EGS_BWD_KEEP_FORWARD_ORDER | EGS_BWD_ACCUMULATE | EGS_BWD_FACTORED_SH | EGS_FUSED_CULLED_LISTS |
-             EGS_FUSED_ANTIALIASED | EGS_FUSED_RAW | EGS_BWD_ABSGRAD);
+             EGS_FUSED_ANTIALIASED | EGS_FUSED_RAW | EGS_BWD_ABSGRAD | EGS_BWD_POSE_ONLY);
   EGS_CHECK_ARG(phase >= 0 && phase <= 2);
+  EGS_CHECK_ARG(!pose_only || (pose && phase == 0 && !accum && !absgrad));
   // (the caller reads the records afterwards: they must be its own; no ABS + EXTRA instance of the draw kernel)
   EGS_CHECK_ARG(!absgrad || ((grad_records || n == 0) && !extras));
   EGS_CHECK_ARG(raw || (!shs_high && !dloss_dshs_high));
@@ -1277,9 +1297,9 @@ extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width,
   EGS_CHECK_ARG(row_begin >= 0 && row_count >= 0 && row_begin + (int64_t)row_count <= n && row_begin % 256 == 0);
   EGS_CHECK_ARG(sh_dim == 3 || sh_dim == 12 || sh_dim == 27 || sh_dim == 48);
   if (n == 0) return 0;
-  EGS_CHECK_ARG(pws && rots && scales && shs && alphas && Rcw && tcw && twc && depths && ws && dloss_dpws &&
-                dloss_dshs && dloss_dalphas && dloss_dscales && dloss_drots && dloss_dus);
-  if (raw) EGS_CHECK_ARG(rec && (sh_dim == 3 || (shs_high && (dloss_dshs_high || factored))));
+  EGS_CHECK_ARG(pws && rots && scales && shs && alphas && Rcw && tcw && twc && depths && ws &&
+                (pose_only || (dloss_dpws && dloss_dshs && dloss_dalphas && dloss_dscales && dloss_drots && dloss_dus)));
+  if (raw) EGS_CHECK_ARG(rec && (sh_dim == 3 || (shs_high && (dloss_dshs_high || factored || pose_only))));
   if (ws_bytes < egs_splat_bwd_ws_bytes(n)) {
     set_error(EGS_ERR_WORKSPACE, "fused_backward workspace too small", __FILE__, __LINE__);
     return EGS_ERR_WORKSPACE;
@@ -1306,21 +1326,29 @@ extern "C" int egs_fused_backward(int n, int sh_dim, int64_t patches, int width,
   dim3 g(div_up(row_count, 256)), b(256);
   hipStream_t s = (hipStream_t)stream;
   float* pose_ws = pose ? (float*)pose->ws : nullptr;
-  // the profiler label names the flavour: AA over POSE over EXTRA
-  const char* label = aa       ? "k_preprocess_bwd_aa"
-                      : pose   ? "k_preprocess_bwd_pose"
-                      : extras ? "k_preprocess_bwd_extra"
-                               : "k_preprocess_bwd";
+  // the profiler label names the flavour: POSE_ONLY over AA over POSE over EXTRA
+  const char* label = pose_only ? "k_preprocess_bwd_pose_only"
+                      : aa      ? "k_preprocess_bwd_aa"
+                      : pose    ? "k_preprocess_bwd_pose"
+                      : extras  ? "k_preprocess_bwd_extra"
+                                : "k_preprocess_bwd";
   // the widths of the SH rows in (shs) and out (dloss_dshs): the low part alone for RAW / the factored gradient
   const int sh_in = raw ? 3 : sh_dim, sh_out = (factored || raw) ? 3 : sh_dim;
   // row_begin is a multiple of the workgroup's 256 rows: every offset pointer keeps its 16-B alignment
-  decltype(&k_preprocess_bwd<1, false, false, false, false, false>) kern = nullptr;   // flags -> template arguments
+  decltype(&k_preprocess_bwd<1, false, false, false, false, false, false>) kern = nullptr;   // flags -> template arguments
   with_sh_dim(sh_dim, [&](auto nc) {
-    with_bools(
-        [&](auto raw_c, auto jw, auto extra, auto pose_c, auto aa_c) {
-          kern = k_preprocess_bwd<nc.value, raw_c.value, jw.value, extra.value, pose_c.value, aa_c.value>;
-        },
-        raw, dcolor_dpws != nullptr, extras != nullptr, pose != nullptr, aa);
+    if (pose_only)   // (instantiated with POSE alone)
+      with_bools(
+          [&](auto raw_c, auto jw, auto extra, auto aa_c) {
+            kern = k_preprocess_bwd<nc.value, raw_c.value, jw.value, extra.value, true, aa_c.value, true>;
+          },
+          raw, dcolor_dpws != nullptr, extras != nullptr, aa);
+    else
+      with_bools(
+          [&](auto raw_c, auto jw, auto extra, auto pose_c, auto aa_c) {
+            kern = k_preprocess_bwd<nc.value, raw_c.value, jw.value, extra.value, pose_c.value, aa_c.value, false>;
+          },
+          raw, dcolor_dpws != nullptr, extras != nullptr, pose != nullptr, aa);
   });
   EGS_LAUNCH(label, kern, g, b, s, row_count, pp, pws + 3 * r0, rots + 4 * r0, scales + 3 * r0, shs + sh_in * r0,
              (raw && shs_high) ? shs_high + kh * r0 : shs_high, alphas + r0, Rcw, tcw, twc, depths + r0,

@@ -67,6 +67,10 @@ class RenderOptions:
     # by each backward, never accumulated, a densification statistic and not a gradient.  Not with depth / alpha /
     # background
     absgrad: bool = False
+    # pose nodes only (fused path): the map is frozen -- backward forms nothing but dL/dRcw and dL/dtcw
+    # (``EGS_BWD_POSE_ONLY``) and returns None for every Gaussian input and ``us``, whatever their requires_grad.  Chosen
+    # here, never inferred.  Not with accumulate, sh_sink, exchange or absgrad
+    pose_only: bool = False
 
     def __post_init__(self):
         if self.mode not in ("fused", "ops"):
@@ -97,6 +101,16 @@ class RenderOptions:
         if self.absgrad and self.has_extras():
             raise ValueError("RenderOptions: absgrad does not combine with depth / alpha / background (the draw kernel "
                              "has no instance for both)")
+        if not isinstance(self.pose_only, bool):
+            raise ValueError("RenderOptions.pose_only must be a bool, got %r" % (self.pose_only,))
+        if self.pose_only:
+            if self.mode != "fused":
+                raise ValueError("RenderOptions: pose_only needs mode='fused' (the pose nodes are the fused path)")
+            for on, name in ((self.accumulate, "accumulate"), (self.sh_sink is not None, "sh_sink"),
+                             (self.exchange is not None, "exchange"), (self.absgrad, "absgrad")):
+                if on:
+                    raise ValueError("RenderOptions: pose_only writes no per-Gaussian gradient and does not combine "
+                                     "with " + name)
         if self.mode == "ops" and self.has_extras():
             raise ValueError("RenderOptions: depth / alpha / background need mode='fused' (the seven-op structure mirrors "
                              "the reference, which renders the image only)")
@@ -137,6 +151,9 @@ def _fused_forward(ctx, leaves, cam, us=None):
     rots_raw) -- through ``cam``, saves them for ``_fused_backward`` and returns the node's outputs.  ``us``: the
     node's ``us`` input, on which ``RenderOptions.absgrad`` delivers its statistic"""
     o = ctx.opts
+    if o is not None and o.pose_only and not isinstance(cam, _PoseCamera):
+        raise ValueError("RenderOptions.pose_only is for GSPoseFunction / GSRawPoseFunction (this node has no pose "
+                         "gradient to return)")
     ctx.extras = None if o is None else o.extras()
     ctx.us_ref = None
     if o is not None and o.absgrad:
@@ -170,6 +187,14 @@ def _fused_backward(ctx, dloss_dgammas, rest, pose=False):
     leaves = ctx.saved_tensors
     k = len(leaves)
     pws, sh, others = leaves[0], leaves[1:k - 3], leaves[k - 3:]    # sh: (shs,) or (low_shs, high_shs)
+    if o is not None and o.pose_only:       # (a pose node: _fused_forward refuses the option elsewhere)
+        cam = ctx.cam
+        dRcw, dtcw = _fused.backward(
+            pws, sh[0], *others, cam, ctx.state, dloss_dgammas.contiguous(), high_shs=sh[1] if len(sh) == 2 else None,
+            exchange=None, dloss_ddepth=None if dd is None else dd.contiguous(),
+            dloss_dalpha=None if da is None else da.contiguous(), pose=(cam.Rcw, cam.tcw), pose_only=True)
+        return (None,) * (k + 1) + (dRcw if ctx.needs_input_grad[k + 1] else None,
+                                    dtcw if ctx.needs_input_grad[k + 2] else None) + (None,) * (ctx.n_inputs - k - 3)
     exchange = None if (pose or o is None) else o.exchange
     # a training step that keeps its SH gradient factored (dist_views.FactoredShGrad): this view leaves dL/dcolour
     # [N,3] in the sink, autograd gets None for the SH inputs, the others go on as usual

@@ -51,6 +51,7 @@ SEG_SPECULATE = os.environ.get("EGS_SEG_SPECULATE", "auto")
 ACCUMULATE = 64           # include/egs_hip.h EGS_BWD_ACCUMULATE
 FACTORED_SH = 128         # include/egs_hip.h EGS_BWD_FACTORED_SH
 ABSGRAD = 1024            # include/egs_hip.h EGS_BWD_ABSGRAD
+POSE_ONLY = 2048          # include/egs_hip.h EGS_BWD_POSE_ONLY
 # the render's flags (FusedState.flags): egs_fused_forward's `flags`, OR-ed into every egs_fused_backward phase
 CULLED_LISTS = 32         # include/egs_hip.h EGS_FUSED_CULLED_LISTS
 ANTIALIASED = 256         # include/egs_hip.h EGS_FUSED_ANTIALIASED
@@ -399,7 +400,8 @@ def accumulation_targets(leaves, node_ctx=None, count=None, explicit=None):
 
 
 def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, high_shs=None, accumulate=None,
-             sh_sink=None, exchange=DEFAULT, dloss_ddepth=None, dloss_dalpha=None, pose=None, absgrad=False):
+             sh_sink=None, exchange=DEFAULT, dloss_ddepth=None, dloss_dalpha=None, pose=None, absgrad=False,
+             pose_only=False):
     """-> (dloss_dpws[N,3], dloss_dshs[N,K], dloss_dalphas[N,1], dloss_dscales[N,3],
            dloss_drots[N,4], dloss_dus[N,2])  -- the gradient tuple of gsmodel.py:87-93.
     With ``high_shs`` (raw tensors, see ``forward``): -> (dpws, dlow_shs[N,3], dhigh_shs[N,K-3],
@@ -417,7 +419,10 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     An anti-aliased render (``forward(..., antialiased=True)``, recorded in ``S.flags``) takes the AA chain rule.
     ``absgrad``: the draw pass also sums the ABSOLUTE per-pixel terms of dloss_dus (``EGS_BWD_ABSGRAD``, DESIGN §3.10:
     AbsGS / gsplat's ``absgrad``) and ``dloss_dus_abs`` [N,2] -- this view's, never accumulated, a statistic and not a
-    gradient -- is appended to the result.  Not for a render with extras."""
+    gradient -- is appended to the result.  Not for a render with extras.
+    ``pose_only`` (``EGS_BWD_POSE_ONLY``; needs ``pose``): the map is frozen and only the camera moves --
+    the chain rule forms nothing but the pose gradient, no per-Gaussian gradient is allocated or written, and the
+    result is just (dloss_dRcw, dloss_dtcw).  Excludes ``accumulate``, ``sh_sink``, ``absgrad`` and an exchange."""
     raw = high_shs is not None
     pws = _chk(pws, "pws", torch.float32, (None, 3))
     n = pws.shape[0]
@@ -449,6 +454,14 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     f32 = torch.float32
     pg = None
     hook = _exchange_hook if exchange is DEFAULT else exchange      # (``exchange``: the call's own ChunkedExchange or None)
+    if pose_only:
+        if pose is None:
+            raise ValueError("fused.backward: pose_only needs pose=(Rcw, tcw)")
+        for v, name in ((accumulate, "accumulate"), (sh_sink, "sh_sink"), (absgrad or None, "absgrad"),
+                        (hook, "a ChunkedExchange")):
+            if v is not None:
+                raise ValueError("fused.backward: pose_only writes no per-Gaussian gradient and does not combine with "
+                                 + name)
     if pose is not None:
         if hook is not None:
             raise ValueError("fused.backward: a pose gradient cannot go with a ChunkedExchange (the chunked chain rule "
@@ -467,7 +480,9 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     widths = [3, 3, K - 3, 1, 3, 4] if raw else [3, K, 1, 3, 4]
     if sh_sink is not None:
         widths = [3, 1, 3, 4]
-    if accumulate is not None:
+    if pose_only:                     # nothing per Gaussian: the seven output pointers go down as NULL
+        parts = [None] * len(widths)
+    elif accumulate is not None:
         parts = [g.view(n, w) for g, w in zip(accumulate, widths)]
     else:
         starts, at = [], 0
@@ -498,7 +513,7 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
     else:
         dpws, dshs, dalphas, dscales, drots = parts
         dhigh = None
-    dus = torch.empty((n, 2), dtype=f32, device=dev)
+    dus = None if pose_only else torch.empty((n, 2), dtype=f32, device=dev)
     ws_bytes = lib.egs_fused_backward_ws_bytes(n)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     st = _stream()
@@ -527,6 +542,9 @@ def backward(pws, shs, alphas, scales, rots, cam, S: FusedState, dloss_dgammas, 
         keep |= FACTORED_SH
     if absgrad:
         keep |= ABSGRAD               # (a bit of the draw pass: phases 0 and 1)
+    if pose_only:
+        launch(POSE_ONLY | keep, 0, n)
+        return dRcw, dtcw
     if hook is not None and sh_sink is not None:
         raise RuntimeError("fused.backward: sh_sink and an attached ChunkedExchange exclude each other")
     chunks = hook.chunks if hook is not None else 1

@@ -33,7 +33,9 @@ import torch.distributed as dist
 from . import dist_views as DV
 from . import fused as _fused
 from .density import DensityControl, expon_lr
-from .function import Camera, GSFunction, GSRawFunction, RenderOptions
+from . import pose as _pose
+from .function import (Camera, GSFunction, GSPoseFunction, GSRawFunction, GSRawPoseFunction,
+                       RenderOptions)
 from .loss import gau_loss, gau_loss_with_grad
 from .optim import FusedAdam, adam_groups
 from .scene import gsdata_type
@@ -77,13 +79,25 @@ class Trainer:
     def __init__(self, scene, cameras: Sequence, gt_images: Sequence[torch.Tensor], max_steps: int,
                  scene_size: float = 1.0, device="cuda", fused_adam: bool = True, seed: int = 0,
                  fused_activations: bool = True, view_streams: int = 4, factored_sh: bool = True, mode: str = "fused",
-                 antialiased: bool = False, absgrad: bool = False, grad_threshold: float = None):
+                 antialiased: bool = False, absgrad: bool = False, grad_threshold: float = None,
+                 pose_opt: bool = False, pose_lr=(_pose.LR_ROT, _pose.LR_TRANS)):
+        """``pose_opt``: also refine the camera poses (fused path only).  Every camera gets a twist on its
+        stored pose (``pose.PoseTable``), every view renders through a pose node, and after the optimizer step the
+        twists of the cameras rendered in the step take a per-row Adam step.  ``pose_lr`` = (rotation step in radians,
+        translation step as a fraction of the camera distance); the defaults are those of examples/pose_refine.py --
+        found for frozen-map refinement on a synthetic scene and NOT tuned for joint training, which nobody has
+        measured.  With ``pose_opt`` the views of one ``step`` must be distinct cameras (a twist takes one Adam step
+        per optimizer step; ``ValueError`` otherwise -- ``fit`` draws from a permutation and never repeats one).
+        Without ``pose_opt`` nothing in a step differs: no pose node, no extra tensor."""
         self.device = device
         # how THIS trainer's renders are evaluated (function.RenderOptions.mode; "ops" needs fused_activations=False):
         # carried by every call, never by a process-wide switch -- two trainers in one process may differ
         self.mode = mode
         if mode != "fused" and fused_activations:
             raise ValueError("Trainer(mode=%r) needs fused_activations=False (GSRawFunction is the fused path)" % (mode,))
+        if pose_opt and mode != "fused":
+            raise ValueError("Trainer(pose_opt=True) needs mode='fused' (the pose nodes are the fused path), got %r"
+                             % (mode,))
         # anti-aliased training (RenderOptions.antialiased, DESIGN §3.9; fused path only): every render of a step
         self.antialiased = bool(antialiased)
         # densify on the ABSOLUTE screen-space gradient (RenderOptions.absgrad, DESIGN §3.10; fused path only): the
@@ -118,6 +132,12 @@ class Trainer:
         self.grad_accum = torch.zeros(n, device=device)             # gsmodel.py:214-230 statistics
         self.vis_count = torch.zeros(n, dtype=torch.int32, device=device)
         self.redone_steps = 0        # steps rendered twice because a view outgrew the enqueue-ahead buffers
+        self.pose_opt = bool(pose_opt)
+        self.pose_table = self.pose_grad = None
+        if self.pose_opt:
+            self.pose_table = _pose.PoseTable(self.cams, device, lr_rot=pose_lr[0], lr_trans=pose_lr[1])
+            # dL/dtwist of the step, dense [V,6]: the rows of the views this rank rendered, zero elsewhere
+            self.pose_grad = torch.zeros((len(self.cams), 6), device=device)
 
     _KEYS = ("pws", "low_shs", "high_shs", "alphas_raw", "scales_raw", "rots_raw")
 
@@ -154,7 +174,17 @@ class Trainer:
             with (vs.lane(i) if vs is not None else contextlib.nullcontext(None)) as lv:
                 p = dict(zip(self._KEYS, lv)) if lv is not None else self.params
                 us = self._us_leaf(k, n)                                             # gsmodel.py:198-199
-                if self.fused_activations:
+                tw = None
+                if self.pose_opt:     # the view's camera: its stored pose under its twist (a leaf of this render)
+                    tw = self.pose_table.leaf(v)
+                    Rcw, tcw = self.pose_table.pose(v, tw)
+                    if self.fused_activations:
+                        image, mask = GSRawPoseFunction.apply(p["pws"], p["low_shs"], p["high_shs"], p["alphas_raw"],
+                                                              p["scales_raw"], p["rots_raw"], us, Rcw, tcw, self.cams[v],
+                                                              opts)
+                    else:
+                        image, mask = GSPoseFunction.apply(*activate(p), us, Rcw, tcw, self.cams[v], opts)
+                elif self.fused_activations:
                     image, mask = GSRawFunction.apply(p["pws"], p["low_shs"], p["high_shs"], p["alphas_raw"],
                                                       p["scales_raw"], p["rots_raw"], us, self.cams[v], opts)
                 else:
@@ -163,6 +193,8 @@ class Trainer:
                 # scaled dL/dimage themselves, backward starts at the image
                 stats, dimage = gau_loss_with_grad(image.detach(), self.gts[v], grad_scale=1.0 / n_views)
                 image.backward(dimage)
+                if tw is not None:      # (per view, never accumulated in the kernel; one row per camera)
+                    self.pose_grad[v] += tw.grad
                 loss_sum[k] += stats[0]
                 with torch.no_grad():                       # per-view ||dL/du|| (undo the 1/len scaling)
                     g = torch.norm((us.absgrad if self.absgrad else us.grad) * n_views, dim=-1)
@@ -186,8 +218,12 @@ class Trainer:
         if len(view_ids) < self.world:
             raise ValueError("step() got %d view(s) for %d ranks: every rank needs at least one view per step"
                              % (len(view_ids), self.world))
+        if self.pose_opt and len(set(view_ids)) != len(view_ids):
+            raise ValueError("step() with pose_opt: a camera appears twice in %r (its twist takes one step per step)"
+                             % (list(view_ids),))
         mine = [view_ids[i] for i in DV.views_for_rank(len(view_ids), self.rank, self.world)]
         self.opt.zero_grad(set_to_none=True)
+        self._clear_pose_grad()
         # The views are rendered with deferred validation: the host does not wait for a patch count inside the
         # step.  commit() (one wait for the binning stage of the last view, while its draw and backward
         # kernels are still queued) tells whether some view outgrew the buffers sized from earlier renders;
@@ -218,6 +254,7 @@ class Trainer:
         if incomplete:
             self.redone_steps += 1
             self.opt.zero_grad(set_to_none=True)
+            self._clear_pose_grad()
             if fx is not None:
                 fx.restart()
             loss_sum, gnorm, count = self._render_views(mine, len(view_ids), opts)   # validated render by render
@@ -234,17 +271,37 @@ class Trainer:
                 fx.finish(self.params["pws"], self.params["low_shs"], self.params["high_shs"], average=False)
             others = {k: v for k, v in self.params.items() if k not in ("low_shs", "high_shs")}
         if self.world > 1:   # sum over ranks of (sum over local views)/V == mean over all views
-            DV.allreduce_sum_(DV.coalesce_grads(list(others.values())) + [gnorm, count, loss_sum])
+            DV.allreduce_sum_(DV.coalesce_grads(list(others.values())) + [gnorm, count, loss_sum] +
+                              ([self.pose_grad] if self.pose_opt else []))
         self.grad_accum += gnorm
         self.vis_count += count
         if sh_rows is not None:
             self.opt.step(factored_sh=sh_rows)
         else:
             self.opt.step()
+        if self.pose_opt:       # the cameras of this step only: the others keep twist, moments and step count
+            self.pose_table.step(view_ids, self.pose_grad)
         self.density.update_pws_lr(self.opt)                                     # gsmodel.py:180-183, 332-338
         self.iteration += 1
         mean = loss_sum / len(view_ids)
         return float(mean) if sync else mean
+
+    def _clear_pose_grad(self):
+        """the pose gradients of a step start from zero -- also when the step is redone"""
+        if self.pose_grad is not None:
+            self.pose_grad.zero_()
+
+    def poses(self):
+        """-> (Rcw [V,3,3], tcw [V,3]): the current pose of every camera (the stored ones without ``pose_opt``)"""
+        if self.pose_table is None:
+            return torch.stack([c.Rcw for c in self.cams]), torch.stack([c.tcw for c in self.cams])
+        return self.pose_table.poses()
+
+    def save_poses(self, fn: str):
+        """The current camera poses as an ``.npz``: ``ids`` [V] (``Camera.id``), ``Rcw`` [V,3,3], ``tcw`` [V,3]."""
+        R, t = self.poses()
+        ids = np.asarray([getattr(c, "id", i) for i, c in enumerate(self.cams)])
+        np.savez(fn, ids=ids, Rcw=R.detach().cpu().numpy(), tcw=t.detach().cpu().numpy())
 
     def densify(self, verbose: bool = False):
         """Prune / clone / split on the statistics gathered since the last call (train.py:71-73 ->

@@ -2,10 +2,11 @@
 """Photometric camera pose refinement through ``GSPoseFunction``: render a target at a true pose, perturb the pose by a
 twist, and optimise the twist with Adam against the target image (the Gaussians stay fixed).
 
-    python examples/pose_refine.py [--n 20000] [--steps 150] [--deg 2.0] [--shift 0.05] [--sh-dim 12]
+    python examples/pose_refine.py [--n 20000] [--steps 150] [--deg 2.0] [--shift 0.05] [--sh-dim 12] [--pose-only]
 
 The twist (omega, rho) acts on the perturbed pose (R0, t0) as  R = exp([omega]x) R0,  t = exp([omega]x) t0 + rho,
-written in torch ops, so autograd carries dL/dRcw and dL/dtcw of the fused backward pass to the six twist parameters.
+written in torch ops (easygaussiansplatting_amd.pose), so autograd carries dL/dRcw and dL/dtcw of the fused backward pass
+to the six twist parameters.
 Prints the rotation error (degrees) and the translation error (relative to the camera distance) as it goes.
 """
 import argparse
@@ -16,24 +17,6 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np  # noqa: E402
-
-
-def hat(w):
-    import torch
-    z = torch.zeros((), dtype=w.dtype, device=w.device)
-    return torch.stack([torch.stack([z, -w[2], w[1]]), torch.stack([w[2], z, -w[0]]),
-                        torch.stack([-w[1], w[0], z])])
-
-
-def exp_so3(w):
-    """Rodrigues' formula in torch ops (differentiable, also at w = 0)"""
-    import torch
-    th2 = (w * w).sum()
-    th = torch.sqrt(th2 + 1e-24)
-    K = hat(w)
-    a = torch.where(th2 > 1e-12, torch.sin(th) / th, 1.0 - th2 / 6.0)
-    b = torch.where(th2 > 1e-12, (1.0 - torch.cos(th)) / (th2 + 1e-24), 0.5 - th2 / 24.0)
-    return torch.eye(3, dtype=w.dtype, device=w.device) + a * K + b * (K @ K)
 
 
 def pose_error(R, t, R_true, t_true, dist):
@@ -50,11 +33,14 @@ def make_scene(n=20_000, width=320, height=240, sh_dim=12, seed=0):
     return sc
 
 
-def refine(sc, steps=150, deg=2.0, shift=0.05, lr_rot=2e-3, lr_trans=4e-3, decay=0.98, seed=0, log=None):
-    """Perturb the scene camera by a twist of ``deg`` degrees and ``shift`` x the camera distance, optimise it back.
+def refine(sc, steps=150, deg=2.0, shift=0.05, lr_rot=2e-3, lr_trans=4e-3, decay=0.98, seed=0, log=None,
+           pose_only=False):
+    """Perturb the scene camera by a twist of ``deg`` degrees and ``shift`` x the camera distance, optimise it back
+    (``pose.refine_pose``).  ``pose_only``: the backward pass forms the camera gradient alone.
     -> list of (step, rotation error deg, translation error rel) from before the first step to after the last."""
     import torch
     from easygaussiansplatting_amd.function import Camera, GSPoseFunction
+    from easygaussiansplatting_amd.pose import exp_so3, refine_pose
 
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
     cam = Camera.from_scene(sc.cam)
@@ -72,31 +58,14 @@ def refine(sc, steps=150, deg=2.0, shift=0.05, lr_rot=2e-3, lr_trans=4e-3, decay
     w0 = torch.tensor(ax * math.radians(deg), dtype=torch.float64)
     R0 = exp_so3(w0).numpy() @ R_true
     t0 = exp_so3(w0).numpy() @ t_true + dr * shift * dist
-    R0_t, t0_t = dev(R0), dev(t0)
-    omega = torch.zeros(3, device="cuda", requires_grad=True)
-    rho = torch.zeros(3, device="cuda", requires_grad=True)
-    opt = torch.optim.Adam([{"params": [omega], "lr": lr_rot}, {"params": [rho], "lr": lr_trans * dist}])
-    sched = torch.optim.lr_scheduler.ExponentialLR(opt, decay)
-
-    def current():
-        E = exp_so3(omega)
-        return E @ R0_t, E @ t0_t + rho
-
     hist = []
-    for step in range(steps + 1):
-        R, t = current()
-        hist.append((step,) + pose_error(R.detach().double().cpu().numpy(), t.detach().double().cpu().numpy(),
-                                          R_true, t_true, dist))
+
+    def record(step, R, t):
+        hist.append((step,) + pose_error(R.double().cpu().numpy(), t.double().cpu().numpy(), R_true, t_true, dist))
         if log is not None and (step % 10 == 0 or step == steps):
             log("step %3d  rotation error %.4f deg  translation error %.5f" % hist[-1])
-        if step == steps:
-            break
-        img, _ = GSPoseFunction.apply(*params, us, R, t, cam)
-        loss = (img - target).abs().mean()
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        sched.step()
+    refine_pose(params, cam, target, steps, lr_rot, lr_trans * dist, decay, Rcw=dev(R0), tcw=dev(t0),
+                pose_only=pose_only, callback=record)
     return hist
 
 
@@ -110,9 +79,11 @@ def main():
     ap.add_argument("--deg", type=float, default=2.0, help="rotation of the perturbation, degrees")
     ap.add_argument("--shift", type=float, default=0.05, help="translation of the perturbation / camera distance")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--pose-only", action="store_true",
+                    help="backward pass forms the camera gradient alone, no per-Gaussian gradients (DESIGN §3.8)")
     a = ap.parse_args()
     sc = make_scene(a.n, a.width, a.height, a.sh_dim, a.seed)
-    hist = refine(sc, a.steps, a.deg, a.shift, seed=a.seed, log=print)
+    hist = refine(sc, a.steps, a.deg, a.shift, seed=a.seed, log=print, pose_only=a.pose_only)
     (_, r0, t0), (_, r1, t1) = hist[0], hist[-1]
     print("rotation error %.4f -> %.4f deg (%.1fx), translation error %.5f -> %.5f (%.1fx)"
           % (r0, r1, r0 / max(r1, 1e-12), t0, t1, t0 / max(t1, 1e-12)))

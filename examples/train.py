@@ -30,6 +30,13 @@ def main():
                          "than the signed one: set --grad-threshold with it")
     ap.add_argument("--grad-threshold", type=float, default=None,
                     help="densification threshold on the accumulated screen-space gradient norm (default: 4e-7)")
+    ap.add_argument("--pose-opt", action="store_true",
+                    help="also refine the camera poses (a twist per camera, per-row Adam; DESIGN §3.8); the refined "
+                         "poses go to poses.npz.  The default rates come from frozen-map refinement on a synthetic "
+                         "scene and are not tuned for joint training")
+    ap.add_argument("--pose-lr-rot", type=float, default=2e-3, help="pose Adam step of the rotation, radians")
+    ap.add_argument("--pose-lr-trans", type=float, default=4e-3,
+                    help="pose Adam step of the translation, as a fraction of the camera distance")
     a = ap.parse_args()
 
     import torch
@@ -52,7 +59,8 @@ def main():
     views_per_step = world
     steps = (len(ds) // views_per_step) * a.epochs
     tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size, antialiased=a.antialiased,
-                 absgrad=a.absgrad, grad_threshold=a.grad_threshold)
+                 absgrad=a.absgrad, grad_threshold=a.grad_threshold, pose_opt=a.pose_opt,
+                 pose_lr=(a.pose_lr_rot, a.pose_lr_trans))
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]
@@ -67,6 +75,8 @@ def main():
             tr.save(os.path.join(a.out, "epoch%04d.npy" % epoch))
     if rank == 0:
         tr.save(os.path.join(a.out, "final.npy"))
+        if a.pose_opt:
+            tr.save_poses(os.path.join(a.out, "poses.npz"))
         print("Training is finished.")
     if world > 1:
         dist.destroy_process_group()

@@ -466,6 +466,15 @@ size_t egs_fused_backward_ws_bytes(int n);
 /* dloss_dus_abs[i] = grad_records[i][10..11] for all n records, after an egs_fused_backward with EGS_BWD_ABSGRAD
  * (zeros for a Gaussian no tile lists).  dloss_dus_abs: [N][2] floats, 8-B aligned. */
 int egs_grad_records_absgrad(int n, const float* grad_records, float* dloss_dus_abs /*[N][2]*/, void* stream);
+/* phase bit of egs_fused_backward: only the camera pose gradient is wanted (tracking / pose refinement against a frozen
+ * map).  The draw pass runs as always; the chain rule takes the POSE_ONLY instances of its kernel
+ * (k_preprocess_bwd_pose_only), which form the same per-Gaussian pose terms and the same fixed-order reduction as the
+ * pose instances and nothing else.  dloss_dpws, dloss_dshs, dloss_dhigh_shs, dloss_dalphas, dloss_dscales, dloss_drots
+ * and dloss_dus may be NULL and are never written, NULL or not (with EGS_FUSED_RAW dloss_dhigh_shs is not required).
+ * Needs pose != NULL and base phase 0; excludes EGS_BWD_ACCUMULATE, EGS_BWD_FACTORED_SH and EGS_BWD_ABSGRAD
+ * (EGS_ERR_BAD_ARG each, before any launch).  Composes with extras, the segment workspace, every EGS_FUSED_* bit and
+ * EGS_BWD_KEEP_FORWARD_ORDER.  n == 0: zeroed pose outputs, as without the bit. */
+#define EGS_BWD_POSE_ONLY 2048
 /* Camera pose gradients (`pose` of egs_fused_backward, nullable): dL/dRcw [3][3] (row-major) and dL/dtcw [3] of this
  * view -- always written, never added to, whatever EGS_BWD_ACCUMULATE says of the per-Gaussian outputs.  The camera
  * centre is treated as twc = -Rcw^T tcw (the rotation convention; equal to -inv(Rcw) tcw on a true rotation): the caller
@@ -487,7 +496,8 @@ size_t egs_pose_ws_bytes(int n);
  * OR-ed into the phase: the forward's EGS_FUSED_* flags (every chunk) and the EGS_BWD_* bits of this call.
  * Without EGS_FUSED_RAW, shs_high and dloss_dhigh_shs are NULL; with it the gradients are those of the raw tensors.
  * extras (nullable): the EgsExtras of the forward's draw (depths, background) with dloss_ddepth / dloss_dalpha;
- * dL/dz is added to dloss_dpws.  pose (nullable): also the camera pose gradient (EgsPoseGrad). */
+ * dL/dz is added to dloss_dpws.  pose (nullable): also the camera pose gradient (EgsPoseGrad); with
+ * EGS_BWD_POSE_ONLY nothing but it. */
 int egs_fused_backward(int n, int sh_dim, int64_t patches, int width, int height, const float* pws,
                        const float* rots, const float* scales, const float* shs, const float* shs_high,
                        const float* alphas, const float* Rcw, const float* tcw, const float* twc, float fx, float fy,

@@ -86,6 +86,7 @@ FOLDED = {
 }
 FOLDED_AGAIN = {
     "k_draw_bwd": (6, ["false"]),                                    # <BOX, FLOOR, CLAMP, RED, SEG, EXTRA> + ABS
+    "k_preprocess_bwd": (6, ["false"]),                              # <NC, RAW, JW, EXTRA, POSE, AA> + POSE_ONLY
 }
 
 

@@ -45,8 +45,8 @@ def kname(k):
         return ("k_draw_bwd_seg" if on(4) else "k_draw_bwd_extra" if on(5) else base) + ("_abs" if on(6) else "")
     if base == "k_preprocess_fwd":     # <NC, RAW, JW, AA>
         return "k_preprocess_fwd_aa" if on(3) else base
-    if base == "k_preprocess_bwd":     # <NC, RAW, JW, EXTRA, POSE, AA>: labelled AA over POSE over EXTRA
-        return base + ("_aa" if on(5) else "_pose" if on(4) else "_extra" if on(3) else "")
+    if base == "k_preprocess_bwd":     # <NC, RAW, JW, EXTRA, POSE, AA, POSE_ONLY>: POSE_ONLY over AA over POSE over EXTRA
+        return base + ("_pose_only" if on(6) else "_aa" if on(5) else "_pose" if on(4) else "_extra" if on(3) else "")
     if base == "k_viewer_prep":        # <NC, AA>
         return "k_viewer_prep_aa" if on(1) else base
     return base
