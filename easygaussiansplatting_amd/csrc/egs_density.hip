@@ -17,6 +17,7 @@
 // device RNG stream, gsmodel.py:274).
 #include "egs_common.h"
 #include "egs_gaussian_math.h"
+#include "egs_rng.h"   // counter-based normals: bit-compatible with easygaussiansplatting_amd/scene.py
 
 namespace egs {
 
@@ -107,26 +108,6 @@ __global__ __launch_bounds__(256) void k_densify_scan(int nblocks, uint32_t* __r
     totals[2] = (int32_t)sums[2];
     totals[3] = n - (int32_t)sums[0];
   }
-}
-
-// ---- counter-based normals: bit-compatible with easygaussiansplatting_amd/scene.py ------------------
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ double uniform01(uint64_t seed, uint64_t stream, uint64_t e) {
-  const uint64_t key = splitmix64(seed * 0x100000001B3ull + stream);
-  uint64_t bits = splitmix64(e ^ key);
-  bits = splitmix64(bits + key);
-  return (double)(bits >> 11) * (1.0 / 9007199254740992.0);
-}
-__device__ __forceinline__ float unit_normal(uint64_t seed, uint64_t stream, uint64_t e) {
-  double u1 = uniform01(seed, 2 * stream + 1000, e);
-  const double u2 = uniform01(seed, 2 * stream + 1001, e);
-  u1 = u1 > 1e-300 ? u1 : 1e-300;
-  return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925 * u2));
 }
 
 // ---- compaction ---------------------------------------------------------------------------------

@@ -195,3 +195,189 @@ class DensityControl:
                 g["lr"] = lr
         self.iteration += 1
         return lr
+
+
+class MCMCControl:
+    """Densification as in "3D Gaussian Splatting as Markov Chain Monte Carlo" (Kheradmand et al., NeurIPS 2024;
+    gsplat's ``MCMCStrategy``) on libegs_mcmc.so (include/egs_mcmc.h has the formulas):
+
+        ctl = MCMCControl(cap_max=1_000_000)
+        ctl.add_regularisers(params)                 # after backward (and the all-reduce), before optimizer.step()
+        ctl.inject_noise(params, lr_pws)             # after optimizer.step()
+        ctl.relocate(params, optimizer)              # every refinement: dead Gaussians move onto live ones ...
+        ctl.grow(params, optimizer)                  # ... and the model grows by 5 % up to cap_max
+
+    No prune, no alpha reset, no gradient threshold; the row count never exceeds ``cap_max``.  Every random number is
+    a pure function of ``(seed, round | step, index)``: replicas that hold the same parameters stay identical.
+    ``round`` counts the samplings done, ``step`` the noise injections; both only select RNG streams."""
+
+    def __init__(self, cap_max: int, seed: int = 0, min_opacity: float = 0.005, noise_lr: float = 5e5,
+                 opacity_reg: float = 0.01, scale_reg: float = 0.01, growth: float = 1.05):
+        if cap_max is None or int(cap_max) < 1:
+            raise ValueError("MCMCControl needs cap_max >= 1, got %r" % (cap_max,))
+        self.cap_max = int(cap_max)
+        self.seed = int(seed)
+        self.min_opacity = float(min_opacity)
+        self.noise_lr = float(noise_lr)
+        self.opacity_reg = float(opacity_reg)
+        self.scale_reg = float(scale_reg)
+        self.growth = float(growth)
+        self.round = 0
+        self.step = 0
+
+    # -- per step -----------------------------------------------------------------------------------------------
+    @staticmethod
+    def _checked(params):
+        cur = [params[k] for k in NAMES]
+        n = cur[0].shape[0]
+        for k, t, w in zip(NAMES, cur, (3, 3, None, 1, 3, 4)):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == n and
+                    (w is None or t.numel() == n * w)):
+                raise ValueError("parameter %s: expected contiguous float32 device tensor [%d, %s]" % (k, n, w))
+        return cur, n
+
+    @torch.no_grad()
+    def add_regularisers(self, params):
+        """``.grad`` of alphas_raw / scales_raw += d/d(raw) of opacity_reg mean(sigmoid(alphas_raw)) +
+        scale_reg mean(exp(scales_raw))."""
+        from . import _mcmclib
+        lib = _mcmclib.load()
+        a, s = params["alphas_raw"], params["scales_raw"]
+        for k, t in (("alphas_raw", a), ("scales_raw", s)):
+            if t.grad is None or not (t.grad.is_cuda and t.grad.dtype == torch.float32 and t.grad.is_contiguous()
+                                      and t.grad.shape == t.shape and t.is_contiguous()):
+                raise ValueError("add_regularisers: %s needs a contiguous float32 device .grad" % k)
+        _mcmclib.check(lib.egs_mcmc_add_reg_grad(a.shape[0], a.data_ptr(), s.data_ptr(), self.opacity_reg,
+                                                 self.scale_reg, a.grad.data_ptr(), s.grad.data_ptr(),
+                                                 torch.cuda.current_stream().cuda_stream))
+
+    @torch.no_grad()
+    def inject_noise(self, params, lr_pws: float, unit_noise: torch.Tensor = None):
+        """pws += Sigma (z w noise_lr lr_pws), w ~ 1 for transparent Gaussians and ~ 0 for opaque ones; ``z`` is
+        ``unit_noise`` [N,3] or ``scene.normal(seed, STREAM_NOISE + step, (N, 3))`` from the device generator."""
+        from . import _mcmclib
+        lib = _mcmclib.load()
+        cur, n = self._checked(params)
+        noise_ptr = None
+        if unit_noise is not None:
+            unit_noise = unit_noise.to(cur[0].device, torch.float32).contiguous()
+            if unit_noise.numel() != 3 * n:
+                raise ValueError("unit_noise must be [N, 3]")
+            noise_ptr = unit_noise.data_ptr()
+        _mcmclib.check(lib.egs_mcmc_add_noise(n, cur[0].data_ptr(), cur[3].data_ptr(), cur[4].data_ptr(),
+                                              cur[5].data_ptr(), noise_ptr, self.noise_lr, float(lr_pws), self.seed,
+                                              self.step, torch.cuda.current_stream().cuda_stream))
+        self.step += 1
+
+    # -- refinement ---------------------------------------------------------------------------------------------
+    @staticmethod
+    def _state(params, optimizer):
+        groups = {g["name"]: g for g in optimizer.param_groups}
+        missing = [k for k in NAMES if k not in params or k not in groups]
+        if missing:
+            raise ValueError("params/optimizer lack the groups %s" % missing)
+        states = [optimizer.state.get(groups[k]["params"][0], None) for k in NAMES]
+        has = [s is not None and "exp_avg" in s for s in states]
+        if any(has) and not all(has):
+            raise ValueError("optimizer state exists for some groups only")
+        return groups, states, all(has)
+
+    def _weights(self, lib, cur, n, relocation, stream):
+        """-> (weight [n], dead [n] uint8, n_dead, n_live): one 8-byte read-back"""
+        from . import _mcmclib
+        dev = cur[0].device
+        weight = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        dead = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int32, device=dev)
+        _mcmclib.check(lib.egs_mcmc_weights(n, cur[3].data_ptr(), self.min_opacity, int(relocation),
+                                            weight.data_ptr(), dead.data_ptr(), totals.data_ptr(), stream))
+        n_dead, n_live = (int(x) for x in totals.tolist())
+        return weight[:n], dead[:n], n_dead, n_live
+
+    def _sample(self, lib, weight, n_positive, n_draws, stream):
+        from . import _mcmclib
+        n = weight.shape[0]
+        ws = torch.empty(lib.egs_mcmc_sample_ws_bytes(n), dtype=torch.uint8, device=weight.device)
+        idx = torch.empty(n_draws, dtype=torch.int32, device=weight.device)
+        _mcmclib.check(lib.egs_mcmc_sample(n, weight.data_ptr(), n_positive, n_draws, self.seed, self.round,
+                                           idx.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+        self.round += 1
+        return idx
+
+    def _relocate(self, lib, tensors, moments, src, dst, stream):
+        from . import _mcmclib
+        n_rows = tensors[0].shape[0]
+        hw = tensors[2].shape[1] if tensors[2].dim() == 2 else 0
+        ws = torch.empty(lib.egs_mcmc_relocate_ws_bytes(n_rows), dtype=torch.uint8, device=tensors[0].device)
+        sets = [_pset(tensors)] + ([_pset(moments[0]), _pset(moments[1])] if moments is not None else [])
+        ptrs = [C.byref(x) for x in sets] + [None] * (3 - len(sets))
+        _mcmclib.check(lib.egs_mcmc_relocate(n_rows, src.shape[0], hw, src.data_ptr(), dst.data_ptr(), ptrs[0],
+                                             ptrs[1], ptrs[2], self.min_opacity, ws.data_ptr(), ws.numel(), stream))
+
+    @torch.no_grad()
+    def relocate(self, params, optimizer):
+        """Every dead Gaussian (opacity <= min_opacity) becomes a copy of a live one drawn with probability
+        proportional to its opacity; the copies and their source share the source's contribution (egs_mcmc.h
+        section 3).  In place; the moments of moved rows and of their sources are zeroed."""
+        from . import _mcmclib
+        lib = _mcmclib.load()
+        cur, n = self._checked(params)
+        _, states, has_state = self._state(params, optimizer)
+        stream = torch.cuda.current_stream().cuda_stream
+        weight, dead, n_dead, n_live = self._weights(lib, cur, n, True, stream)
+        if n_dead == 0:
+            return {"relocated": 0}
+        if n_live == 0:
+            raise RuntimeError("MCMCControl.relocate: no Gaussian is alive (every opacity <= %g)" % self.min_opacity)
+        src = self._sample(lib, weight, n_live, n_dead, stream)
+        dst = torch.nonzero(dead, as_tuple=False).reshape(-1).to(torch.int32)      # ascending
+        moments = None
+        if has_state:
+            moments = ([s["exp_avg"] for s in states], [s["exp_avg_sq"] for s in states])
+            for t in moments[0] + moments[1]:
+                if not t.is_contiguous():
+                    raise ValueError("optimizer moments must be contiguous")
+        self._relocate(lib, [t.data for t in cur], moments, src, dst, stream)
+        return {"relocated": n_dead}
+
+    @torch.no_grad()
+    def grow(self, params, optimizer):
+        """Append min(cap_max, int(growth n)) - n Gaussians: copies of rows drawn with probability proportional to
+        their opacity, corrected like relocated ones.  Mutates ``params`` and ``optimizer`` as
+        ``DensityControl.update_gaussian_density`` does."""
+        from . import _mcmclib
+        lib = _mcmclib.load()
+        cur, n = self._checked(params)
+        groups, states, has_state = self._state(params, optimizer)
+        n_new = min(self.cap_max, int(self.growth * n))
+        k = n_new - n
+        if k <= 0:
+            return {"added": 0, "total": n}
+        dev = cur[0].device
+        stream = torch.cuda.current_stream().cuda_stream
+        weight, _, _, _ = self._weights(lib, cur, n, False, stream)
+        src = self._sample(lib, weight, n, k, stream)
+        dst = torch.arange(n, n_new, dtype=torch.int32, device=dev)
+
+        def grown(t):
+            out = torch.empty((n_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+            out[:n].copy_(t)
+            return out
+        new = [grown(t.data) for t in cur]
+        moments = None
+        if has_state:
+            moments = ([grown(s["exp_avg"]) for s in states], [grown(s["exp_avg_sq"]) for s in states])
+        self._relocate(lib, new, moments, src, dst, stream)
+        # hand the new tensors to the optimizer as update_gaussian_density does
+        for i, name in enumerate(NAMES):
+            grp = groups[name]
+            old_p = grp["params"][0]
+            st = optimizer.state.pop(old_p, None)
+            p = torch.nn.Parameter(new[i].requires_grad_(True))
+            grp["params"][0] = p
+            if st is not None:
+                if moments is not None:
+                    st["exp_avg"], st["exp_avg_sq"] = moments[0][i], moments[1][i]
+                optimizer.state[p] = st
+            params[name] = p
+        return {"added": k, "total": n_new}

@@ -32,7 +32,7 @@ import torch.distributed as dist
 
 from . import dist_views as DV
 from . import fused as _fused
-from .density import DensityControl, expon_lr
+from .density import DensityControl, MCMCControl, expon_lr
 from . import pose as _pose
 from .function import (Camera, GSFunction, GSPoseFunction, GSRawFunction, GSRawPoseFunction,
                        RenderOptions)
@@ -80,8 +80,17 @@ class Trainer:
                  scene_size: float = 1.0, device="cuda", fused_adam: bool = True, seed: int = 0,
                  fused_activations: bool = True, view_streams: int = 4, factored_sh: bool = True, mode: str = "fused",
                  antialiased: bool = False, absgrad: bool = False, grad_threshold: float = None,
-                 pose_opt: bool = False, pose_lr=(_pose.LR_ROT, _pose.LR_TRANS)):
-        """``pose_opt``: also refine the camera poses (fused path only).  Every camera gets a twist on its
+                 pose_opt: bool = False, pose_lr=(_pose.LR_ROT, _pose.LR_TRANS), strategy: str = "default",
+                 cap_max: int = None, mcmc_options: dict = None):
+        """``strategy``: how Gaussians are added and removed.  "default" is the reference's clone / split / prune /
+        alpha reset (``density.DensityControl``).  "mcmc" (needs ``cap_max``, the hard limit on the number
+        of Gaussians) is ``density.MCMCControl``: every step adds the opacity / scale regularisers' gradient before the
+        optimizer step and a covariance-shaped position noise after it, ``densify`` relocates dead Gaussians and grows
+        the model by 5 % up to ``cap_max``, and ``fit`` never resets alpha.  ``mcmc_options``: further keyword arguments
+        of ``MCMCControl`` (min_opacity, noise_lr, opacity_reg, scale_reg, growth).  With "default" nothing in a step
+        differs.
+
+        ``pose_opt``: also refine the camera poses (fused path only).  Every camera gets a twist on its
         stored pose (``pose.PoseTable``), every view renders through a pose node, and after the optimizer step the
         twists of the cameras rendered in the step take a per-row Adam step.  ``pose_lr`` = (rotation step in radians,
         translation step as a fraction of the camera distance); the defaults are those of examples/pose_refine.py --
@@ -90,6 +99,10 @@ class Trainer:
         per optimizer step; ``ValueError`` otherwise -- ``fit`` draws from a permutation and never repeats one).
         Without ``pose_opt`` nothing in a step differs: no pose node, no extra tensor."""
         self.device = device
+        if strategy not in ("default", "mcmc"):
+            raise ValueError("Trainer(strategy=%r): expected 'default' or 'mcmc'" % (strategy,))
+        if strategy == "mcmc" and cap_max is None:
+            raise ValueError("Trainer(strategy='mcmc') needs cap_max, the hard limit on the number of Gaussians")
         # how THIS trainer's renders are evaluated (function.RenderOptions.mode; "ops" needs fused_activations=False):
         # carried by every call, never by a process-wide switch -- two trainers in one process may differ
         self.mode = mode
@@ -119,6 +132,8 @@ class Trainer:
         self.params = raw_params_from_scene(scene, device)
         self.opt = make_optimizer(self.params, fused_adam)
         self.density = DensityControl(scene_size, max_steps, seed)
+        self.strategy = strategy
+        self.mcmc = MCMCControl(cap_max, seed=seed, **(mcmc_options or {})) if strategy == "mcmc" else None
         if grad_threshold is not None:
             self.density.grad_threshold = float(grad_threshold)
         self.cams = [c if isinstance(c, Camera) else Camera.from_scene(c, device) for c in cameras]
@@ -275,10 +290,14 @@ class Trainer:
                               ([self.pose_grad] if self.pose_opt else []))
         self.grad_accum += gnorm
         self.vis_count += count
+        if self.mcmc is not None:     # after the all-reduce: identical on every rank
+            self.mcmc.add_regularisers(self.params)
         if sh_rows is not None:
             self.opt.step(factored_sh=sh_rows)
         else:
             self.opt.step()
+        if self.mcmc is not None:     # with the learning rate the step just used
+            self.mcmc.inject_noise(self.params, [g["lr"] for g in self.opt.param_groups if g["name"] == "pws"][0])
         if self.pose_opt:       # the cameras of this step only: the others keep twist, moments and step count
             self.pose_table.step(view_ids, self.pose_grad)
         self.density.update_pws_lr(self.opt)                                     # gsmodel.py:180-183, 332-338
@@ -305,9 +324,16 @@ class Trainer:
 
     def densify(self, verbose: bool = False):
         """Prune / clone / split on the statistics gathered since the last call (train.py:71-73 ->
-        gsmodel.py:232-317).  Identical on every rank (statistics are already all-reduced)."""
-        self.density.set_density_info(self.grad_accum, self.vis_count)
-        report = self.density.update_gaussian_density(self.params, self.opt, verbose=verbose)
+        gsmodel.py:232-317).  Identical on every rank (statistics are already all-reduced).  With strategy "mcmc":
+        relocate the dead Gaussians, then grow towards ``cap_max`` (the statistics are not used)."""
+        if self.mcmc is not None:
+            report = self.mcmc.relocate(self.params, self.opt)
+            report.update(self.mcmc.grow(self.params, self.opt))
+            if verbose:
+                print("mcmc density update report: relocated %(relocated)d added %(added)d total %(total)d" % report)
+        else:
+            self.density.set_density_info(self.grad_accum, self.vis_count)
+            report = self.density.update_gaussian_density(self.params, self.opt, verbose=verbose)
         n = self.params["pws"].shape[0]
         self.grad_accum = torch.zeros(n, device=self.device)
         self.vis_count = torch.zeros(n, dtype=torch.int32, device=self.device)
@@ -345,7 +371,7 @@ class Trainer:
             if 1 < epoch <= densify_until:
                 if epoch % densify_every == 0:
                     self.densify(verbose and self.rank == 0)
-                if epoch % reset_alpha_every == 0:
+                if epoch % reset_alpha_every == 0 and self.mcmc is None:     # (MCMC: dead Gaussians are relocated)
                     self.reset_alpha()
         return history
 

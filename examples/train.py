@@ -37,7 +37,13 @@ def main():
     ap.add_argument("--pose-lr-rot", type=float, default=2e-3, help="pose Adam step of the rotation, radians")
     ap.add_argument("--pose-lr-trans", type=float, default=4e-3,
                     help="pose Adam step of the translation, as a fraction of the camera distance")
+    ap.add_argument("--strategy", choices=("default", "mcmc"), default="default",
+                    help="densification: the reference's clone / split / prune / alpha reset, or MCMC relocation with "
+                         "a hard cap on the number of Gaussians (DESIGN §3.11; needs --cap-max)")
+    ap.add_argument("--cap-max", type=int, default=None, help="--strategy mcmc: the largest number of Gaussians")
     a = ap.parse_args()
+    if a.strategy == "mcmc" and a.cap_max is None:
+        ap.error("--strategy mcmc needs --cap-max")
 
     import torch
     import torch.distributed as dist
@@ -60,7 +66,7 @@ def main():
     steps = (len(ds) // views_per_step) * a.epochs
     tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size, antialiased=a.antialiased,
                  absgrad=a.absgrad, grad_threshold=a.grad_threshold, pose_opt=a.pose_opt,
-                 pose_lr=(a.pose_lr_rot, a.pose_lr_trans))
+                 pose_lr=(a.pose_lr_rot, a.pose_lr_trans), strategy=a.strategy, cap_max=a.cap_max)
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]
@@ -69,7 +75,7 @@ def main():
         if 1 < epoch <= 50:                                   # train.py:70-76
             if epoch % 5 == 0:
                 tr.densify(verbose=rank == 0)
-            if epoch % 15 == 0:
+            if epoch % 15 == 0 and a.strategy == "default":     # (MCMC relocates dead Gaussians instead)
                 tr.reset_alpha()
         if epoch % 10 == 0 and rank == 0:
             tr.save(os.path.join(a.out, "epoch%04d.npy" % epoch))
