@@ -58,12 +58,6 @@ struct ProfScope {
     ::egs::ProfScope ps__(name, stream);                                 \
     hipLaunchKernelGGL(kern, grid, block, 0, stream, __VA_ARGS__);       \
   } while (0)
-// same with `lds` bytes of dynamic LDS (used only to cap residency: see k_draw launch)
-#define EGS_LAUNCH_LDS(name, kern, grid, block, lds, stream, ...)        \
-  do {                                                                   \
-    ::egs::ProfScope ps__(name, stream);                                 \
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);     \
-  } while (0)
 
 // ---- runtime flags -> template arguments --------------------------------------
 // A kernel's flavour is a set of template arguments; a launch site turns its runtime flags into them once:

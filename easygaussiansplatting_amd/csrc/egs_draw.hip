@@ -4,38 +4,18 @@
 // reference by design.
 #include "egs_draw_device.h"
 
-#include <stdlib.h>
-
 namespace egs {
-
-// default dispatch order of the tiles for the forward / backward draw kernel (k_tile_order modes)
-#ifndef EGS_TILE_ORDER_F_DEFAULT
-#define EGS_TILE_ORDER_F_DEFAULT 1
-#endif
-#ifndef EGS_TILE_ORDER_B_DEFAULT
-#define EGS_TILE_ORDER_B_DEFAULT 1
-#endif
-#ifndef EGS_DRAWB_RED_DEFAULT
-#define EGS_DRAWB_RED_DEFAULT 7
-#endif
-// waves per SIMD the ABS instances of k_draw_bwd are compiled for (chosen by measurement)
-#ifndef EGS_DRAWB_ABS_WAVES
-#define EGS_DRAWB_ABS_WAVES 4
-#endif
 
 // Longest-list-first dispatch order of the tiles for the two draw kernels.  A tile is one wave whose run
 // time is proportional to its list length (0 ... ~2x the mean on the 1 M scene); workgroups are handed to
 // the SIMDs in index order, so with tiles in IMAGE order a launch ends with whichever SIMD drew the longest
 // lists while the others idle.  Sorted by length (descending) the long tiles start first and the short ones
-// fill the gaps (LPT scheduling); when every tile is resident at once (k_draw: 8 waves per SIMD) the
-// sorted order is dealt out in a serpentine of `period` slots so that every SIMD receives one tile of each
-// length stratum, alternately from its top and its bottom.
-//   mode 1: one global order           mode 2: global, serpentine
-//   mode 3: per XCD (tile row % 8 stays on XCD b % 8: horizontal neighbours share one L2), sorted
-//   mode 4: per XCD, serpentine
-// One workgroup: counting sort on (class, length) in LDS -- 8160 tiles take a few microseconds.
+// fill the gaps (LPT scheduling).  (Tried: the sorted order dealt out in a serpentine over the SIMDs, and sorted
+// per XCD with tile row % 8 kept on one XCD, with and without the serpentine -- none faster, DESIGN 3.3, docs/LAB.md.)
+// One workgroup: counting sort on the length in LDS -- 8160 tiles take a few microseconds.
 constexpr int TO_BINS = 1024;
 constexpr int TO_REGS = 16;    // tiles per thread whose (bin, rank) stay in registers between the two passes
+constexpr int TO_TAIL = 24;    // ... and parked in the order buffer itself: (TO_REGS + TO_TAIL) * 1024 = 40960 tiles (4K: 32400)
 // sort key of tile t: its list length, or -- `work` given -- the work the forward draw kernel measured for it
 __device__ __forceinline__ int tile_len(const int32_t* __restrict__ ranges, const int32_t* __restrict__ work, int t) {
   if (work) return work[t];
@@ -43,14 +23,13 @@ __device__ __forceinline__ int tile_len(const int32_t* __restrict__ ranges, cons
   return r.y - r.x;
 }
 __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__ ranges,
-                                                     const int32_t* __restrict__ work, int T, int gx, int mode,
-                                                     int period, int32_t* __restrict__ order, int ngrid,
+                                                     const int32_t* __restrict__ work, int T,
+                                                     int32_t* __restrict__ order,
                                                      const int32_t* __restrict__ walk = nullptr,
                                                      uint32_t* __restrict__ hint = nullptr) {
   // walk / hint (nullable): hint[1] receives the longest WALK of the camera's previous render (walk[T], next to its work),
   // hint[0] the longest list when the tiles are sorted by length -- page-locked words the host steers by (fused.py: long
   // walks take the segment path)
-  // 8192 bins in all: one class of 8192 (global modes) or eight of 1024 (per-XCD modes).
   // ONE LDS atomic per tile: the returning add that counts a bin also hands the tile its rank inside the bin
   // (arrival order -- any order inside a bin will do); after the scan of the bins its slot is start + rank.
   // LDS atomics retire about one lane per clock whatever the conflicts, so the kernel costs ~T cycles per pass:
@@ -58,12 +37,8 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
   constexpr int NB = 8 * TO_BINS;
   __shared__ uint32_t bins[NB];
   __shared__ uint32_t wsum[16];
-  __shared__ uint32_t cbase[9];
   const int tid = threadIdx.x;
-  const bool per_xcd = mode >= 3;
-  const int cbins = per_xcd ? TO_BINS : NB;                       // bins per class
-  // key -> bin: list lengths 1:1 (1:4 per XCD); the forward kernel's work measure is ~6x a length
-  const int shift = (per_xcd ? 2 : 0) + (work ? 2 : 0);
+  const int shift = work ? 2 : 0;   // key -> bin: list lengths 1:1; the forward kernel's work measure is ~6x a length
   int lenr[TO_REGS];     // all loads in flight at once: the kernel is a chain of latencies, not of bytes
 #pragma unroll
   for (int r = 0; r < TO_REGS; ++r) {
@@ -71,8 +46,6 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
     lenr[r] = t < T ? tile_len(ranges, work, t) : 0;
   }
   for (int i = tid; i < NB; i += 1024) bins[i] = 0u;
-  if (per_xcd)   // classes are padded to the largest one: slots without a tile stay -1
-    for (int i = tid; i < ngrid; i += 1024) order[i] = -1;
   if (hint) {
     int mx = 0;
     if (walk) { for (int t = tid; t < T; t += 1024) mx = max(mx, walk[t]); }
@@ -92,11 +65,7 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
     hint[walk ? 1 : 0] = mx;
   }
   __syncthreads();
-  auto key_of = [&](int t, int len) {
-    const int q = min(max(len, 0) >> shift, cbins - 1);
-    const int cls = per_xcd ? ((t / gx) & 7) : 0;
-    return cls * cbins + (cbins - 1 - q);
-  };
+  auto key_of = [&](int len) { return NB - 1 - min(max(len, 0) >> shift, NB - 1); };   // longest first
   // pass 1: (bin, rank) per tile, packed 13 + 19 bits (T < 2^19: checked by the host)
   uint32_t kr[TO_REGS];
 #pragma unroll
@@ -104,13 +73,13 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
     const int t = tid + r * 1024;
     kr[r] = 0u;
     if (t < T) {
-      const int key = key_of(t, lenr[r]);
+      const int key = key_of(lenr[r]);
       kr[r] = ((uint32_t)key << 19) | atomicAdd(&bins[key], 1u);
     }
   }
   // (tiles beyond TO_REGS * 1024 keep their (bin, rank) in the order buffer itself until pass 2)
   for (int t = tid + TO_REGS * 1024; t < T; t += 1024) {
-    const int key = key_of(t, tile_len(ranges, work, t));
+    const int key = key_of(tile_len(ranges, work, t));
     order[t] = (int32_t)(((uint32_t)key << 19) | atomicAdd(&bins[key], 1u));
   }
   __syncthreads();
@@ -128,24 +97,10 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
     for (int k = 0; k < 8; ++k) { bins[8 * tid + k] = ex; ex += v[k]; }
   }
   __syncthreads();
-  if (tid < 8) cbase[tid] = per_xcd ? bins[tid * TO_BINS] : (tid == 0 ? 0u : (uint32_t)T);
-  if (tid == 8) cbase[8] = (uint32_t)T;
-  __syncthreads();
-  const bool serp = (mode == 2 || mode == 4) && period > 0;
-  auto slot_of = [&](uint32_t packed) {
-    const int key = (int)(packed >> 19);
-    const int cls = key / cbins;
-    int r = (int)(bins[key] + (packed & 0x7FFFFu) - cbase[cls]);
-    if (serp) {
-      const int cnt = (int)(cbase[cls + 1] - cbase[cls]);
-      const int st = r / period, ps = r - st * period;
-      if (st & 1) r = st * period + (min(period, cnt - st * period) - 1 - ps);
-    }
-    return per_xcd ? 8 * r + cls : r;
-  };
+  // start of the bin + rank inside it: a permutation of [0, T)
+  auto slot_of = [&](uint32_t packed) { return (int)(bins[packed >> 19] + (packed & 0x7FFFFu)); };
   // pass 2 for the tiles parked in the order buffer: read them ALL before any slot is written (a slot may be
   // another tile's parking place)
-  constexpr int TO_TAIL = 24;      // up to (TO_REGS + TO_TAIL) * 1024 = 40960 tiles (a 4K image has 32400)
   uint32_t tail[TO_TAIL];
 #pragma unroll
   for (int u = 0; u < TO_TAIL; ++u) {
@@ -153,26 +108,18 @@ __global__ __launch_bounds__(1024) void k_tile_order(const int32_t* __restrict__
     tail[u] = t < T ? (uint32_t)order[t] : 0u;
   }
   __syncthreads();
-  if (per_xcd) {   // the parking places go back to "no tile" before the real slots are written
-#pragma unroll
-    for (int u = 0; u < TO_TAIL; ++u) {
-      const int t = tid + (TO_REGS + u) * 1024;
-      if (t < T) order[t] = -1;
-    }
-    __syncthreads();
-  }
 #pragma unroll
   for (int r = 0; r < TO_REGS; ++r) {
     const int t = tid + r * 1024;
-    if (t < T) { const int slot = slot_of(kr[r]); if (slot < ngrid) order[slot] = t; }
+    if (t < T) order[slot_of(kr[r])] = t;
   }
 #pragma unroll
   for (int u = 0; u < TO_TAIL; ++u) {
     const int t = tid + (TO_REGS + u) * 1024;
-    if (t < T) { const int slot = slot_of(tail[u]); if (slot < ngrid) order[slot] = t; }
+    if (t < T) order[slot_of(tail[u])] = t;
   }
 }
-static_assert(TILE_ORDER_MAX_T == (TO_REGS + 24) * 1024, "what k_tile_order handles");
+static_assert(TILE_ORDER_MAX_T == (TO_REGS + TO_TAIL) * 1024, "what k_tile_order handles");
 
 // The per-tile work measure of k_draw (sum of the four blocks' largest contributor index + twice the tile's)
 // rebuilt from the `contrib` image, for a backward pass that was not handed the forward pass's record.
@@ -207,8 +154,6 @@ __global__ __launch_bounds__(64) void k_tile_walk(int W, int H, int gx, const in
   for (int d = 32; d >= 1; d >>= 1) mx = max(mx, __shfl_xor(mx, d, 64));
   if (lane == 0) walk[tile] = mx;
 }
-// capacity of an order buffer: the per-XCD modes pad every class to the largest one
-int tile_order_len(int gx, int gy) { return 8 * div_up(gy, 8) * gx; }
 
 // ============================================================================
 // draw: per-tile front-to-back blend                   (reference kernel.cu:152-271)
@@ -224,7 +169,7 @@ __device__ __forceinline__ int xcd_tile(int b, const DrawParams& p) {
   }
   if (p.map_mode == 0) return b < p.T ? b : -1;
   const int xcd = b & 7, k = b >> 3;
-  if (p.map_mode == 1) {
+  if (p.map_mode == 1) {   // (never set: make_draw_params picks 0 or 2)
     if (b >= p.T) return -1;
     const int q = p.T >> 3, r = p.T & 7;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
@@ -235,15 +180,8 @@ __device__ __forceinline__ int xcd_tile(int b, const DrawParams& p) {
   const int ty = xcd + 8 * (k / p.gx), tx = k % p.gx;
   return ty < p.gy ? ty * p.gx + tx : -1;
 }
-// Dynamic LDS requested only to CAP the number of resident tile-waves per CU (experiment knobs
-// EGS_DRAW_LDS_PAD / EGS_DRAWB_LDS_PAD, bytes): fewer resident waves let the dispatcher hand the
-// remaining tiles to whichever SIMD drains first (dynamic load balance).
-static size_t draw_lds_pad(int which) {
-  static const size_t pad[2] = {
-      [] { const char* e = getenv("EGS_DRAW_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }(),
-      [] { const char* e = getenv("EGS_DRAWB_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }()};
-  return pad[which];
-}
+// (Tried: dynamic LDS requested only to cap the resident tile-waves per CU, so that the dispatcher hands the remaining
+// tiles to whichever SIMD drains first -- no faster for either draw kernel, docs/LAB.md.)
 int draw_grid(const DrawParams& p) {
   if (p.order) return p.ngrid;
   return p.map_mode == 2 ? 8 * div_up(p.gy, 8) * p.gx : p.T;
@@ -576,27 +514,6 @@ __device__ __forceinline__ float odd_lanes_tail_abs(const float (&q)[11], float 
   EGS_MERGE_BANK(sa, sx, sy, "row_half_mirror", "0xa");
   return merge2<M1>(r, merge2<M2>(s8, sa, h2), h1);
 }
-template <int NQ>
-__device__ __forceinline__ float rows_to_lanes9(const float (&q)[NQ], int c16) {
-  const bool h8 = (c16 & 8) != 0, h4 = (c16 & 4) != 0, h2 = (c16 & 2) != 0, h1 = (c16 & 1) != 0;
-  constexpr int M8 = 0x140, M4 = 0x141, M2 = 0x4E, M1 = 0xB1;  // row_mirror, row_half_mirror, quad [2,3,0,1], [1,0,3,2]
-  const float p01 = merge2<M8>(q[0], q[1], h8), p23 = merge2<M8>(q[2], q[3], h8);
-  const float p45 = merge2<M8>(q[4], q[5], h8), p67 = merge2<M8>(q[6], q[7], h8);
-  if constexpr (NQ == 11) {
-    const float a = merge2<M4>(p01, p23, h4), b = merge2<M4>(p45, p67, h4);
-    return odd_lanes_tail_abs(q, merge2<M2>(a, b, h2), h2, h1);
-  } else if constexpr (NQ == 10) {
-    const float a = merge2<M4>(p01, p23, h4), b = merge2<M4>(p45, p67, h4);
-    return odd_lanes_tail(q, merge2<M2>(a, b, h2), h2, h1);
-  } else {
-    float s8 = q[8] + dpp_get<M8>(q[8]);
-    const float a = merge2<M4>(p01, p23, h4), b = merge2<M4>(p45, p67, h4);
-    s8 += dpp_get<M4>(s8);
-    const float r = merge2<M2>(a, b, h2);
-    s8 += dpp_get<M2>(s8);
-    return merge2<M1>(r, s8, h1);
-  }
-}
 
 // ---- the in-row stage without selects ----------------------------------------------------------------------
 // Measured on gfx950 (tools/ubench_calib.hip, cycles per wave instruction per SIMD): add / mul / fma 2.5 (full
@@ -605,8 +522,8 @@ __device__ __forceinline__ float rows_to_lanes9(const float (&q)[NQ], int c16) {
 // of a CU: moving the cross-row exchanges there was measured 10 % SLOWER, so they stay v_permlane swaps).
 // merge2 above costs two v_cndmask and a DPP add.  The first two levels split the row by lane bits 3 and 2 --
 // exactly what DPP's bank mask addresses (a bank = four consecutive lanes of a row): one DPP add for everybody,
-// one bank-masked DPP add for the lanes that reduce the second register; no select.
-// same result layout as rows_to_lanes9: totals in lanes {0, 8, 4, 12, 2, 10, 6, 14, odd} of every row
+// one bank-masked DPP add for the lanes that reduce the second register; no select.  (Tried: merge2 at every level,
+// slower, docs/LAB.md.)  Totals in lanes {0, 8, 4, 12, 2, 10, 6, 14, odd} of every row
 template <int NQ>
 __device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c16) {
   const bool h2 = (c16 & 2) != 0, h1 = (c16 & 1) != 0;
@@ -665,9 +582,10 @@ __device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c
 // different pixels on a large Gaussian cannot cancel.  cinv is the entry's sD[j] (a broadcast read), the two sums are
 // leaves 10 and 11 of the reduction and go out with the other nine, in the same atomic instruction, to the pad slots
 // gpack[i][10] and gpack[i][11] (the chain rule never reads them; egs_grad_records_absgrad copies them out).  A
-// statistic, not a gradient.  Occupancy: EGS_DRAWB_ABS_WAVES.
-template <bool BOX, bool FLOOR, bool CLAMP, int RED, bool SEG, bool EXTRA, bool ABS = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : (ABS ? EGS_DRAWB_ABS_WAVES : 5), 8))) void k_draw_bwd(DrawParams p, const int32_t* __restrict__ ranges,
+// statistic, not a gradient.  Occupancy: DRAWB_ABS_WAVES.
+constexpr int DRAWB_ABS_WAVES = 4;   // waves per SIMD the ABS instances are compiled for (chosen by measurement)
+template <bool BOX, bool FLOOR, bool CLAMP, bool SEG, bool EXTRA, bool ABS = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : (ABS ? DRAWB_ABS_WAVES : 5), 8))) void k_draw_bwd(DrawParams p, const int32_t* __restrict__ ranges,
                                                  const int32_t* __restrict__ gsid,
                                                  const float4* __restrict__ rec,
                                                  const float* __restrict__ final_tau,
@@ -679,9 +597,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
   __shared__ float4 sA[64], sB[64], sC[64], sD[64];  // sD = {cinv.x, cinv.y, cinv.z, gsid}
   __shared__ float4 szero[3];                        // a line of zeros (see the accumulator reset below)
   __shared__ float sZ[EXTRA ? 64 : 1];               // (never touched by the other instances: no LDS there)
-  constexpr bool ZLDS = (RED & 2) != 0, LAZY = (RED & 4) != 0;
   constexpr int NQ = EXTRA ? 10 : (ABS ? 11 : 9);
-  if (ZLDS && threadIdx.x < 3) szero[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (threadIdx.x < 3) szero[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
   const uint32_t zaddr = (uint32_t)(uintptr_t)szero;   // LDS byte offset of the zero line
   int tile, seg_lo = 0, seg_hi = 0x7fffffff;   // SEG: the entries [seg_lo, seg_hi) of the tile's list are this wave's
   size_t seg_state = 0;
@@ -844,7 +761,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
       bool any = false;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (ZLDS) {
+        {
           // The nine zeros come out of LDS: broadcast reads of a zero line cost the VALU nothing (nine v_mov_b32 or
           // five v_mov_b64 are 21 issue cycles per slot in a kernel that is VALU-issue bound; the LDS pipe idles).
           // Inline asm, because the compiler would hoist a plain load and hand out register copies again.  The
@@ -860,15 +777,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
           acc[e][0] = z0.x; acc[e][1] = z0.y; acc[e][2] = z0.z; acc[e][3] = z0.w;
           acc[e][4] = z1.x; acc[e][5] = z1.y; acc[e][6] = z1.z; acc[e][7] = z1.w;
           acc[e][8] = z2;
-        } else {  // nine zeros from five 64-bit moves (v_mov_b64 on gfx940+)
-#pragma unroll
-          for (int q = 0; q < 8; q += 2) {
-            unsigned long long z = 0ull;
-            asm volatile("" : "+v"(z));   // materialise the pair in VGPRs, keep it from being split into two constants
-            acc[e][q] = __uint_as_float((unsigned)z);
-            acc[e][q + 1] = __uint_as_float((unsigned)(z >> 32));
-          }
-          acc[e][8] = 0.f;
         }
         if constexpr (EXTRA) acc[e][NQ - 1] = 0.f;
         if constexpr (ABS) { acc[e][9] = 0.f; acc[e][10] = 0.f; }
@@ -893,37 +801,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
             iny[b] = (pyb[b] >= y0) && (pyb[b] < y1);
           }
         }
-        // LAZY: the exponent from scratch per evaluated block (7 full-rate instructions) instead of the separable
-        // form (14 per entry up front + 2 per block): most entries reach one or two of the four blocks.
+        // The exponent from scratch per evaluated block (7 full-rate instructions) instead of the separable form
+        // cxx[bx] + cyy[by] + cxy[bx] dy[by] (14 per entry up front + 2 per block; tried, slower, docs/LAB.md): most
+        // entries reach one or two of the four blocks.
         // (Measured and dropped: skipping the floor / clamp v_med3 for entries with a positive-definite conic and
         // alpha <= 0.989 behind a wave-uniform flag -- the two scalar branches cost more than the two half-rate
         // instructions they save: +1.5 %.)
-        float dx[2], dy[2], cxx[2], cxy[2], cyy[2];
-        if (!LAZY) {
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            dx[b] = A.x - fpx[b];
-            cxx[b] = A.z * dx[b] * dx[b];
-            cxy[b] = A.w * dx[b];
-            dy[b] = A.y - fpy[b];
-            cyy[b] = B.x * dy[b] * dy[b];
-          }
-        }
+        float dx[2], dy[2];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int bx = k & 1, by = k >> 1;
           if (!(reach & (1 << k))) continue;  // scalar branch: block culled or past its last contributor
-          float pw;
-          if (LAZY) {
-            dx[bx] = A.x - fpx[bx];
-            dy[by] = A.y - fpy[by];
-            float t = A.z * dx[bx];
-            t = fmaf(A.w, dy[by], t);
-            pw = t * dx[bx];
-            pw = fmaf(B.x * dy[by], dy[by], pw);
-          } else {
-            pw = cxx[bx] + cyy[by] + cxy[bx] * dy[by];
-          }
+          dx[bx] = A.x - fpx[bx];
+          dy[by] = A.y - fpy[by];
+          float t = A.z * dx[bx];
+          t = fmaf(A.w, dy[by], t);
+          float pw = t * dx[bx];
+          pw = fmaf(B.x * dy[by], dy[by], pw);
           bool hit = (i < cont[k]) && (pw >= C.w);  // kernel.cu:899,913
           if (BOX) hit = hit && inx[bx] && iny[by];
           if (hit) {
@@ -968,7 +862,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXTRA ? 4 : 
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
           rows[q] = rows_of4(acc[0][ORDER[q]], acc[1][ORDER[q]], acc[2][ORDER[q]], acc[3][ORDER[q]]);
-        const float v = (RED & 1) == 0 ? rows_to_lanes9(rows, c16) : rows_to_lanes9_bank(rows, c16);
+        const float v = rows_to_lanes9_bank(rows, c16);
         // row r of the wave holds the totals of slot e = {0,2,1,3}[r]
         const int row = lane >> 4;
         const int e = ((row & 1) << 1) | (row >> 1);
@@ -1023,12 +917,8 @@ DrawParams make_draw_params(int W, int H, const EgsPolicy* pol, bool backward) {
   p.T = p.gx * p.gy;
   // tile -> workgroup map, chosen by measurement (same-box A/B, 1 M Gaussians at 1080p): the forward kernel
   // is 2 % faster with tile rows interleaved over the XCDs (223 vs 227 us), the backward kernel 2.5 % faster
-  // with the plain map (580 vs 595 us).  EGS_TILE_MAP=0|1|2 overrides both (tuning knob).
-  static const int forced = [] {
-    const char* e = getenv("EGS_TILE_MAP");
-    return e ? atoi(e) : -1;
-  }();
-  p.map_mode = forced >= 0 ? forced : (backward ? 0 : 2);
+  // with the plain map (580 vs 595 us).
+  p.map_mode = backward ? 0 : 2;
   p.order = nullptr;
   p.ngrid = 0;
   p.zero_buf = nullptr;
@@ -1045,29 +935,15 @@ DrawParams make_draw_params(int W, int H, const EgsPolicy* pol, bool backward) {
   return p;
 }
 
-// Longest-list-first dispatch (k_tile_order) for one of the draw kernels: which = 0 forward, 1 backward.
-// Mode by measurement (same-box A/B at 1 M / 1080p); EGS_TILE_ORDER_F / _B = 0..4 and
-// EGS_TILE_SERP override (tuning knobs).
-int tile_order_mode(int which) {
-  static const int mode[2] = {
-      [] { const char* e = getenv("EGS_TILE_ORDER_F"); return e ? atoi(e) : EGS_TILE_ORDER_F_DEFAULT; }(),
-      [] { const char* e = getenv("EGS_TILE_ORDER_B"); return e ? atoi(e) : EGS_TILE_ORDER_B_DEFAULT; }()};
-  return mode[which];
-}
-int tile_order_enqueue(DrawParams& p, int which, int32_t* buf, size_t buf_len, const int32_t* ranges, hipStream_t s,
+// Longest-list-first dispatch (k_tile_order) for one of the draw kernels; without a buffer, or for an image of more
+// tiles than the kernel handles, the plain tile map stays.
+int tile_order_enqueue(DrawParams& p, int32_t* buf, size_t buf_len, const int32_t* ranges, hipStream_t s,
                        const int32_t* work, const int32_t* walk, uint32_t* hint) {
-  const int mode = tile_order_mode(which);
-  if (mode <= 0 || !buf) return 0;
-  const bool per_xcd = mode >= 3;
-  const int ngrid = per_xcd ? tile_order_len(p.gx, p.gy) : p.T;
-  if ((size_t)ngrid > buf_len || p.T > TILE_ORDER_MAX_T) return 0;   // (larger images keep the plain map)
-  static const int serp = [] { const char* e = getenv("EGS_TILE_SERP"); return e ? atoi(e) : 0; }();
-  const int period = serp > 0 ? serp : (per_xcd ? 128 : 1024);   // SIMDs per XCD / per chip
-  EGS_LAUNCH("k_tile_order", k_tile_order, dim3(1), dim3(1024), s, ranges, work, p.T, p.gx, mode, period, buf, ngrid,
-             walk, hint);
+  if (!buf || (size_t)p.T > buf_len || p.T > TILE_ORDER_MAX_T) return 0;
+  EGS_LAUNCH("k_tile_order", k_tile_order, dim3(1), dim3(1024), s, ranges, work, p.T, buf, walk, hint);
   EGS_LAUNCH_OK();
   p.order = buf;
-  p.ngrid = ngrid;
+  p.ngrid = p.T;
   return 0;
 }
 
@@ -1088,45 +964,29 @@ int launch_draw(const DrawParams& dp, const EgsPolicy* pol, int32_t* ranges, con
         kern = k_draw<box.value, flr.value, clamp.value, skip.value, extra.value>;
       },
       pol->footprint == 1, pol->maha_floor != 0, pol->alpha_clamp != 0, pol->alpha_skip > 0.f, ex != nullptr);
-  EGS_LAUNCH_LDS(ex ? "k_draw_extra" : "k_draw", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(0), s, dp, ranges, gsid,
-                 rec, image, contrib, final_tau, ex ? *ex : DrawExtras{});
+  EGS_LAUNCH(ex ? "k_draw_extra" : "k_draw", kern, dim3(draw_grid(dp)), dim3(64), s, dp, ranges, gsid, rec, image,
+             contrib, final_tau, ex ? *ex : DrawExtras{});
   EGS_LAUNCH_OK();
   return 0;
 }
 
-// ... backward draw.  ex (nullable): the render extras -- that flavour exists in the default reduction variant only
-// (EGS_DRAWB_RED is an A/B knob of the plain kernel)
+// ... backward draw.  ex (nullable): the render extras
 int launch_draw_bwd(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                     const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg, float* gpack,
                     const DrawExtras* ex, hipStream_t s, bool absgrad) {
-  // variants of the backward kernel (bit 0: in-row merges of the wave reduction with bank-masked DPP adds instead
-  // of selects; bit 1: accumulator zeros loaded from LDS instead of moved; bit 2: exponent per evaluated block);
-  // EGS_DRAWB_RED = 0 | 3 | 7 overrides
-  static const int red = [] { const char* e = getenv("EGS_DRAWB_RED"); return e ? atoi(e) : EGS_DRAWB_RED_DEFAULT; }();
   const bool box = pol->footprint == 1, flr = pol->maha_floor != 0, clamp = pol->alpha_clamp != 0;
   if (ex) {   // the flavour's own kernel argument: two pointer types
-    decltype(&k_draw_bwd<false, false, false, EGS_DRAWB_RED_DEFAULT, false, true>) kern = nullptr;
-    with_bools([&](auto b, auto f, auto c) { kern = k_draw_bwd<b.value, f.value, c.value, EGS_DRAWB_RED_DEFAULT, false, true>; },
-               box, flr, clamp);
-    EGS_LAUNCH_LDS("k_draw_bwd_extra", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), s, dp, ranges, gsid, rec,
-                   final_tau, contrib, dLdg, gpack, DrawBwdFlavour<true>{*ex});
-  } else if (absgrad) {   // (the default reduction variant only, as EXTRA)
-    decltype(&k_draw_bwd<false, false, false, EGS_DRAWB_RED_DEFAULT, false, false, true>) kern = nullptr;
-    with_bools([&](auto b, auto f, auto c) { kern = k_draw_bwd<b.value, f.value, c.value, EGS_DRAWB_RED_DEFAULT, false, false, true>; },
-               box, flr, clamp);
-    EGS_LAUNCH_LDS("k_draw_bwd_abs", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), s, dp, ranges, gsid, rec,
-                   final_tau, contrib, dLdg, gpack, DrawBwdFlavour<false>{});
+    decltype(&k_draw_bwd<false, false, false, false, true>) kern = nullptr;
+    with_bools([&](auto b, auto f, auto c) { kern = k_draw_bwd<b.value, f.value, c.value, false, true>; }, box, flr, clamp);
+    EGS_LAUNCH("k_draw_bwd_extra", kern, dim3(draw_grid(dp)), dim3(64), s, dp, ranges, gsid, rec, final_tau, contrib,
+               dLdg, gpack, DrawBwdFlavour<true>{*ex});
   } else {
-    decltype(&k_draw_bwd<false, false, false, 0, false, false>) kern = nullptr;
+    decltype(&k_draw_bwd<false, false, false, false, false>) kern = nullptr;
     with_bools(
-        [&](auto b, auto f, auto c) {
-          kern = red == 0   ? k_draw_bwd<b.value, f.value, c.value, 0, false, false>
-                 : red == 3 ? k_draw_bwd<b.value, f.value, c.value, 3, false, false>
-                            : k_draw_bwd<b.value, f.value, c.value, 7, false, false>;
-        },
-        box, flr, clamp);
-    EGS_LAUNCH_LDS("k_draw_bwd", kern, dim3(draw_grid(dp)), dim3(64), draw_lds_pad(1), s, dp, ranges, gsid, rec, final_tau,
-                   contrib, dLdg, gpack, DrawBwdFlavour<false>{});
+        [&](auto b, auto f, auto c, auto a) { kern = k_draw_bwd<b.value, f.value, c.value, false, false, a.value>; },
+        box, flr, clamp, absgrad);
+    EGS_LAUNCH(absgrad ? "k_draw_bwd_abs" : "k_draw_bwd", kern, dim3(draw_grid(dp)), dim3(64), s, dp, ranges, gsid, rec,
+               final_tau, contrib, dLdg, gpack, DrawBwdFlavour<false>{});
   }
   EGS_LAUNCH_OK();
   return 0;
@@ -1135,19 +995,11 @@ int launch_draw_bwd(const DrawParams& dp, const EgsPolicy* pol, const int32_t* r
 int launch_draw_bwd_seg(const DrawParams& dp, const EgsPolicy* pol, const int32_t* ranges, const int32_t* gsid,
                         const float4* rec, const float* final_tau, const int32_t* contrib, const float* dLdg,
                         float* gpack, const SegArgs& sga, int grid, hipStream_t s, bool absgrad) {
-  decltype(&k_draw_bwd<false, false, false, 7, true, false>) kern = nullptr;
-  if (absgrad) {
-    with_bools([&](auto flr, auto clamp) { kern = k_draw_bwd<false, flr.value, clamp.value, 7, true, false, true>; },
-               pol->maha_floor != 0, pol->alpha_clamp != 0);
-    EGS_LAUNCH("k_draw_bwd_seg_abs", kern, dim3(grid), dim3(64), s, dp, ranges, gsid, rec, final_tau, contrib, dLdg,
-               gpack, DrawBwdFlavour<false>{sga});
-    EGS_LAUNCH_OK();
-    return 0;
-  }
-  with_bools([&](auto flr, auto clamp) { kern = k_draw_bwd<false, flr.value, clamp.value, 7, true, false>; },
-             pol->maha_floor != 0, pol->alpha_clamp != 0);
-  EGS_LAUNCH("k_draw_bwd_seg", kern, dim3(grid), dim3(64), s, dp, ranges, gsid, rec, final_tau, contrib, dLdg, gpack,
-             DrawBwdFlavour<false>{sga});
+  decltype(&k_draw_bwd<false, false, false, true, false>) kern = nullptr;
+  with_bools([&](auto flr, auto clamp, auto a) { kern = k_draw_bwd<false, flr.value, clamp.value, true, false, a.value>; },
+             pol->maha_floor != 0, pol->alpha_clamp != 0, absgrad);
+  EGS_LAUNCH(absgrad ? "k_draw_bwd_seg_abs" : "k_draw_bwd_seg", kern, dim3(grid), dim3(64), s, dp, ranges, gsid, rec,
+             final_tau, contrib, dLdg, gpack, DrawBwdFlavour<false>{sga});
   EGS_LAUNCH_OK();
   return 0;
 }
@@ -1176,5 +1028,5 @@ extern "C" int egs_grad_records_absgrad(int n, const float* grad_records, float*
 // a caller-held tile_order buffer: [dispatch order of the forward draw | per-tile work it measured | walk (T ints each)]
 extern "C" size_t egs_tile_order_len(int width, int height) {
   const int gx = egs::div_up(width, EGS_TILE), gy = egs::div_up(height, EGS_TILE);
-  return (size_t)egs::tile_order_len(gx, gy) + 2 * (size_t)gx * gy;
+  return 3 * (size_t)gx * gy;
 }

@@ -51,16 +51,13 @@ __device__ __forceinline__ TileAt tile_at(int t, int gx, int gy, int H, int W) {
 // read 155 MB for the forward kernel's 50 MB of pixels and 281 MB for the gradient kernel's 125 (rocprofv3 --pmc).
 // Here every XCD walks a contiguous eighth of the tile list (row-major over channel, tile row, tile column), its
 // resident workgroups side by side: the ~96 tiles in flight on an XCD span three tile rows (1.5 MB of halo tiles).
-#ifndef EGS_LOSS_XCD_BANDS
-#define EGS_LOSS_XCD_BANDS 1
-#endif
 // (Eight XCDs and the b % 8 dispatch are MI355X's -- this library is built for gfx950 only, csrc/Makefile.  The walk is
 // CORRECT for any mapping of workgroups to dies: on a part with another die count the bands would merely stop matching
 // the L2s, i.e. fall back to what the strided walk did.)
 struct TileWalk { int t, end, step; };
 __device__ __forceinline__ TileWalk tile_walk(int ntiles) {
   const int b = blockIdx.x, G = gridDim.x;
-  if (!EGS_LOSS_XCD_BANDS || G < 16) return {b, ntiles, G};
+  if (G < 16) return {b, ntiles, G};
   const int xcd = b & 7, slot = b >> 3;
   const int per = (G - xcd + 7) >> 3;                       // workgroups that run on this XCD
   const int lo = (int)((long long)ntiles * xcd / 8), hi = (int)((long long)ntiles * (xcd + 1) / 8);

@@ -190,22 +190,12 @@ __global__ __launch_bounds__(256) void k_cov2d(int n, const float* __restrict__ 
 }
 
 // ---- sh2color                                         (reference kernel.cu:619-807)
-// A/B knobs: colour and dcolor/dpw in ONE pass over the SH row (sh_color_and_jac_dpw) in k_sh2color / in
-// k_preprocess_fwd<.., JW>.  Measured (round 4, same-box A/B): the training instance of k_preprocess_fwd drops from 82
-// to 60 VGPRs (5 -> 8 waves per SIMD) -- and gets SLOWER, 99 -> 110 us: more resident waves mean more SH rows competing
-// for the 32-KB L1 between the twelve row loads of a lane.  Off there.
-#ifndef EGS_SH_FUSED_JAC
-#define EGS_SH_FUSED_JAC 1
-#endif
-#ifndef EGS_SH_FUSED_JAC_PRE
-#define EGS_SH_FUSED_JAC_PRE 0
-#endif
-
-#ifndef EGS_SH2COLOR_WAVES     // A/B knob: minimum waves per SIMD of k_sh2color (106 VGPRs = 4 as compiled freely)
-#define EGS_SH2COLOR_WAVES 1
-#endif
+// Colour and dcolor/dpw come out of ONE pass over the SH row here (sh_color_and_jac_dpw).  (Tried: the same one pass
+// in k_preprocess_fwd<.., JW> -- 82 -> 60 VGPRs, 5 -> 8 waves per SIMD, and SLOWER, 99 -> 110 us: more resident waves
+// mean more SH rows competing for the 32-KB L1 between the twelve row loads of a lane; docs/LAB.md)
+constexpr int SH2COLOR_WAVES = 1;   // minimum waves per SIMD of k_sh2color (106 VGPRs = 4 as compiled freely)
 template <int NC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EGS_SH2COLOR_WAVES, 8))) void k_sh2color(int n, const float* __restrict__ shs,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SH2COLOR_WAVES, 8))) void k_sh2color(int n, const float* __restrict__ shs,
                                                   const float* __restrict__ pws,
                                                   const float* __restrict__ twc,
                                                   float* __restrict__ colors,
@@ -218,7 +208,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EGS_SH2COLO
   float col[3] = {0.f, 0.f, 0.f}, jp[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j) jp[j] = 0.f;
-#if EGS_SH_FUSED_JAC
   // Round 4: the basis row leaves FIRST (it depends on the direction alone), then ONE pass over the coefficients sums
   // colour and dcolor/ddir, re-evaluating each basis value where it is used: neither the 16 basis values nor the
   // consumed part of the SH row stay in registers (110 -> see DESIGN 3.1).
@@ -241,27 +230,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EGS_SH2COLO
   }
   rows_out<3>(col, colors, n, base, stage);
   if (jac) rows_out<9>(jp, dcolor_dpws, n, base, stage);
-#else
-  float B[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) B[c] = 0.f;
-  if (i < n) {   // colour has no depth test in the reference (kernel.cu:619-725)
-    float sh[K];
-    load_sh_row<K>(shs + (size_t)K * i, sh);
-    const ShDir<NC> d = sh_basis_f<NC>(ld3(pws + 3 * (size_t)i), twc);
-    sh_color_f<NC>(d, sh, col);
-    if (jac) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) B[c] = d.B[c];
-      sh_jac_dpw<NC>(d, sh, jp);
-    }
-  }
-  rows_out<3>(col, colors, n, base, stage);
-  if (jac) {
-    rows_out<NC>(B, dcolor_dshs, n, base, stage);
-    rows_out<9>(jp, dcolor_dpws, n, base, stage);
-  }
-#endif
 }
 
 // ---- inverse_cov2d                                    (reference kernel.cu:274-324)
@@ -401,7 +369,7 @@ __global__ __launch_bounds__(256) void k_chain_rule(
 struct PreParams {
   float fx, fy, cx, cy, limx, limy, det_eps, alpha_skip;
   int clamp_fov, near_cull, nan_cull, radius_mode, footprint, W, H;
-  int stage_in;   // experiment knob (EGS_PRE_STAGE_IN): k_preprocess_bwd also stages the SH rows it reads
+  int stage_in;   // always 0 (experiment, lost: k_preprocess_bwd also stages the SH rows it reads; docs/LAB.md)
 };
 
 // ---- activations of the raw training parameters (reference gsplat/utils.py:121-150) -------------
@@ -558,19 +526,13 @@ __device__ __forceinline__ void stage_span_out(const float* row, float* __restri
 // RAW: rots/scales/alphas are the un-activated tensors, shs = low_shs [N,3], shs_high = high_shs [N,K-3]
 // JW: also write dcolor/dpw (dcolor_dpws) for the backward pass -- a training render; the SH Jacobian keeps ~40 more
 // registers alive, so these instances are not pinned to 8 waves per SIMD
-// A/B knob: rotation / scale / opacity requested together with the position.  The unpinned JW instance then also
-// hoists all twelve SH loads (101 VGPRs, 5 waves per SIMD, ONE round trip per row instead of six): measured equal
-// to the 58-register form within the noise of three same-box pairs (0.860-0.868 ms per step either way) -- the
-// kernel is bound by the memory system's queues, not by the latency of a row.  Off.
-#ifndef EGS_PRE_EARLY_LOADS
-#define EGS_PRE_EARLY_LOADS 0
-#endif
-#ifndef EGS_PRE_JW_WAVES       // A/B knob: minimum waves per SIMD of the JW instances (register cap 512 / waves)
-#define EGS_PRE_JW_WAVES 1
-#endif
+// (Tried: rotation / scale / opacity requested together with the position, which makes the unpinned JW instance hoist
+// all twelve SH loads -- 101 VGPRs, one round trip per row instead of six -- and measures equal within noise,
+// 0.860-0.868 ms per step either way: the kernel is bound by the memory system's queues; docs/LAB.md.)
+constexpr int PRE_JW_WAVES = 1;   // minimum waves per SIMD of the JW instances (register cap 512 / waves)
 // AA (anti-aliased rendering): every Gaussian is binned and drawn with opacity alpha comp
 template <int NC, bool RAW, bool JW, bool AA>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (JW ? EGS_PRE_JW_WAVES : 8), 8))) void k_preprocess_fwd(int n, PreParams pp, const float* __restrict__ pws,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (JW ? PRE_JW_WAVES : 8), 8))) void k_preprocess_fwd(int n, PreParams pp, const float* __restrict__ pws,
                                                         const float* __restrict__ rots,
                                                         const float* __restrict__ scales,
                                                         const float* __restrict__ shs,
@@ -610,12 +572,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
   uint4 crec = make_uint4(0u, 0u, 0u, 0u);
   if (i < n) {
     const f3 pw = ld3(pws + 3 * (size_t)i);
-#if EGS_PRE_EARLY_LOADS
-    // (requested with the position, not after the colour: one dependent round trip less per row)
-    float4 q_in = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
-    f3 sc_in = ld3(scales + 3 * (size_t)i);
-    const float alpha_in = (rec || bo.br) ? alphas[i] : 0.f;
-#endif
     float col[3];
     {  // colour has no depth test in the reference (kernel.cu:619-725)
       if constexpr (RAW) {
@@ -624,15 +580,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
         load_sh_row<K>(shs + (size_t)K * i, sh);
       }
       const ShDir<NC> d = sh_basis_f<NC>(pw, twc);
-#if EGS_SH_FUSED_JAC_PRE
-      if constexpr (JW) sh_color_and_jac_dpw<NC>(d, sh, col, jw);
-      else sh_color_f<NC>(d, sh, col);
-      if (colors) st3(colors + 3 * (size_t)i, {col[0], col[1], col[2]});
-#else
       sh_color_f<NC>(d, sh, col);
       if (colors) st3(colors + 3 * (size_t)i, {col[0], col[1], col[2]});
       if constexpr (JW) sh_jac_dpw<NC>(d, sh, jw);
-#endif
     }
     const Proj P = project_f(pw, Rcw, tcw, pp.fx, pp.fy, pp.cx, pp.cy);
     float u0 = 0.f, u1 = 0.f, depth = EGS_BAD_MARKER, ci[3] = {0.f, 0.f, 0.f};
@@ -640,13 +590,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
     float aa_comp = 0.f;   // (AA: the opacity compensation; 0 for near-culled Gaussians)
     if (!(pp.near_cull && P.pc.z < EGS_MIN_DEPTH)) {
       u0 = P.u0; u1 = P.u1; depth = P.pc.z;
-#if EGS_PRE_EARLY_LOADS
-      float4 q = q_in;
-      f3 sc = sc_in;
-#else
       float4 q = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
       f3 sc = ld3(scales + 3 * (size_t)i);
-#endif
       if constexpr (RAW) { float nrm; q = act_rot(q, nrm); sc = act_scale(sc); }
       const Cov3 c3 = cov3d_f(q, sc);
       const Cov2 c2 = cov2d_f(c3.c, P.pc, Rcw, pp.fx, pp.fy, pp.limx, pp.limy, pp.clamp_fov);
@@ -658,11 +603,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
         radius_f(c2.c, pp.radius_mode, rx, ry);
       }
     }
-#if EGS_PRE_EARLY_LOADS
-    float alpha_act = (rec || bo.br) ? (RAW ? act_alpha(alpha_in) : alpha_in) : 0.f;
-#else
     float alpha_act = (rec || bo.br) ? (RAW ? act_alpha(alphas[i]) : alphas[i]) : 0.f;
-#endif
     // AA: the Gaussian is binned and drawn with the compensated opacity alpha comp (the records carry it)
     if constexpr (AA) alpha_act *= aa_comp;
     if (bo.br) {  // getRects + depth key of the binning stage, straight from registers (no k_bin_count pass)
@@ -1176,8 +1117,7 @@ static PreParams make_pre_params(const EgsPolicy* pol, float fx, float fy, float
   pp.footprint = pol->footprint; pp.W = width; pp.H = height;
   pp.clamp_fov = pol->fov_mode != 2; pp.near_cull = pol->near_cull; pp.nan_cull = pol->nan_cull;
   pp.radius_mode = pol->radius_mode;
-  static const int stage_in = [] { const char* e = getenv("EGS_PRE_STAGE_IN"); return e ? atoi(e) : 0; }();
-  pp.stage_in = stage_in;
+  pp.stage_in = 0;
   return pp;
 }
 
@@ -1221,16 +1161,14 @@ extern "C" int egs_fused_forward(int n, int sh_dim, const float* pws, const floa
   const BinParams bp = make_bin_params(width, height, pol, cull_lists);
   const PreParams pp = make_pre_params(pol, fx, fy, cx, cy, width, height);
   dim3 g(div_up(n, 256)), b(256);
-  // EGS_PRE_LDS_PAD (bytes of dynamic LDS, experiment knob): caps the resident workgroups per CU of this kernel
-  static const size_t lds_pad = [] { const char* e = getenv("EGS_PRE_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }();
+  // (tried: dynamic LDS to cap the resident workgroups per CU of this kernel at 4, 3, 2 -- no faster, docs/LAB.md)
   decltype(&k_preprocess_fwd<1, false, false, false>) kern = nullptr;   // flags -> template arguments
   with_sh_dim(sh_dim, [&](auto nc) {
     with_bools([&](auto raw_c, auto jw, auto aa_c) { kern = k_preprocess_fwd<nc.value, raw_c.value, jw.value, aa_c.value>; },
                raw, dcolor_dpws != nullptr, aa);
   });
-  EGS_LAUNCH_LDS(aa ? "k_preprocess_fwd_aa" : "k_preprocess_fwd", kern, g, b, lds_pad, s, n, pp, pws, rots, scales, shs,
-                 shs_high, alphas, Rcw, tcw, twc, us, depths, cinv2ds, colors, areas, (float4*)rec, bp, bo, visible,
-                 dcolor_dpws);
+  EGS_LAUNCH(aa ? "k_preprocess_fwd_aa" : "k_preprocess_fwd", kern, g, b, s, n, pp, pws, rots, scales, shs, shs_high,
+             alphas, Rcw, tcw, twc, us, depths, cinv2ds, colors, areas, (float4*)rec, bp, bo, visible, dcolor_dpws);
   EGS_LAUNCH_OK();
   // the kernel above already did getRects + depth keys (k_bin_count of egs_splat_bin)
   return splat_bin_after_count(n, key_bits_hint, ws_bin, ws_bin_bytes, total_patches, stream, host_totals);

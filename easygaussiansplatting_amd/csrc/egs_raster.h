@@ -77,7 +77,7 @@ struct DrawParams {
   int maha_floor, alpha_clamp;
   int nan_blend;  // EgsPolicy.nan_maha == 0: an entry whose conic or centre holds a NaN blends at min(0.99, alpha) everywhere
   int map_mode;  // 0: tile = block; 1: contiguous band per XCD; 2: tile rows interleaved over XCDs
-  // longest-list-first dispatch (k_tile_order): workgroup b draws tile order[b] (-1: padding) when set
+  // longest-list-first dispatch (k_tile_order): workgroup b draws tile order[b] when set
   const int32_t* order;
   int ngrid;     // entries of `order` (= workgroups launched)
   // k_draw only: buffer its workgroups zero on the side (the packed gradient records of the coming backward
@@ -107,11 +107,9 @@ struct DrawExtras {
   float bg[3];             // image += T_final * bg
 };
 int draw_grid(const DrawParams& p);
-// capacity of a dispatch-order buffer (the per-XCD modes pad every class to the largest one)
-int tile_order_len(int gx, int gy);
 constexpr int TILE_ORDER_MAX_T = (16 + 24) * 1024;   // what k_tile_order handles (larger images keep the plain tile map)
-int tile_order_mode(int which);                       // 0 forward, 1 backward
-int tile_order_enqueue(DrawParams& p, int which, int32_t* buf, size_t buf_len, const int32_t* ranges, hipStream_t s,
+// buf (T ints; NULL: no order, the plain tile map) receives the dispatch order and becomes p.order
+int tile_order_enqueue(DrawParams& p, int32_t* buf, size_t buf_len, const int32_t* ranges, hipStream_t s,
                        const int32_t* work = nullptr, const int32_t* walk = nullptr, uint32_t* hint = nullptr);
 // the per-tile work measure of k_draw rebuilt from `contrib` (work nullable: the walk alone)
 int tile_work_from_contrib(const DrawParams& p, const int32_t* contrib, int32_t* work, int32_t* walk, hipStream_t s);

@@ -14,10 +14,7 @@ namespace egs {
 constexpr int RS_THREADS = 256;
 // items per thread: 16 (4096-item tiles) for long arrays; 8 for short ones, where 4096-item tiles would
 // leave fewer workgroups than there are CUs (1 M depth keys = 245 tiles)
-#ifndef EGS_RS_SHORT           // A/B knob
-#define EGS_RS_SHORT (5 << 19)
-#endif
-constexpr int64_t RS_SHORT = EGS_RS_SHORT;         // <= 2.6 M items: 2048-item tiles (measured: 4 M patches prefer 4096)
+constexpr int64_t RS_SHORT = 5 << 19;              // <= 2.6 M items: 2048-item tiles (measured: 4 M patches prefer 4096)
 static int rs_ipt(int64_t n) { return n <= RS_SHORT ? 8 : 16; }
 
 // `maxkey` (nullable, device): upper bound of all keys.  A pass whose digit is 0 for every key

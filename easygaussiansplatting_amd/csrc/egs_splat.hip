@@ -22,7 +22,7 @@ struct DrawLayout {
 };
 static size_t draw_ws_bytes(int n, int64_t P, int width, int height) {
   const size_t N = (size_t)(n > 0 ? n : 1), PP = (size_t)(P > 0 ? P : 1);
-  const size_t ord = (size_t)tile_order_len(div_up(width, EGS_TILE), div_up(height, EGS_TILE));
+  const size_t ord = (size_t)div_up(width, EGS_TILE) * div_up(height, EGS_TILE);   // the tiles' dispatch order
   return 3 * align_up(PP * 4, 256) + align_up(N * 48, 256) + align_up(ord * 4, 256) + sort_ws_bytes(P) + 4096;
 }
 static bool draw_carve(void* ws, size_t bytes, int n, int64_t P, int width, int height, DrawLayout* L) {
@@ -32,7 +32,7 @@ static bool draw_carve(void* ws, size_t bytes, int n, int64_t P, int width, int 
   L->tkeys_alt = cv.take<uint32_t>(PP);
   L->gsid_alt = cv.take<uint32_t>(PP);
   L->rec = cv.take<float4>(3 * N);
-  L->order = cv.take<int32_t>((size_t)tile_order_len(div_up(width, EGS_TILE), div_up(height, EGS_TILE)));
+  L->order = cv.take<int32_t>((size_t)div_up(width, EGS_TILE) * div_up(height, EGS_TILE));
   return sort_ws_carve(cv, P, &L->sort) && cv.ok();
 }
 
@@ -104,42 +104,35 @@ int splat_bwd_packed(int n, int64_t patches, int width, int height, const EgsPol
     return launch_draw_bwd_seg(dp, pol, fwd.ranges, fwd.gsid, rec, fwd.final_tau, fwd.contrib, dloss_dgammas,
                                gpack, sga, grid, s, carry.absgrad);
   }
-  static const int by_work = [] { const char* e = getenv("EGS_DRAWB_BY_WORK"); return e ? atoi(e) : 1; }();
-  const bool same_mode = tile_order_mode(0) == tile_order_mode(1) && tile_order_mode(1) > 0;
-  if (carry.tile_order && carry.keep_forward_order && same_mode) {
+  if (carry.tile_order && (carry.keep_forward_order || (size_t)dp.T > BWD_ORDER_CAP)) {
     // the forward pass already dispatched by measured work (that of the camera's previous render, one step or
-    // one epoch old -- as good a key for this pass as for that one): no second k_tile_order (8 us)
+    // one epoch old -- as good a key for this pass as for that one): no second k_tile_order (8 us); nor for an
+    // image whose order does not fit the workspace, which keeps the forward pass's order too
     dp.order = carry.tile_order;
-    dp.ngrid = tile_order_mode(1) >= 3 ? tile_order_len(dp.gx, dp.gy) : dp.T;
-  } else if (carry.tile_order && by_work && tile_order_mode(1) > 0 &&
-             (size_t)tile_order_len(dp.gx, dp.gy) <= BWD_ORDER_CAP) {
+    dp.ngrid = dp.T;
+  } else if (carry.tile_order) {
     // the forward draw kernel left behind how far every tile walked its list: order the tiles by THAT (the list
     // length mis-ranks tiles whose pixels saturate early; simulated with the measured work of the 1 M scene:
     // makespan 1.11 x ideal by length, 1.03 x by work)
     int32_t* order = (int32_t*)((char*)ws + 2 * align_up((size_t)n * 48, 256));
-    const int32_t* wk = carry.tile_order + tile_order_len(dp.gx, dp.gy);      // [work | walk] of the forward draw
-    const int rc = tile_order_enqueue(dp, 1, order, BWD_ORDER_CAP, fwd.ranges, s, wk,
+    const int32_t* wk = carry.tile_order + dp.T;      // [work | walk] of the forward draw
+    const int rc = tile_order_enqueue(dp, order, BWD_ORDER_CAP, fwd.ranges, s, wk,
                                       carry.seg_hint ? wk + dp.T : nullptr, carry.seg_hint);
     if (rc) return rc;
-  } else if (carry.tile_order && same_mode) {
-    // the forward pass left its dispatch order behind (same mode): no second k_tile_order
-    dp.order = carry.tile_order;
-    dp.ngrid = tile_order_mode(1) >= 3 ? tile_order_len(dp.gx, dp.gy) : dp.T;
   } else {
     // no record of the forward pass (the seven-op surface: splatB only gets tensors): the work measure is rebuilt
     // from `contrib`, exactly as k_draw would have left it, and the tiles are ordered by it (k_draw_bwd 465 ->
     // 445 us against ordering by list length, for a 4-us kernel)
     int32_t* order = (int32_t*)((char*)ws + 2 * align_up((size_t)n * 48, 256));
-    const size_t len = (size_t)tile_order_len(dp.gx, dp.gy);
     int32_t* work = nullptr;
     int32_t* walk = nullptr;
-    if (by_work && tile_order_mode(1) > 0 && len + (size_t)dp.T <= BWD_ORDER_CAP) {
-      work = order + len;
-      if (carry.seg_hint && len + 2 * (size_t)dp.T <= BWD_ORDER_CAP) walk = work + dp.T;
+    if (2 * (size_t)dp.T <= BWD_ORDER_CAP) {
+      work = order + dp.T;
+      if (carry.seg_hint && 3 * (size_t)dp.T <= BWD_ORDER_CAP) walk = work + dp.T;
       const int rc = tile_work_from_contrib(dp, fwd.contrib, work, walk, s);
       if (rc) return rc;
     }
-    const int rc = tile_order_enqueue(dp, 1, order, BWD_ORDER_CAP, fwd.ranges, s, work, walk,
+    const int rc = tile_order_enqueue(dp, order, BWD_ORDER_CAP, fwd.ranges, s, work, walk,
                                       walk ? carry.seg_hint : nullptr);
     if (rc) return rc;
   }
@@ -217,12 +210,11 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
     if (o.tile_order) {
       // the caller keeps [order | work] between renders and will trust it next time (order_ready): it must hold
       // a valid permutation and the work of THIS render (none) whatever happened here
-      const size_t olen = (size_t)tile_order_len(dp.gx, dp.gy);
       if (!o.order_ready) {
-        const int rc = tile_order_enqueue(dp, 0, o.tile_order, olen, patch_range_per_tile, s, nullptr);
+        const int rc = tile_order_enqueue(dp, o.tile_order, (size_t)dp.T, patch_range_per_tile, s, nullptr);
         if (rc) return rc;
       }
-      EGS_HIP(hipMemsetAsync(o.tile_order + olen, 0, (size_t)dp.T * 8, s));   // work and walk
+      EGS_HIP(hipMemsetAsync(o.tile_order + dp.T, 0, (size_t)dp.T * 8, s));   // work and walk
     }
     if (o.seg_ws) {   // a backward pass may still be handed the workspace: no items, nothing split
       SegArgs sa;
@@ -273,11 +265,10 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
   }
   if (seg) {
     const SegConfig cfg = seg_config();   // (read once per render: the plan kernel leaves L in the workspace header)
-    const size_t olen = (size_t)tile_order_len(dp.gx, dp.gy);
-    const int32_t* hist = (o.tile_order && (o.flags & EGS_DRAW_SEG_HISTORY)) ? o.tile_order + olen + dp.T : nullptr;
-    sga.hist_walk = o.tile_order ? o.tile_order + olen + dp.T : nullptr;
+    const int32_t* hist = (o.tile_order && (o.flags & EGS_DRAW_SEG_HISTORY)) ? o.tile_order + 2 * dp.T : nullptr;
+    sga.hist_walk = o.tile_order ? o.tile_order + 2 * dp.T : nullptr;
     const int speculate = (o.flags & EGS_DRAW_SEG_SPECULATE) ? 1 : 0;    // (with a walk on record: where that looks stale)
-    if (o.tile_order) dp.work_out = o.tile_order + olen;
+    if (o.tile_order) dp.work_out = o.tile_order + dp.T;
     if (o.grad_records) {   // (zero_per: set by draw_segments_forward from its grid)
       dp.zero_buf = (float4*)o.grad_records;
       dp.zero_n4 = (uint32_t)(3 * (size_t)n);
@@ -285,18 +276,18 @@ static int splat_draw_impl(int n, int64_t patches, int width, int height, const 
     return draw_segments_forward(dp, pol, sga, cfg, patches, hist, speculate, hist || speculate, o.walk_word,
                                  o.seg_hint, true, patch_range_per_tile, gsid_per_patch, rec, image, contrib, final_tau, s);
   }
-  if (o.order_ready && o.tile_order && tile_order_mode(0) > 0 && dp.T <= TILE_ORDER_MAX_T) {
+  if (o.order_ready && o.tile_order && dp.T <= TILE_ORDER_MAX_T) {
     dp.order = o.tile_order;
-    dp.ngrid = tile_order_mode(0) >= 3 ? tile_order_len(dp.gx, dp.gy) : dp.T;
+    dp.ngrid = dp.T;
   } else {
     // (prev_tile_work is the work part of a camera's own buffer: its walk part lies T ints behind it)
     // (no hint words from here, as in round 5 -- the walk of the camera's PREVIOUS render is stale after reset_alpha and
     // would overwrite what the range kernel just published; the draw waves gather both words of this render)
-    rc = tile_order_enqueue(dp, 0, o.tile_order ? o.tile_order : D.order, (size_t)tile_order_len(dp.gx, dp.gy),
-                            patch_range_per_tile, s, o.prev_tile_work, nullptr, o.walk_word ? nullptr : o.seg_hint);
+    rc = tile_order_enqueue(dp, o.tile_order ? o.tile_order : D.order, (size_t)dp.T, patch_range_per_tile, s,
+                            o.prev_tile_work, nullptr, o.walk_word ? nullptr : o.seg_hint);
     if (rc) return rc;
   }
-  if (o.tile_order) { dp.work_out = o.tile_order + tile_order_len(dp.gx, dp.gy); dp.walk_out = dp.work_out + dp.T; }
+  if (o.tile_order) { dp.work_out = o.tile_order + dp.T; dp.walk_out = dp.work_out + dp.T; }
   if (o.tile_order) dp.walk_max = o.walk_word;     // (every render refreshes the host's hint, one render late)
   if (o.grad_records) {
     dp.zero_buf = (float4*)o.grad_records;

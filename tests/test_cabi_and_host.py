@@ -239,6 +239,26 @@ def test_variant_patches_apply():
             assert knob not in src, "%s still holds %s" % (os.path.basename(f), knob)
 
 
+def test_library_reads_no_settled_knob():
+    """the library's settled A/B knobs are history, not branches in the product sources: the only environment variables
+    csrc/ reads are the segment configuration's two, and no retired run-time or compile-time knob is named there, in code
+    or in a comment"""
+    import glob
+    retired = ("EGS_TILE_ORDER_F", "EGS_TILE_ORDER_B", "EGS_TILE_SERP", "EGS_DRAWB_BY_WORK", "EGS_DRAWB_RED",
+               "EGS_DRAW_LDS_PAD", "EGS_DRAWB_LDS_PAD", "EGS_PRE_LDS_PAD", "EGS_TILE_MAP", "EGS_PRE_STAGE_IN",
+               "EGS_SH_FUSED_JAC", "EGS_PRE_EARLY_LOADS", "EGS_SH_NT_LOAD", "EGS_SH2COLOR_WAVES", "EGS_PRE_JW_WAVES",
+               "EGS_DRAWB_ABS_WAVES", "EGS_RS_SHORT", "EGS_LOSS_XCD_BANDS")
+    files = glob.glob(os.path.join(REPO, "easygaussiansplatting_amd", "csrc", "*.h*"))
+    assert len(files) >= 10
+    read = set()
+    for f in files:
+        src = open(f).read()
+        read |= set(re.findall(r"getenv\(\s*([^)]*?)\s*\)", src))
+        for knob in retired:     # (a prefix covers the _DEFAULT and _PRE forms)
+            assert knob not in src, "%s still holds %s" % (os.path.basename(f), knob)
+    assert read == {'"EGS_SEG_L"', '"EGS_SEG_MIN"'}, read
+
+
 # ---- ABI 12: one tensor-form and one records-form call per stage of splat / splatB -------------------------------------
 # (shared with the four test files that pin the ABI version: the names join their "removed" lists)
 REMOVED_IN_ABI_12 = ("egs_splat_draw_dev", "egs_splat_draw_rec", "egs_splat_draw_rec_dev", "egs_splat_draw_rec_plain",

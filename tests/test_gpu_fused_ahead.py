@@ -168,6 +168,34 @@ def test_tile_dispatch_order_is_a_sorted_permutation():
         fused.SEGMENTS = keep_seg
 
 
+def test_tile_dispatch_order_past_the_register_path():
+    """``k_tile_order`` keeps the (bin, rank) of its first 16 * 1024 tiles in registers and parks the rest in the order
+    buffer itself: 2064 x 2064 is 129 x 129 = 16 641 tiles, 257 of them parked.  Both orders are permutations, by list
+    length and by measured work, and the image does not depend on them."""
+    from easygaussiansplatting_amd import fused
+    args, cam = _scene(20000, 2064, 2064, 4)
+    T = 129 * 129
+    assert 16 * 1024 < T < 17 * 1024
+    keep_seg, fused.SEGMENTS = fused.SEGMENTS, "0"
+    try:
+        snaps, imgs = [], []
+        with torch.no_grad():
+            for rep in range(2):
+                img, _, st = fused.forward(*args, cam)
+                torch.cuda.synchronize()
+                snaps.append(st.order.cpu().numpy().copy())
+                imgs.append(img.cpu().numpy())
+        lens = (st.ranges[:, 1] - st.ranges[:, 0]).cpu().numpy()
+    finally:
+        fused.SEGMENTS = keep_seg
+    for buf in snaps:
+        assert np.array_equal(np.sort(buf[:T]), np.arange(T))
+    assert (np.diff(lens[snaps[0][:T]]) <= 0).all()          # first render: by list length
+    work = snaps[0][len(snaps[0]) - 2 * T:len(snaps[0]) - T]
+    assert (np.diff((work // 4)[snaps[1][:T]]) <= 0).all()   # second render: by the first one's work, bins of 4
+    np.testing.assert_array_equal(imgs[1], imgs[0])
+
+
 def _order_protocol(fused, args, cam, T, snaps, imgs):
     with torch.no_grad():
         for rep in range(fused.ORDER_REFRESH + 1):

@@ -88,6 +88,12 @@ FOLDED_AGAIN = {
     "k_draw_bwd": (6, ["false"]),                                    # <BOX, FLOOR, CLAMP, RED, SEG, EXTRA> + ABS
     "k_preprocess_bwd": (6, ["false"]),                              # <NC, RAW, JW, EXTRA, POSE, AA> + POSE_ONLY
 }
+# A template argument that was retired at its only surviving value: kernel -> (index, that value).  A name whose argument
+# there is still a number is an older dump's: it takes the folds above and, at that value, loses the argument; the
+# instances of the other values keep their names and are reported "only in a".  Today's names take no fold.
+DROPPED = {
+    "k_draw_bwd": (3, "7"),                                          # <BOX, FLOOR, CLAMP, RED, SEG, EXTRA, ABS> - RED
+}
 
 
 def canonical(name):
@@ -99,11 +105,16 @@ def canonical(name):
     if not m or m.group(1) not in FOLDED:
         return name
     base, args = m.group(1), [x.strip() for x in m.group(2).split(",")]
+    dropped = DROPPED.get(FOLDED[base][0])
+    if dropped and not args[dropped[0]].isdigit():
+        return "%s<%s>" % (base, ", ".join(args))
     new_base, arity, appended = FOLDED[base]
     if len(args) == arity:
         base, args = new_base, args + appended
     if base in FOLDED_AGAIN and len(args) == FOLDED_AGAIN[base][0]:
         args = args + FOLDED_AGAIN[base][1]
+    if dropped and args[dropped[0]] == dropped[1]:
+        del args[dropped[0]]
     return "%s<%s>" % (base, ", ".join(args))
 
 
