@@ -759,7 +759,8 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     }
     if constexpr (!POSE_ONLY) { dL_du[2 * (size_t)i] = gu0; dL_du[2 * (size_t)i + 1] = gu1; }
     if (pp.near_cull && depth_i < EGS_MIN_DEPTH) {  // culled: never drawn, all gradients are zero
-      if constexpr (AA && !POSE_ONLY) dL_dalpha[i] = o_alpha;
+      // (without AA the store above has already put ga.x there: records handed in by a phase-2 caller need not be zero)
+      if constexpr (!POSE_ONLY) dL_dalpha[i] = o_alpha;
       if (!POSE_ONLY && !accum) {   // (POSE_ONLY: pg stays zero, nothing else to write)
         st3(dL_dpw + 3 * (size_t)i, {0.f, 0.f, 0.f});
         st3(dL_dscale + 3 * (size_t)i, {0.f, 0.f, 0.f});
