@@ -8,6 +8,7 @@ import numpy as np
 
 from easygaussiansplatting_amd import scene as S
 from oracle import gs_oracle as O
+from tests.draw_tile_ref import poly_exponent
 
 f = np.float32
 NHL2E = f(-0.72134752044)          # -0.5 log2(e): the record's pre-scaled conic (egs_gaussian_math.h)
@@ -55,14 +56,9 @@ def _errors(sc, limit=60000):
     # direct: cxx = (qxx dx) dx + la; cyy = qyy dy dy; e = cxx + cyy + (qxy dx) dy
     dx, dy = (ux - px).astype(f), (uy - py).astype(f)
     e_dir = (((qxx * dx) * dx + la) + (qyy * dy) * dy + (qxy * dx) * dy).astype(f)
-    # polynomial about the tile centre: coefficients in fp32 (the staging lane), five FMAs per pixel
-    cx0, cy0 = q((tx * 16).astype(f) + f(7.5)), q((ty * 16).astype(f) + f(7.5))
-    Dx, Dy = (cx0 - ux).astype(f), (cy0 - uy).astype(f)
-    c0 = (la + (qxx * Dx * Dx + qxy * Dx * Dy + qyy * Dy * Dy)).astype(f)
-    c1 = (f(2) * qxx * Dx + qxy * Dy).astype(f); c2 = (f(2) * qyy * Dy + qxy * Dx).astype(f)
-    X = (l16 - f(7.5))[None, None, :]; Y = (l16 - f(7.5))[None, :, None]
-    e = (c2 * Y + c0).astype(f); e = (c1 * X + e).astype(f); e = (qyy * (Y * Y).astype(f) + e).astype(f)
-    e = (qxy * (X * Y).astype(f) + e).astype(f); e_pol = (qxx * (X * X).astype(f) + e).astype(f)
+    # polynomial about the tile centre: coefficients in fp32 (the staging lane), five FMAs per pixel -- the restatement
+    # tests/draw_tile_ref.py shares with the one-tile draw tests
+    e_pol = poly_exponent(qxx, qxy, qyy, ux, uy, la, q(tx), q(ty))
     hit = e64 >= np.log2(0.002)                                  # the pixels that blend (kernel.cu:246)
     flips = lambda a: int(((a >= lskip) != hit).sum())
     return np.abs(e_dir - e64)[hit], np.abs(e_pol - e64)[hit], flips(e_dir), flips(e_pol), int(hit.sum())
