@@ -169,6 +169,41 @@ class DensityControl:
         return report
 
     @torch.no_grad()
+    def prune(self, params, optimizer, keep: torch.Tensor):
+        """Keep the rows where ``keep`` (bool [N]) is set, in their order: the six parameter tensors and both Adam
+        moments are compacted and handed to the optimizer the way ``update_gaussian_density`` does.  For masks from
+        ``importance.keep_mask``; runs once per thousands of steps, so plain row gathers.  -> dict(pruned, total)"""
+        groups = {g["name"]: g for g in optimizer.param_groups}
+        missing = [k for k in NAMES if k not in params or k not in groups]
+        if missing:
+            raise ValueError("params/optimizer lack the groups %s" % missing)
+        n = params[NAMES[0]].shape[0]
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != (n,):
+            raise ValueError("prune: keep must be a bool tensor of shape [%d]" % n)
+        idx = torch.nonzero(keep.to(params[NAMES[0]].device), as_tuple=False).reshape(-1)      # ascending
+        n_out = int(idx.shape[0])
+        if n_out == 0:
+            raise ValueError("prune: keep is all False, no Gaussian would be left")
+        report = {"pruned": n - n_out, "total": n_out}
+        if n_out == n:
+            return report
+        for k in NAMES:
+            grp = groups[k]
+            old_p = grp["params"][0]
+            st = optimizer.state.pop(old_p, None)
+            p = torch.nn.Parameter(old_p.data.index_select(0, idx).contiguous().requires_grad_(True))
+            grp["params"][0] = p
+            if st is not None:
+                if "exp_avg" in st:
+                    st["exp_avg"] = st["exp_avg"].index_select(0, idx).contiguous()
+                    st["exp_avg_sq"] = st["exp_avg_sq"].index_select(0, idx).contiguous()
+                optimizer.state[p] = st
+            params[k] = p
+        self.grad_accum = None
+        self.cunt = None
+        return report
+
+    @torch.no_grad()
     def reset_alpha(self, params, optimizer):
         """gsmodel.py:319-330: alphas_raw = min(alphas_raw, logit(0.01)); zero its Adam moments."""
         lib = _lib.load()

@@ -32,6 +32,7 @@ import torch.distributed as dist
 
 from . import dist_views as DV
 from . import fused as _fused
+from . import importance as _importance
 from .density import DensityControl, MCMCControl, expon_lr
 from . import pose as _pose
 from .function import (Camera, GSFunction, GSPoseFunction, GSRawFunction, GSRawPoseFunction,
@@ -343,10 +344,55 @@ class Trainer:
         """train.py:74-76 -> gsmodel.py:319-330."""
         self.density.reset_alpha(self.params, self.opt)
 
+    def importance(self, view_ids: Sequence[int] = None):
+        """-> ``importance.BlendStats``: sum / max / count of the blending weight every Gaussian receives over the views
+        ``view_ids`` (default: all cameras).  Each rank renders its share, forward only, with this
+        trainer's ``antialiased`` and -- with ``pose_opt`` -- the current poses; the statistics are then all-reduced, so
+        every rank holds the same ones."""
+        view_ids = list(range(len(self.cams))) if view_ids is None else [int(v) for v in view_ids]
+        mine = [view_ids[i] for i in DV.views_for_rank(len(view_ids), self.rank, self.world)]
+        p = self.params
+        st = _importance.BlendStats(p["pws"].shape[0], p["pws"].device)
+        with torch.no_grad():
+            if self.fused_activations:
+                args, high = (p["pws"], p["low_shs"], p["alphas_raw"], p["scales_raw"], p["rots_raw"]), p["high_shs"]
+            else:
+                args, high = activate(p), None
+            poses = self.pose_table.poses() if self.pose_table is not None else None
+            for v in mine:
+                cam = self.cams[v]
+                if poses is not None:
+                    cam = Camera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy, poses[0][v].detach(),
+                                 poses[1][v].detach(), self.device, id=cam.id, path=cam.path)
+                _importance.render_weights(st, *args, cam, high_shs=high, antialiased=self.antialiased)
+        if self.world > 1:
+            st.allreduce_()
+        return st
+
+    def prune_by_importance(self, score: str = "max", threshold=None, fraction=None, view_ids: Sequence[int] = None,
+                            verbose: bool = False):
+        """Remove the Gaussians whose ``score`` ("max", "sum" or "hits" of ``importance()``) lies below ``threshold``,
+        or the ``fraction`` of them with the lowest score (``importance.keep_mask``).  Identical on every rank.
+        -> dict(pruned, total)"""
+        st = self.importance(view_ids)
+        keep = _importance.keep_mask(st, score=score, threshold=threshold, fraction=fraction)
+        report = self.density.prune(self.params, self.opt, keep)
+        n = self.params["pws"].shape[0]
+        self.grad_accum = torch.zeros(n, device=self.device)
+        self.vis_count = torch.zeros(n, dtype=torch.int32, device=self.device)
+        if verbose:
+            print("importance pruning report (%s): pruned %d total %d" % (score, report["pruned"], report["total"]))
+        return report
+
     def fit(self, epochs: int, views_per_step: int = None, rng_seed: int = 0, densify_every: int = 5,
-            reset_alpha_every: int = 15, densify_until: int = 50, verbose: bool = False) -> List[float]:
+            reset_alpha_every: int = 15, densify_until: int = 50, verbose: bool = False,
+            prune_importance_at: Sequence[int] = (), prune_score: str = "max", prune_threshold=None,
+            prune_fraction=None) -> List[float]:
         """The epoch loop of train.py:44-80: shuffled views, ``views_per_step`` views per optimizer step
-        (1 in the reference), densification every 5th and alpha reset every 15th epoch in (1, 50]."""
+        (1 in the reference), densification every 5th and alpha reset every 15th epoch in (1, 50].
+        ``prune_importance_at``: epochs at whose end ``prune_by_importance(prune_score, prune_threshold,
+        prune_fraction)`` runs over all cameras (after that epoch's densification, if any); empty: never."""
+        prune_at = set(int(e) for e in prune_importance_at)
         vps = views_per_step or self.world
         if vps < self.world or len(self.cams) < self.world:
             raise ValueError("views_per_step=%d, %d cameras: every one of the %d ranks needs a view in each step"
@@ -373,6 +419,9 @@ class Trainer:
                     self.densify(verbose and self.rank == 0)
                 if epoch % reset_alpha_every == 0 and self.mcmc is None:     # (MCMC: dead Gaussians are relocated)
                     self.reset_alpha()
+            if epoch in prune_at:
+                self.prune_by_importance(prune_score, prune_threshold, prune_fraction,
+                                         verbose=verbose and self.rank == 0)
         return history
 
     def save(self, fn: str) -> np.ndarray:

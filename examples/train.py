@@ -41,9 +41,19 @@ def main():
                     help="densification: the reference's clone / split / prune / alpha reset, or MCMC relocation with "
                          "a hard cap on the number of Gaussians (DESIGN §3.11; needs --cap-max)")
     ap.add_argument("--cap-max", type=int, default=None, help="--strategy mcmc: the largest number of Gaussians")
+    ap.add_argument("--prune-importance-at", default="", metavar="E[,E...]",
+                    help="epochs at whose end Gaussians are pruned on their blending weight over all training views "
+                         "(DESIGN §3.12); needs --prune-threshold or --prune-fraction")
+    ap.add_argument("--prune-score", choices=("max", "sum", "hits"), default="max",
+                    help="the statistic pruned on: largest weight (RadSplat), summed weight (Mini-Splatting), pixels hit")
+    ap.add_argument("--prune-threshold", type=float, default=None, help="keep Gaussians whose score is at least this")
+    ap.add_argument("--prune-fraction", type=float, default=None, help="drop this share of the Gaussians, lowest score first")
     a = ap.parse_args()
     if a.strategy == "mcmc" and a.cap_max is None:
         ap.error("--strategy mcmc needs --cap-max")
+    prune_at = sorted({int(e) for e in a.prune_importance_at.split(",") if e.strip()})
+    if prune_at and (a.prune_threshold is None) == (a.prune_fraction is None):
+        ap.error("--prune-importance-at needs exactly one of --prune-threshold / --prune-fraction")
 
     import torch
     import torch.distributed as dist
@@ -77,6 +87,8 @@ def main():
                 tr.densify(verbose=rank == 0)
             if epoch % 15 == 0 and a.strategy == "default":     # (MCMC relocates dead Gaussians instead)
                 tr.reset_alpha()
+        if epoch in prune_at:
+            tr.prune_by_importance(a.prune_score, a.prune_threshold, a.prune_fraction, verbose=rank == 0)
         if epoch % 10 == 0 and rank == 0:
             tr.save(os.path.join(a.out, "epoch%04d.npy" % epoch))
     if rank == 0:
