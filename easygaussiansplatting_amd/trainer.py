@@ -32,6 +32,7 @@ import torch.distributed as dist
 
 from . import dist_views as DV
 from . import fused as _fused
+from . import features as _features
 from . import importance as _importance
 from .density import DensityControl, MCMCControl, expon_lr
 from . import pose as _pose
@@ -368,6 +369,23 @@ class Trainer:
         if self.world > 1:
             st.allreduce_()
         return st
+
+    def render_features(self, view_id: int, feats):
+        """-> [C,H,W]: ``feats`` ([N,C] float32, one row per Gaussian) rendered into camera ``view_id`` with the current
+        parameters (``features.render``), with this trainer's ``antialiased`` and -- with ``pose_opt`` --
+        the current pose.  No gradient."""
+        p = self.params
+        with torch.no_grad():
+            if self.fused_activations:
+                args, high = (p["pws"], p["low_shs"], p["alphas_raw"], p["scales_raw"], p["rots_raw"]), p["high_shs"]
+            else:
+                args, high = activate(p), None
+            cam = self.cams[int(view_id)]
+            if self.pose_table is not None:
+                poses = self.pose_table.poses()
+                cam = Camera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy, poses[0][int(view_id)].detach(),
+                             poses[1][int(view_id)].detach(), self.device, id=cam.id, path=cam.path)
+            return _features.render(feats, *args, cam, high_shs=high, antialiased=self.antialiased)
 
     def prune_by_importance(self, score: str = "max", threshold=None, fraction=None, view_ids: Sequence[int] = None,
                             verbose: bool = False):
