@@ -7,7 +7,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import EgsPolicy
+from ._lib import DRAW_MASKED_LISTS, EgsPolicy
 
 _policy_name = "gsplatcu"
 _policy = None
@@ -87,3 +87,44 @@ def _alphas(alphas, n):
     if not isinstance(alphas, torch.Tensor) or alphas.numel() != n:
         raise ValueError("alphas must be a tensor of shape [N] or [N,1] with N=%d" % n)
     return _chk(alphas.reshape(n), "alphas", torch.float32, (n,))
+
+
+def _state_lists(state):
+    """What a walk over the tile lists of a finished fused render needs, from its ``fused.FusedState``: settles the
+    render's ticket -> (n, W, H, rec, ranges, gsid, contrib, flags)."""
+    state.patch_count()
+    flags = DRAW_MASKED_LISTS if state.culled else 0
+    return (state.depths.shape[0], int(state.width), int(state.height), state.rec, state.ranges, state.gsid,
+            state.contrib, flags)
+
+
+def _splat_lists(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, areas, what):
+    """The same for one ``gsplatcu.splat`` under the current policy, from its inputs and its outputs ``contrib``,
+    ``patch_range_per_tile`` and ``gsid_per_patch`` (plain lists): validates them and packs the draw records (None when
+    there are no Gaussians).  ``areas`` is needed under the pixel-box policy; ``what`` names the caller in that error."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError("height and width must be positive")
+    us = _chk(us, "us", torch.float32, (None, 2))
+    n = us.shape[0]
+    contrib = _chk(contrib, "contrib", torch.int32, (H, W))
+    ranges = _chk(ranges, "patch_range_per_tile", torch.int32, (_tiles(W, H), 2))
+    gsid = _chk(gsid, "gsid_per_patch", torch.int32, (None,))
+    if n == 0:
+        return n, W, H, None, ranges, gsid, contrib, 0
+    cinv2ds = _chk(cinv2ds, "cinv2ds", torch.float32, (n, 3))
+    alphas = _alphas(alphas, n)
+    _chk(depths, "depths", torch.float32, (n,))
+    pol = _pol()
+    if pol.footprint == 1:
+        if areas is None:
+            raise ValueError("%s needs `areas` under the pixel-box policy" % what)
+        areas = _chk(areas, "areas", torch.int32, (n, 2))
+    else:
+        areas = None
+    lib = _lib.load()
+    rec = torch.empty((n, 12), dtype=torch.float32, device=us.device)
+    colors = torch.zeros((n, 3), dtype=torch.float32, device=us.device)     # the records' colour slots: never read here
+    _lib.check(lib.egs_pack_records(n, W, H, _ptr(us), _ptr(cinv2ds), _ptr(alphas), _ptr(colors), _ptr(areas),
+                                    C.byref(pol), _ptr(rec), _stream()))
+    return n, W, H, rec, ranges, gsid, contrib, 0

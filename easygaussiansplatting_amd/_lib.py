@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libegs_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 ABI_VERSION = 12
+DRAW_MASKED_LISTS = 2      # include/egs_hip.h EGS_DRAW_MASKED_LISTS
 
 
 class EgsPolicy(C.Structure):
@@ -149,33 +150,40 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-def load():
-    """Load the library once; raise EgsLibraryError if it is absent or stale."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
+def load_library(path, signatures, abi_symbol, abi):
+    """Load one of the project's shared libraries: -> the ctypes library with ``restype`` / ``argtypes`` set from
+    ``signatures``; raise EgsLibraryError if it is absent, lacks a symbol or reports another ABI number than ``abi``."""
+    name = os.path.basename(path)
+    if not os.path.exists(path):
         raise EgsLibraryError(
             "%s not found: the HIP extension is not built (run `python -c 'import __graft_entry__ as g; "
-            "g.build()'` or `make -C %s`). There is no CPU fallback." % (LIB_PATH, CSRC))
-    # torch must own the HIP runtime in this process: libegs_hip.so's DT_NEEDED
+            "g.build()'` or `make -C %s`). There is no CPU fallback." % (path, CSRC))
+    # torch must own the HIP runtime in this process: the library's DT_NEEDED
     # libamdhip64.so.7 then resolves (by SONAME) to the copy torch already loaded.
     import torch  # noqa: F401
     try:
-        lib = C.CDLL(LIB_PATH)
+        lib = C.CDLL(path)
     except OSError as e:
-        raise EgsLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in SIGNATURES.items():
+        raise EgsLibraryError("cannot load %s: %s" % (path, e)) from e
+    for sym, (res, args) in signatures.items():
         try:
-            fn = getattr(lib, name)
+            fn = getattr(lib, sym)
         except AttributeError as e:
-            raise EgsLibraryError("libegs_hip.so does not export %s (stale build?)" % name) from e
+            raise EgsLibraryError("%s does not export %s (stale build?)" % (name, sym)) from e
         fn.restype = res
         fn.argtypes = args
-    if lib.egs_abi_version() != ABI_VERSION:
-        raise EgsLibraryError("libegs_hip.so ABI %d != expected %d" % (lib.egs_abi_version(), ABI_VERSION))
-    _lib = lib
+    found = getattr(lib, abi_symbol)()
+    if found != abi:
+        raise EgsLibraryError("%s ABI %d != expected %d" % (name, found, abi))
     return lib
+
+
+def load():
+    """Load the library once; raise EgsLibraryError if it is absent or stale."""
+    global _lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, SIGNATURES, "egs_abi_version", ABI_VERSION)
+    return _lib
 
 
 def check(rc: int):

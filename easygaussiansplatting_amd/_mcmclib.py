@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from ._lib import CSRC, EgsGaussianParams, EgsLibraryError
+from ._lib import EgsGaussianParams, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libegs_mcmc.so")
@@ -46,29 +46,9 @@ _lib = None
 def load():
     """Load the library once; raise EgsLibraryError if it is absent or stale."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise EgsLibraryError(
-            "%s not found: the HIP extension is not built (run `python -c 'import __graft_entry__ as g; "
-            "g.build()'` or `make -C %s`). There is no CPU fallback." % (LIB_PATH, CSRC))
-    # torch must own the HIP runtime in this process (see _lib.load)
-    import torch  # noqa: F401
-    try:
-        lib = C.CDLL(LIB_PATH)
-    except OSError as e:
-        raise EgsLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise EgsLibraryError("libegs_mcmc.so does not export %s (stale build?)" % name) from e
-        fn.restype = res
-        fn.argtypes = args
-    if lib.egs_mcmc_abi_version() != ABI_VERSION:
-        raise EgsLibraryError("libegs_mcmc.so ABI %d != expected %d" % (lib.egs_mcmc_abi_version(), ABI_VERSION))
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, SIGNATURES, "egs_mcmc_abi_version", ABI_VERSION)
+    return _lib
 
 
 def check(rc: int):

@@ -441,37 +441,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((!BOX && SKI
 // ============================================================================
 // draw backward: per-tile back-to-front gradients        (reference kernel.cu:809-950)
 // ============================================================================
-// gfx950 cross-half / cross-row swaps (v_permlane32_swap_b32, v_permlane16_swap_b32)
-__device__ __forceinline__ void swap32(float& a, float& b) {  // a[32..63] <-> b[0..31]
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void swap16(float& a, float& b) {  // odd rows of a <-> even rows of b
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
 // ---- transposing wave reduction ------------------------------------------------------------------
 // 4 entries x 9 quantities = 36 per-lane partials have to become 36 wave totals.  Every step pairs two
 // registers, sends half of each to the partner lanes and adds: one output register per input pair, so the
 // register count halves with the lane span (36 -> 18 -> 9 across the 16-lane rows with
 // v_permlane32_swap / v_permlane16_swap, then 9 -> 5 -> 3 -> 2 -> 1 inside the rows with DPP mirrors).
 // 54 + 27 instructions instead of 36 x 6 DPP adds, and the nine totals of an entry land in nine
-// different lanes of its row -- exactly where the one-instruction atomic wants them.
-__device__ __forceinline__ float rows_of4(float e0, float e1, float e2, float e3) {
-  swap32(e0, e1);
-  const float s01 = e0 + e1;  // lanes 0-31: e0 halves, lanes 32-63: e1 halves
-  swap32(e2, e3);
-  const float s23 = e2 + e3;
-  float a = s01, b = s23;
-  swap16(a, b);               // rows of a: [e0, e2, e1, e3]; rows of b: the other halves
-  return a + b;               // row r: 16 partial sums of entry {0,2,1,3}[r]
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_get(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
+// different lanes of its row -- exactly where the one-instruction atomic wants them.  The first step is rows_of4 of
+// egs_draw_device.h; the merges inside the rows follow.
 // `hi` lanes reduce b, the others reduce a; partner lane through the mirror CTRL (a bijection between
 // the two lane classes)
 template <int CTRL>

@@ -1,4 +1,5 @@
-// Device helpers shared by the blend loops of egs_draw.hip (k_draw, k_draw_bwd) and egs_segments.hip (k_draw_seg).
+// Device helpers shared by the blend loops of egs_draw.hip (k_draw, k_draw_bwd), egs_segments.hip (k_draw_seg) and
+// egs_list_walk.h (k_blend_weights, k_feature_render, k_feature_gather).
 #pragma once
 #include "egs_raster.h"
 
@@ -64,6 +65,52 @@ __device__ __forceinline__ void walk_raise(int32_t* __restrict__ word, int wmax)
 // low bound is finite so the compiler cannot fold the median back into a min)
 __device__ __forceinline__ float min_hi(float x, float hi) {
   return __builtin_amdgcn_fmed3f(x, hi, -3.0e38f);
+}
+
+// gfx950 cross-half / cross-row swaps (v_permlane32_swap_b32, v_permlane16_swap_b32)
+__device__ __forceinline__ void swap32(float& a, float& b) {  // a[32..63] <-> b[0..31]
+  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
+__device__ __forceinline__ void swap16(float& a, float& b) {  // odd rows of a <-> even rows of b
+  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_get(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+
+// ---- transposing wave reduction of four entries -------------------------------------------------------------------
+// Two steps, both generic over the operation (add unless told otherwise).  rows_of4: four per-lane partials become one
+// register of row-wise partials -- after the two swaps row r of the wave holds 16 partials of entry {0, 2, 1, 3}[r]
+// (k_draw_bwd stops here and merges nine such registers inside the rows).  row_total: four DPP steps inside the row
+// leave the total in every lane of it.  total_of4 is the two together.
+struct OpAdd { __device__ __forceinline__ float operator()(float a, float b) const { return a + b; } };
+struct OpMax { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+
+template <typename Op = OpAdd>
+__device__ __forceinline__ float rows_of4(float e0, float e1, float e2, float e3, Op op = Op{}) {
+  swap32(e0, e1);
+  float a = op(e0, e1);   // lanes 0-31: e0 halves, lanes 32-63: e1 halves
+  swap32(e2, e3);
+  float b = op(e2, e3);
+  swap16(a, b);           // rows of a: [e0, e2, e1, e3]; rows of b: the other halves
+  return op(a, b);
+}
+template <typename Op = OpAdd>
+__device__ __forceinline__ float row_total(float v, Op op = Op{}) {
+  v = op(v, dpp_get<0x140>(v));   // row_mirror
+  v = op(v, dpp_get<0x141>(v));   // row_half_mirror
+  v = op(v, dpp_get<0x4E>(v));    // quad_perm [2, 3, 0, 1]
+  v = op(v, dpp_get<0xB1>(v));    // quad_perm [1, 0, 3, 2]
+  return v;
+}
+template <typename Op = OpAdd>
+__device__ __forceinline__ float total_of4(float e0, float e1, float e2, float e3, Op op = Op{}) {
+  return row_total(rows_of4(e0, e1, e2, e3, op), op);
 }
 
 }  // namespace egs

@@ -10,40 +10,16 @@
 // Built into libegs_mcmc.so, a library of its own: it shares headers with libegs_hip.so (the quaternion -> covariance
 // math, the counter-based generator) but no symbol, and keeps its own last-error string.
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
 
-#include "egs_common.h"
+#define EGS_SIDE_LIBRARY "egs_mcmc"
+#include "egs_side_error.h"
 #include "egs_gaussian_math.h"
 #include "egs_rng.h"
 #include "../../include/egs_mcmc.h"
 
+static_assert(EGS_MCMC_ERR_BAD_ARG == EGS_ERR_BAD_ARG, "one bad-argument code across the libraries");
+
 namespace egs_mcmc {
-
-static thread_local char g_err[512] = "no error";
-
-static void set_error(int code, const char* what, const char* file, int line) {
-  const char* base = strrchr(file, '/');
-  snprintf(g_err, sizeof(g_err), "egs_mcmc error %d: %s (%s:%d)", code, what ? what : "?", base ? base + 1 : file,
-           line);
-}
-
-#define MCMC_CHECK_ARG(cond)                                                                    \
-  do {                                                                                          \
-    if (!(cond)) {                                                                              \
-      ::egs_mcmc::set_error(EGS_MCMC_ERR_BAD_ARG, "bad argument: " #cond, __FILE__, __LINE__);  \
-      return EGS_MCMC_ERR_BAD_ARG;                                                              \
-    }                                                                                           \
-  } while (0)
-
-#define MCMC_HIP(expr)                                                              \
-  do {                                                                              \
-    hipError_t e__ = (expr);                                                        \
-    if (e__ != hipSuccess) {                                                        \
-      ::egs_mcmc::set_error((int)e__, hipGetErrorString(e__), __FILE__, __LINE__);  \
-      return (int)e__;                                                              \
-    }                                                                               \
-  } while (0)
 
 using egs::align_up;
 using egs::div_up;
@@ -354,19 +330,19 @@ static size_t scan_blocks(int n) { return (size_t)div_up(n > 0 ? n : 1, SCAN_ROW
 using namespace egs_mcmc;
 
 extern "C" int egs_mcmc_abi_version(void) { return EGS_MCMC_ABI_VERSION; }
-extern "C" const char* egs_mcmc_last_error_string(void) { return egs_mcmc::g_err; }
+extern "C" const char* egs_mcmc_last_error_string(void) { return egs_side::g_err; }
 
 extern "C" int egs_mcmc_weights(int n, const float* alphas_raw, float min_opacity, int relocation, float* weight,
                                 uint8_t* dead, int32_t* totals, void* stream) {
-  MCMC_CHECK_ARG(n >= 0 && totals);
-  MCMC_CHECK_ARG(n == 0 || (alphas_raw && weight && dead));
-  MCMC_CHECK_ARG(min_opacity >= 0.f && min_opacity < 1.f);
+  SIDE_CHECK_ARG(n >= 0 && totals);
+  SIDE_CHECK_ARG(n == 0 || (alphas_raw && weight && dead));
+  SIDE_CHECK_ARG(min_opacity >= 0.f && min_opacity < 1.f);
   hipStream_t s = (hipStream_t)stream;
-  MCMC_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(int32_t), s));
+  SIDE_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(int32_t), s));
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_mcmc_weights, dim3(div_up(n, 256)), dim3(256), 0, s, n, alphas_raw, min_opacity,
                      relocation != 0, weight, dead, totals);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   return 0;
 }
 
@@ -377,26 +353,26 @@ extern "C" size_t egs_mcmc_sample_ws_bytes(int n) {
 
 extern "C" int egs_mcmc_sample(int n, const float* weight, int n_positive, int n_draws, uint64_t seed, uint64_t round,
                                int32_t* idx, void* ws, size_t ws_bytes, void* stream) {
-  MCMC_CHECK_ARG(n >= 0 && n_draws >= 0);
+  SIDE_CHECK_ARG(n >= 0 && n_draws >= 0);
   if (n_draws == 0) return 0;
-  MCMC_CHECK_ARG(n > 0 && n_positive > 0 && n_positive <= n);      // total == 0: nothing alive to draw from
-  MCMC_CHECK_ARG(weight && idx && ws);
-  MCMC_CHECK_ARG(((uintptr_t)weight & 15) == 0 && ((uintptr_t)ws & 255) == 0);
-  MCMC_CHECK_ARG(ws_bytes >= egs_mcmc_sample_ws_bytes(n));
-  MCMC_CHECK_ARG(round < (1ull << 61));
+  SIDE_CHECK_ARG(n > 0 && n_positive > 0 && n_positive <= n);      // total == 0: nothing alive to draw from
+  SIDE_CHECK_ARG(weight && idx && ws);
+  SIDE_CHECK_ARG(((uintptr_t)weight & 15) == 0 && ((uintptr_t)ws & 255) == 0);
+  SIDE_CHECK_ARG(ws_bytes >= egs_mcmc_sample_ws_bytes(n));
+  SIDE_CHECK_ARG(round < (1ull << 61));
   const int nb = (int)scan_blocks(n);
   double* cdf = (double*)ws;
   double* blocksum = (double*)((char*)ws + align_up((size_t)n * sizeof(double), 256));
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_mcmc_scan_blocks, dim3(nb), dim3(256), 0, s, n, weight, blocksum);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_mcmc_scan_sums, dim3(1), dim3(256), 0, s, nb, blocksum);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_mcmc_scan_apply, dim3(nb), dim3(256), 0, s, n, weight, (const double*)blocksum, cdf);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_mcmc_draw, dim3(div_up(n_draws, 256)), dim3(256), 0, s, n, n_draws, weight, (const double*)cdf,
                      (const double*)(blocksum + nb), seed, round, idx);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   return 0;
 }
 
@@ -408,12 +384,12 @@ extern "C" int egs_mcmc_relocate(int n_rows, int n_draws, int high_sh_width, con
                                  const EgsGaussianParams* params, const EgsGaussianParams* exp_avg,
                                  const EgsGaussianParams* exp_avg_sq, float min_opacity, void* ws, size_t ws_bytes,
                                  void* stream) {
-  MCMC_CHECK_ARG(n_rows >= 0 && n_draws >= 0 && high_sh_width >= 0);
-  MCMC_CHECK_ARG(min_opacity >= 0.f && min_opacity < 1.f);
-  MCMC_CHECK_ARG((exp_avg != nullptr) == (exp_avg_sq != nullptr));
+  SIDE_CHECK_ARG(n_rows >= 0 && n_draws >= 0 && high_sh_width >= 0);
+  SIDE_CHECK_ARG(min_opacity >= 0.f && min_opacity < 1.f);
+  SIDE_CHECK_ARG((exp_avg != nullptr) == (exp_avg_sq != nullptr));
   if (n_draws == 0 || n_rows == 0) return 0;
-  MCMC_CHECK_ARG(src && dst && params && ws);
-  MCMC_CHECK_ARG(ws_bytes >= egs_mcmc_relocate_ws_bytes(n_rows));
+  SIDE_CHECK_ARG(src && dst && params && ws);
+  SIDE_CHECK_ARG(ws_bytes >= egs_mcmc_relocate_ws_bytes(n_rows));
   RelocArgs A;
   A.p = to_set(params); A.m = to_set(exp_avg); A.v = to_set(exp_avg_sq);
   const bool has_state = exp_avg != nullptr;
@@ -421,46 +397,46 @@ extern "C" int egs_mcmc_relocate(int n_rows, int n_draws, int high_sh_width, con
   for (int t = 0; t < NT; ++t) {
     A.w.w[t] = widths[t];
     if (widths[t] == 0) continue;
-    MCMC_CHECK_ARG(A.p.t[t]);
-    if (has_state) MCMC_CHECK_ARG(A.m.t[t] && A.v.t[t]);
+    SIDE_CHECK_ARG(A.p.t[t]);
+    if (has_state) SIDE_CHECK_ARG(A.m.t[t] && A.v.t[t]);
   }
   if (!has_state) A.m.t[0] = nullptr;
   A.n_rows = n_rows; A.n_draws = n_draws; A.src = src; A.dst = dst; A.count = (const int32_t*)ws;
   A.min_opacity = min_opacity;
   hipStream_t s = (hipStream_t)stream;
-  MCMC_HIP(hipMemsetAsync(ws, 0, (size_t)n_rows * sizeof(int32_t), s));
+  SIDE_HIP(hipMemsetAsync(ws, 0, (size_t)n_rows * sizeof(int32_t), s));
   hipLaunchKernelGGL(k_mcmc_reloc_count, dim3(div_up(n_draws, 256)), dim3(256), 0, s, n_rows, n_draws, src,
                      (int32_t*)ws);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_mcmc_reloc_draw, dim3(div_up(n_draws, 256)), dim3(256), 0, s, A);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_mcmc_reloc_src, dim3(div_up(n_rows, 256)), dim3(256), 0, s, A);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   return 0;
 }
 
 extern "C" int egs_mcmc_add_reg_grad(int n, const float* alphas_raw, const float* scales_raw, float lambda_o,
                                      float lambda_s, float* g_alphas_raw, float* g_scales_raw, void* stream) {
-  MCMC_CHECK_ARG(n >= 0);
+  SIDE_CHECK_ARG(n >= 0);
   if (n == 0) return 0;
-  MCMC_CHECK_ARG(alphas_raw && scales_raw && g_alphas_raw && g_scales_raw);
+  SIDE_CHECK_ARG(alphas_raw && scales_raw && g_alphas_raw && g_scales_raw);
   hipLaunchKernelGGL(k_mcmc_reg_grad, dim3(div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, n, alphas_raw,
                      scales_raw, (float)((double)lambda_o / n), (float)((double)lambda_s / (3.0 * n)), g_alphas_raw,
                      g_scales_raw);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   return 0;
 }
 
 extern "C" int egs_mcmc_add_noise(int n, float* pws, const float* alphas_raw, const float* scales_raw,
                                   const float* rots_raw, const float* unit_noise, float noise_lr, float lr_pws,
                                   uint64_t seed, uint64_t step, void* stream) {
-  MCMC_CHECK_ARG(n >= 0);
+  SIDE_CHECK_ARG(n >= 0);
   if (n == 0) return 0;
-  MCMC_CHECK_ARG(pws && alphas_raw && scales_raw && rots_raw);
-  MCMC_CHECK_ARG(((uintptr_t)rots_raw & 15) == 0);
-  MCMC_CHECK_ARG(step < (1ull << 60));
+  SIDE_CHECK_ARG(pws && alphas_raw && scales_raw && rots_raw);
+  SIDE_CHECK_ARG(((uintptr_t)rots_raw & 15) == 0);
+  SIDE_CHECK_ARG(step < (1ull << 60));
   hipLaunchKernelGGL(k_mcmc_noise, dim3(div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, n, pws, alphas_raw,
                      scales_raw, rots_raw, unit_noise, noise_lr * lr_pws, seed, step);
-  MCMC_HIP(hipGetLastError());
+  SIDE_HIP(hipGetLastError());
   return 0;
 }

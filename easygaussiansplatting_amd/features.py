@@ -23,8 +23,8 @@ import ctypes as C
 
 import torch
 
-from . import _featlib, _lib
-from ._host import _alphas, _chk, _pol, _ptr, _stream, _tiles
+from . import _featlib
+from ._host import _chk, _pol, _ptr, _splat_lists, _state_lists, _stream
 
 
 def _channels(c, what):
@@ -58,34 +58,25 @@ def _gather(n, W, H, rec, ranges, gsid, contrib, flags, gmap, out):
     return out
 
 
-def _state_args(state):
-    state.patch_count()
-    n = state.depths.shape[0]
-    flags = _featlib.DRAW_MASKED_LISTS if state.culled else 0
-    return n, int(state.width), int(state.height), flags
-
-
 def render_features(state, feats) -> torch.Tensor:
     """-> float32 [C,H,W]: ``feats`` ([N,C] float32) blended with the weights of one fused render.  ``state`` is the
     ``fused.FusedState`` of ``fused.forward(..., need_grad=False)`` or of a training forward, under the current raster
     policy.  Settles the render's ticket, then walks its own records and lists on the current stream."""
-    n, W, H, flags = _state_args(state)
-    feats = _chk(feats, "feats", torch.float32, (n, None))
+    feats = _chk(feats, "feats", torch.float32, (state.depths.shape[0], None))
     _channels(feats.shape[1], "render_features")
     if feats.device != state.depths.device:
         raise ValueError("feats lives on %s, the state on %s" % (feats.device, state.depths.device))
-    return _render(n, W, H, state.rec, state.ranges, state.gsid, state.contrib, flags, feats.detach())
+    return _render(*_state_lists(state), feats.detach())
 
 
 def gather_features(state, gmap, out=None) -> torch.Tensor:
     """-> float32 [N,C]: the adjoint of ``render_features``, ``sum_p sum_k w_k(p) gmap[:, p]`` per Gaussian.  ``gmap``
     is float32 [C,H,W].  With ``out`` ([N,C] float32, contiguous) the result is ADDED to it and it is returned."""
-    n, W, H, flags = _state_args(state)
-    gmap = _chk(gmap, "gmap", torch.float32, (None, H, W))
+    gmap = _chk(gmap, "gmap", torch.float32, (None, int(state.height), int(state.width)))
     _channels(gmap.shape[0], "gather_features")
     if gmap.device != state.depths.device:
         raise ValueError("gmap lives on %s, the state on %s" % (gmap.device, state.depths.device))
-    return _gather(n, W, H, state.rec, state.ranges, state.gsid, state.contrib, flags, gmap.detach(), out)
+    return _gather(*_state_lists(state), gmap.detach(), out)
 
 
 class FeatureRender(torch.autograd.Function):
@@ -113,33 +104,9 @@ def render(feats, pws, shs, alphas, scales, rots, cam, high_shs=None, antialiase
     return FeatureRender.apply(feats, out[2])
 
 
-def _splat_args(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, areas, what):
-    """validation and draw records of the seven-op surface, as ``importance.splat_weights`` builds them"""
-    H, W = int(H), int(W)
-    if H <= 0 or W <= 0:
-        raise ValueError("height and width must be positive")
-    us = _chk(us, "us", torch.float32, (None, 2))
-    n = us.shape[0]
-    contrib = _chk(contrib, "contrib", torch.int32, (H, W))
-    ranges = _chk(ranges, "patch_range_per_tile", torch.int32, (_tiles(W, H), 2))
-    gsid = _chk(gsid, "gsid_per_patch", torch.int32, (None,))
-    if n == 0:
-        return n, H, W, None, ranges, gsid, contrib
-    cinv2ds = _chk(cinv2ds, "cinv2ds", torch.float32, (n, 3))
-    alphas = _alphas(alphas, n)
-    _chk(depths, "depths", torch.float32, (n,))
-    pol = _pol()
-    if pol.footprint == 1:
-        if areas is None:
-            raise ValueError("%s needs `areas` under the pixel-box policy" % what)
-        areas = _chk(areas, "areas", torch.int32, (n, 2))
-    else:
-        areas = None
-    lib = _lib.load()
-    rec = torch.empty((n, 12), dtype=torch.float32, device=us.device)
-    colors = torch.zeros((n, 3), dtype=torch.float32, device=us.device)     # the records' colour slots: never read here
-    _lib.check(lib.egs_pack_records(n, W, H, _ptr(us), _ptr(cinv2ds), _ptr(alphas), _ptr(colors), _ptr(areas),
-                                    C.byref(pol), _ptr(rec), _stream()))
+def _splat_args(*args):
+    """``_host._splat_lists`` as (n, H, W, rec, ranges, gsid, contrib), the form tests/test_gpu_features.py takes"""
+    n, W, H, rec, ranges, gsid, contrib, _ = _splat_lists(*args)
     return n, H, W, rec, ranges, gsid, contrib
 
 
@@ -148,21 +115,19 @@ def splat_features(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, fea
     """-> [C,H,W]: ``feats`` ([N,C]) blended with the weights of one ``gsplatcu.splat`` under the current policy, from
     its inputs and its outputs ``contrib``, ``patch_range_per_tile`` and ``gsid_per_patch`` (plain lists).  ``areas``
     ([N,2] int32, as ``splat`` left them) is needed under the pixel-box policy, as for ``splatB``."""
-    n, H, W, rec, ranges, gsid, contrib = _splat_args(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, areas,
-                                                      "splat_features")
-    feats = _chk(feats, "feats", torch.float32, (n, None))
+    lists = _splat_lists(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, areas, "splat_features")
+    feats = _chk(feats, "feats", torch.float32, (lists[0], None))
     _channels(feats.shape[1], "splat_features")
-    return _render(n, W, H, rec, ranges, gsid, contrib, 0, feats)
+    return _render(*lists, feats)
 
 
 @torch.no_grad()
 def splat_gather(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, gmap, areas=None, out=None) -> torch.Tensor:
     """-> [N,C]: the adjoint of ``splat_features`` for ``gmap`` ([C,H,W]); with ``out`` the result is added to it."""
-    n, H, W, rec, ranges, gsid, contrib = _splat_args(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, areas,
-                                                      "splat_gather")
-    gmap = _chk(gmap, "gmap", torch.float32, (None, H, W))
+    lists = _splat_lists(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, areas, "splat_gather")
+    gmap = _chk(gmap, "gmap", torch.float32, (None, lists[2], lists[1]))
     _channels(gmap.shape[0], "splat_gather")
-    return _gather(n, W, H, rec, ranges, gsid, contrib, 0, gmap, out)
+    return _gather(*lists, gmap, out)
 
 
 @torch.no_grad()

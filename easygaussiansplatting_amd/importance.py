@@ -20,8 +20,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib, _prunelib
-from ._host import _alphas, _chk, _pol, _ptr, _stream, _tiles
+from . import _prunelib
+from ._host import _pol, _ptr, _splat_lists, _state_lists, _stream
 
 SCORES = ("max", "sum", "hits")
 
@@ -108,11 +108,8 @@ def from_state(state, stats: BlendStats = None) -> BlendStats:
     ``fused.forward(..., need_grad=False)`` under the current raster policy.  Settles the render's ticket, then walks
     its own records and lists on the current stream.  Anti-aliased and raw states work unchanged (the kernel reads
     the packed records)."""
-    state.patch_count()
-    n = state.depths.shape[0]
-    stats = _stats_for(stats, n, state.depths.device)
-    flags = _prunelib.DRAW_MASKED_LISTS if state.culled else 0
-    return _accumulate(n, state.width, state.height, state.rec, state.ranges, state.gsid, state.contrib, flags, stats)
+    lists = _state_lists(state)
+    return _accumulate(*lists, _stats_for(stats, lists[0], state.depths.device))
 
 
 @torch.no_grad()
@@ -130,35 +127,8 @@ def splat_weights(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, area
     """The statistics of one ``gsplatcu.splat`` under the current policy, from its inputs and its outputs ``contrib``,
     ``patch_range_per_tile`` and ``gsid_per_patch`` (plain lists).  ``areas`` ([N,2] int32, as ``splat`` left them) is
     needed under the pixel-box policy, as for ``splatB``."""
-    H, W = int(H), int(W)
-    if H <= 0 or W <= 0:
-        raise ValueError("height and width must be positive")
-    us = _chk(us, "us", torch.float32, (None, 2))
-    n = us.shape[0]
-    dev = us.device
-    stats = _stats_for(stats, n, dev)
-    if n == 0:
-        stats.views += 1
-        return stats
-    cinv2ds = _chk(cinv2ds, "cinv2ds", torch.float32, (n, 3))
-    alphas = _alphas(alphas, n)
-    _chk(depths, "depths", torch.float32, (n,))
-    contrib = _chk(contrib, "contrib", torch.int32, (H, W))
-    ranges = _chk(ranges, "patch_range_per_tile", torch.int32, (_tiles(W, H), 2))
-    gsid = _chk(gsid, "gsid_per_patch", torch.int32, (None,))
-    pol = _pol()
-    if pol.footprint == 1:
-        if areas is None:
-            raise ValueError("splat_weights needs `areas` under the pixel-box policy")
-        areas = _chk(areas, "areas", torch.int32, (n, 2))
-    else:
-        areas = None
-    lib = _lib.load()
-    rec = torch.empty((n, 12), dtype=torch.float32, device=dev)
-    colors = torch.zeros((n, 3), dtype=torch.float32, device=dev)      # the records' colour slots: never read here
-    _lib.check(lib.egs_pack_records(n, W, H, _ptr(us), _ptr(cinv2ds), _ptr(alphas), _ptr(colors), _ptr(areas),
-                                    C.byref(pol), _ptr(rec), _stream()))
-    return _accumulate(n, W, H, rec, ranges, gsid, contrib, 0, stats)
+    lists = _splat_lists(H, W, us, cinv2ds, alphas, depths, contrib, ranges, gsid, areas, "splat_weights")
+    return _accumulate(*lists, _stats_for(stats, lists[0], us.device))
 
 
 def keep_mask(stats: BlendStats, score: str = "max", threshold=None, fraction=None) -> torch.Tensor:

@@ -23,10 +23,11 @@ built on it, against the float64 reference of tests/blend_weights_ref.py.
 Test 1 prints, per tensor, the largest distance | the largest kernel error | the largest error / bound (errors and
 distances relative to the row's reference).  Measured on MI355X, largest over the five sets and two policies
 (10 tests pass, 0 rows excluded):
-                      distance   kernel error   error / bound
-  sum                 3.9e-05    2.9e-05        0.83
-  max                 5.7e-05    5.7e-05        0.77
-(the largest of both on the steepest conics of set values; the median set stands at 0.5).  ``hits`` were the reference's
+                      distance   kernel error   error / bound   error / bound on the shared walk
+  sum                 3.9e-05    2.9e-05        0.83            0.83
+  max                 5.7e-05    5.7e-05        0.77            0.77
+(the last column: the kernel on csrc/egs_list_walk.h, whose four words per row are those of its predecessor bit for bit
+on all ten cases; the largest of both on the steepest conics of set values; the median set stands at 0.5).  ``hits`` were the reference's
 on every row and two runs bitwise equal on every set.  Without part (d) of the distance two rows of lengths0 / gsplatcu
 stood at 1.25 x their bound (tile 12, entry 0: 6.7 float32 ulps on a sum of 128 weights); with it that set is at 0.50.
 Test 2 on MI355X: P = 11 753 after culling, 6 890 rows hit, 120 with a near pixel (1.74 %); sum 9.3e-7 of its largest

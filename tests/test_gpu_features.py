@@ -19,6 +19,8 @@ against the float64 reference of tests/feature_ref.py.
    ops' 2D tensors over the state's own lists and contrib; an all-ones channel against 1 - final_tau and against
    ``importance``'s sum.
 4. Adjointness on the device.  5. Autograd through ``FeatureRender``.  6. ``lift`` over two views.  7. n = 0.
+9. The gather of a one-channel all-ones map beside ``importance.splat_weights``' ``sum`` on the one-tile sets: both
+   kernels take the walk of csrc/egs_list_walk.h (see the test's docstring for what they still do not share).
 
 Test 1 prints, per tensor, the largest distance | the largest kernel error | the largest error / bound.
 Measured on MI355X, largest over the five sets, two policies and five
@@ -362,6 +364,42 @@ def test_lift_over_two_views(gpu):
     want = num[seen_h] / den[seen_h][:, None]
     _gradcheck_columns(_host(feats)[seen_h], want, "lifted features")
     assert not _bits(_host(feats))[~seen_h].any(), "unseen rows are not zero bit for bit"
+
+
+# ------------------------------------------------------------------- 9. the all-ones gather beside importance's sum
+@pytest.mark.parametrize("pname", list(D.POLICIES))
+@pytest.mark.parametrize("name", D.SETS)
+def test_all_ones_gather_is_the_weight_sum(gpu, name, pname):
+    """``splat_gather`` of one all-ones channel against ``splat_weights``' ``sum``, row by row.  k_feature_gather and
+    k_blend_weights stage an entry, form its exponent and reduce a group of four with the same code
+    (csrc/egs_list_walk.h, total_of4), fmaf(w, 1, acc) is acc + w, and every Gaussian of these sets lies on one tile
+    (one atomic per row), so the two columns were expected to be equal bit for bit.  They are not: on MI355X they
+    differ on 0 .. 139 rows of a set (none on reach / gsplatcu), by at most 2 ulps.  The staging and the exponent ARE
+    the same instructions in both kernels; the difference is in the accumulation behind them.  k_blend_weights'
+    ``ws += w`` is contracted with ``w = tau alpha'`` into one v_fmac_f32 (ws = fma(tau, alpha', ws), one rounding) --
+    as it was before the walk was shared: its words are the same bit for bit -- while the gather multiplies the ROUNDED
+    w (v_mul_f32) with the pixel's gradient (acc = fma(w, 1, acc), two roundings).  So the rows are held to the rule of
+    tests/test_gpu_blend_weights.py for ``sum`` instead: |gather - sum| <= max(floor, 2 x distance) of
+    tests/blend_weights_ref.py.  Rows that hit nothing are zero bit for bit in both."""
+    gsc, fused, imp = gpu
+    ref, dist, floor = B.reference(name, pname), B.distance(name, pname), B.row_floor(name, pname)
+    args, kw = _splat(gsc, fused, name, pname)
+    st = imp.splat_weights(*args, **kw)
+    gath = features.splat_gather(*args, torch.ones((1, D.H, D.W), device="cuda"), **kw)
+    torch.cuda.synchronize()
+    got, want = _host(gath), _host(st.sum)
+    assert tuple(got.shape) == (D.case(name).n, 1) and want.any()
+    got = got[:, 0]
+    ulps = np.abs(_bits(got).astype(np.int64) - _bits(want).astype(np.int64))
+    print("%-8s %-11s gather != sum on %d of %d rows, largest difference %d ulps"
+          % (name, pname, int((ulps > 0).sum()), ulps.size, int(ulps.max())))
+    zero = ref["hits"] == 0
+    assert not _bits(got)[zero].any() and not _bits(want)[zero].any()
+    err = np.abs(got.astype(np.float64) - want.astype(np.float64))
+    bound = np.maximum(floor["sum"], 2 * dist["sum"])
+    bad = np.nonzero(err > bound)[0]
+    assert bad.size == 0, (name, pname, "%d rows beyond their bound; first: Gaussian %d: gather %.9g, sum %.9g, bound %.3g"
+                           % (bad.size, bad[0], got[bad[0]], want[bad[0]], bound[bad[0]]))
 
 
 # ------------------------------------------------------------------------------------------------------------ 7. n == 0

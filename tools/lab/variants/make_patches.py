@@ -73,17 +73,20 @@ tools/lab/lab_issue_probe.sh.  Not part of the product sources.
 
 # 2. reduction probes + hit bits of k_draw_bwd
 def bwd_probes(s):
-    s=rep(s,'''__device__ __forceinline__ float rows_of4(float e0, float e1, float e2, float e3) {
+    s=rep(s,'''          rows[q] = rows_of4(acc[0][ORDER[q]], acc[1][ORDER[q]], acc[2][ORDER[q]], acc[3][ORDER[q]]);
+''','''#if EGS_PROBE_REDUCE
+          rows[q] = (acc[0][ORDER[q]] + acc[1][ORDER[q]]) + (acc[2][ORDER[q]] + acc[3][ORDER[q]]);
+#else
+          rows[q] = rows_of4(acc[0][ORDER[q]], acc[1][ORDER[q]], acc[2][ORDER[q]], acc[3][ORDER[q]]);
+#endif
+''')
+    s=rep(s,'''template <int NQ>
+__device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c16) {
 ''','''#ifndef EGS_PROBE_REDUCE   // timing probes (the sums are not the wave totals: gradients are not the scene's): 1 = the cross-row stage as plain adds, 2 = the in-row stage too
 #define EGS_PROBE_REDUCE 0
 #endif
-__device__ __forceinline__ float rows_of4(float e0, float e1, float e2, float e3) {
-#if EGS_PROBE_REDUCE
-  return (e0 + e1) + (e2 + e3);
-#endif
-''')
-    s=rep(s,'''__device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c16) {
-''','''__device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c16) {
+template <int NQ>
+__device__ __forceinline__ float rows_to_lanes9_bank(const float (&q)[NQ], int c16) {
 #if EGS_PROBE_REDUCE >= 2
   return ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7])) + q[8];
 #endif
