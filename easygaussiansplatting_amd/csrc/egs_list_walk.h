@@ -5,10 +5,10 @@
 // layout.
 //
 // 64-entry chunks are staged in LDS by the lane that owns the entry: the conic, the cap, the polynomial about the tile
-// centre and (BOX) the pixel box -- no colours.  The exponent is k_draw's (same polynomial, same fmaf order, log2 alpha
-// from the record's threshold, one min against the cap), so the tau formed here is the forward's tau and the skip
-// decisions agree with it.  Entry i is live at a pixel iff i < contrib there: tau only falls, so every entry in front of
-// a pixel's last contributor met `tau >= tau_stop` in the forward pass, and none behind it hit.
+// centre and (BOX) the pixel box -- no colours.  The exponent is k_draw's, from the same two functions (stage_math and
+// pixel_exponent of egs_draw_device.h), so the tau formed here is the forward's tau and the skip decisions agree with it.
+// Entry i is live at a pixel iff i < contrib there: tau only falls, so every entry in front of a pixel's last
+// contributor met `tau >= tau_stop` in the forward pass, and none behind it hit.
 #pragma once
 #include <math.h>
 
@@ -17,21 +17,17 @@
 
 namespace egs {
 
-// One wave64 per 16x16 tile, four pixels per lane: pixel k = 2 by + bx of lane l is (tx0 + (l & 7) + 8 bx,
-// ty0 + (l >> 3) + 8 by), k_draw's mapping.
-struct Lane {
-  int pxb[2], pyb[2];
+// One wave64 per 16x16 tile, four pixels per lane: k_draw's mapping and monomials (TileLane) and what bounds this walk.
+struct Lane : TileLane {
   int cont[4];     // contrib of the lane's four pixels (0 outside the image)
   int bmax[4];     // wave-uniform: largest contrib of block k -> entries >= bmax[k] are inert for it
   int maxcont;     // wave-uniform: the tile is walked to here and no further (0: nothing to walk)
-  float X[2], Y[2], XX[2], YY[2], XY[4];
 };
 
 template <typename P>
 __device__ __forceinline__ void lane_init(Lane& L, const P& p, int tx0, int ty0, int lane, int n,
                                           const int32_t* __restrict__ contrib) {
-  L.pxb[0] = tx0 + (lane & 7); L.pxb[1] = L.pxb[0] + 8;
-  L.pyb[0] = ty0 + (lane >> 3); L.pyb[1] = L.pyb[0] + 8;
+  tile_lane_init(L, tx0, ty0, lane);
   L.maxcont = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -43,12 +39,6 @@ __device__ __forceinline__ void lane_init(Lane& L, const P& p, int tx0, int ty0,
     L.bmax[k] = __builtin_amdgcn_readfirstlane(max(min(mx, n), 0));
     L.maxcont = max(L.maxcont, L.bmax[k]);
   }
-  L.X[0] = (float)(lane & 7) - 7.5f; L.X[1] = (float)(lane & 7) + 0.5f;
-  L.Y[0] = (float)(lane >> 3) - 7.5f; L.Y[1] = (float)(lane >> 3) + 0.5f;
-#pragma unroll
-  for (int b = 0; b < 2; ++b) { L.XX[b] = L.X[b] * L.X[b]; L.YY[b] = L.Y[b] * L.Y[b]; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) L.XY[k] = L.X[k & 1] * L.Y[k >> 1];
 }
 
 // The staging lane's share of a 64-entry chunk: the conic, the cap, the polynomial about the tile centre and (BOX) the
@@ -58,24 +48,15 @@ template <bool BOX, bool FLOOR, bool CLAMP, bool SKIP, typename P>
 __device__ __forceinline__ int stage_entry(const P& p, const Lane& L, int idx, int gm, int tx0, int ty0,
                                            const float4* __restrict__ rec, float4* sA, float4* sB, float* sC, int lane,
                                            int& g) {
-  constexpr float L99 = -0.014499569695115089f;  // log2(0.99)
   int mymask = 0;
   g = p.masked ? (int)((uint32_t)gm & EGS_GSID_MASK) : gm;
   if ((unsigned)g < (unsigned)p.N) {
-    float4 A = rec[3 * (size_t)g], B = rec[3 * (size_t)g + 1];
-    const float4 C = rec[3 * (size_t)g + 2];
-    const bool nanfix = p.nan_blend && nan_entry_fix(A, B);
-    if (C.w < INFINITY) mymask = p.masked ? (int)((uint32_t)gm >> EGS_GSID_BITS) : reach_mask<BOX>(A, C, tx0, ty0);
-    if (nanfix && !BOX && !p.masked && C.w < INFINITY) mymask = 0xF;
-    const float la = SKIP ? p.lskip - C.w : __builtin_amdgcn_logf(B.y);
-    float cap = 3.0e38f;
-    if (FLOOR) cap = CLAMP ? fminf(la, L99) : la;
-    else if (CLAMP) cap = L99;
-    const float cx0 = (float)tx0 + 7.5f, cy0 = (float)ty0 + 7.5f;
-    const float Dx = cx0 - A.x, Dy = cy0 - A.y;
-    const float c0 = la + (A.z * Dx * Dx + A.w * Dx * Dy + B.x * Dy * Dy);
-    const float c1 = 2.f * A.z * Dx + A.w * Dy, c2 = 2.f * B.x * Dy + A.w * Dx;
-    sA[lane] = make_float4(A.z, A.w, B.x, cap);
+    const float4 A = rec[3 * (size_t)g], B = rec[3 * (size_t)g + 1], C = rec[3 * (size_t)g + 2];
+    float4 Q;
+    float c0, c1, c2;
+    mymask = stage_math<BOX, FLOOR, CLAMP, SKIP>(A, B, C, gm, tx0, ty0, (float)tx0 + 7.5f, (float)ty0 + 7.5f, p.lskip,
+                                                 p.masked, p.nan_blend, Q, c0, c1, c2);
+    sA[lane] = Q;
     sB[lane] = make_float4(c0, c1, c2, C.y);
     if constexpr (BOX) sC[lane] = C.z;
   }
@@ -85,20 +66,15 @@ __device__ __forceinline__ int stage_entry(const P& p, const Lane& L, int idx, i
   return mymask;
 }
 
-// Entry j of the staged chunk (index i of the tile list) at the lane's four pixels: k_draw's exponent (same polynomial,
-// same fmaf order, one min against the cap), live iff i < contrib, a hit iff live and not below the skip threshold.  On a
+// Entry j of the staged chunk (index i of the tile list) at the lane's four pixels: k_draw's exponent (pixel_exponent, one
+// min against the cap), live iff i < contrib, a hit iff live and not below the skip threshold.  On a
 // hit of pixel K: w = tau alpha', tau -= w, on_hit(integral_constant<K>, w).  -> the lane hit somewhere
 template <int K, bool BOX, bool FLOOR, bool CLAMP, typename F>
 __device__ __forceinline__ bool blend_pixel(const Lane& L, int reach, int i, const float4& Q, const float4& P, bool inbox,
                                             float lthr, float (&tau)[4], F&& on_hit) {
-  constexpr int bx = K & 1, by = K >> 1;
   bool hit = false;
   if (reach & (1 << K)) {  // scalar branch: block K is in reach and some pixel of it got this far
-    float ex = fmaf(P.z, L.Y[by], P.x);
-    ex = fmaf(P.y, L.X[bx], ex);
-    ex = fmaf(Q.z, L.YY[by], ex);
-    ex = fmaf(Q.y, L.XY[K], ex);
-    ex = fmaf(Q.x, L.XX[bx], ex);
+    float ex = pixel_exponent(L, K, Q, P);
     hit = (i < L.cont[K]) && (ex >= lthr);
     if (BOX) hit = hit && inbox;
     if (hit) {

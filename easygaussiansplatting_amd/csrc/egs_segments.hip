@@ -1,6 +1,7 @@
 // Long tile lists split over several waves: the plan kernel, the three forward launches over work items
-// (k_draw_seg<ROLE>), the segment workspace and its configuration.  The backward kernel over the same work items is
-// k_draw_bwd<.., SEG = true> in egs_draw.hip.  Reference: one 256-thread workgroup per tile, gsplatcu/kernel.cu:152-271.
+// (k_draw_seg<ROLE>), the segment workspace and its configuration.  The walk of a segment is k_draw's blend loop itself
+// (blend_range, egs_draw_device.h).  The backward kernel over the same work items is k_draw_bwd<.., SEG = true> in
+// egs_draw.hip.  Reference: one 256-thread workgroup per tile, gsplatcu/kernel.cu:152-271.
 #include "egs_draw_device.h"
 
 #include <stdlib.h>
@@ -248,8 +249,8 @@ __global__ __launch_bounds__(256) void k_seg_plan_place(int T, const int32_t* __
 //      walk, all segments at once
 //   2  items3 (COMPOSE): composes the SPEC segments in order, walks on from there while a pixel is alive, writes the
 //      tile's pixels and turns the slots into the backward pass's segment-end states
-// The blend loop is k_draw's, unchanged (one stop threshold for the whole wave: a re-walk or a continuation starts
-// from the TRUE transmittance, not from 1).
+// The blend loop is k_draw's: both call blend_range (egs_draw_device.h), here over the entries [e0, e1) of the item
+// (one stop threshold for the whole wave: a re-walk or a continuation starts from the TRUE transmittance, not from 1).
 template <bool FLOOR, bool CLAMP, int ROLE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 8 : (ROLE == 2 ? 2 : 5), 8))) void k_draw_seg(
     DrawParams p, SegArgs sg, int32_t* __restrict__ ranges, const int32_t* __restrict__ gsid,
@@ -257,11 +258,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 
     float* __restrict__ final_tau) {
   __shared__ float4 sA[64], sB[64], sC[64];
   const int lane = threadIdx.x;
-  if (ROLE == 0 && p.zero_buf) {   // every workgroup of the grid clears its slice of the gradient records
-    const uint32_t z0 = blockIdx.x * p.zero_per, z1 = min(p.zero_n4, z0 + p.zero_per);
-    float4* __restrict__ zb = p.zero_buf;
-    for (uint32_t i = z0 + lane; i < z1; i += 64) zb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  if (ROLE == 0) zero_slice(p, lane);   // the gradient records
   constexpr bool PER_TILE = ROLE == 2;
   // launch 1 runs FOUR waves per item, one per 8x8 block of the tile: what it costs is the latency of ONE lone wave
   // walking one segment (it executes 3 % of launch 0's instructions), and a wave that blends one block instead of up
@@ -280,35 +277,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 
   const int r0 = ranges[2 * (size_t)tile], r1 = ranges[2 * (size_t)tile + 1];
   const int n = sg.rebuild ? min(r1 - r0, sg.walk[tile]) : r1 - r0;
   const int tx0 = (tile % p.gx) * EGS_TILE, ty0 = (tile / p.gx) * EGS_TILE;
-  const int pxb[2] = {tx0 + (lane & 7), tx0 + (lane & 7) + 8};
-  const int pyb[2] = {ty0 + (lane >> 3), ty0 + (lane >> 3) + 8};
+  TileLane G;
+  tile_lane_init(G, tx0, ty0, lane);
   const size_t HW = (size_t)p.W * p.H;
   // (recomputed where they are used: nothing of this stays in registers across the blend loop)
-  auto inside_px = [&](int k) { return (pxb[k & 1] < p.W) && (pyb[k >> 1] < p.H); };
-  auto pix_of = [&](int k) { return (size_t)min(pyb[k >> 1], p.H - 1) * p.W + min(pxb[k & 1], p.W - 1); };
+  auto inside_px = [&](int k) { return (G.pxb[k & 1] < p.W) && (G.pyb[k >> 1] < p.H); };
+  auto pix_of = [&](int k) { return (size_t)min(G.pyb[k >> 1], p.H - 1) * p.W + min(G.pxb[k & 1], p.W - 1); };
   if (n <= 0) {  // (DIRECT only) empty tile: zeros, final_tau = 0, ranges (0, 0) -- as k_draw
     if (ROLE != 0) return;
     if (p.work_out && lane == 0) p.work_out[tile] = 0;
     if (lane == 0) { sg.walk[tile] = 0; if (sg.hist_walk) sg.hist_walk[tile] = 0; }
-    if (lane == 0 && (r0 != 0 || r1 != 0)) { ranges[2 * (size_t)tile] = 0; ranges[2 * (size_t)tile + 1] = 0; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (inside_px(k)) {
-        image[pix_of(k)] = 0.f; image[HW + pix_of(k)] = 0.f; image[2 * HW + pix_of(k)] = 0.f;
-        contrib[pix_of(k)] = 0; final_tau[pix_of(k)] = 0.f;
-      }
+    empty_tile<false>(G, p, tile, r0, r1, lane, ranges, image, contrib, final_tau, nullptr);
     return;
   }
   const int slot0 = sg.seg_base[tile];
-  const float stop = p.tau_stop, lthr = p.lskip;
-  const float X[2] = {(float)(lane & 7) - 7.5f, (float)(lane & 7) + 0.5f};
-  const float Y[2] = {(float)(lane >> 3) - 7.5f, (float)(lane >> 3) + 0.5f};
-  const float XX[2] = {X[0] * X[0], X[1] * X[1]}, YY[2] = {Y[0] * Y[0], Y[1] * Y[1]};
-  const float XY[4] = {X[0] * Y[0], X[1] * Y[0], X[0] * Y[1], X[1] * Y[1]};
-  constexpr float L99 = -0.014499569695115089f;
-  const float cx0 = (float)tx0 + 7.5f, cy0 = (float)ty0 + 7.5f;
-  float tau[4], cr[4], cg[4], cb[4];   // blend state of one walk; a pixel that does not take part holds tau = -1
-  int cont[4];
+  const float stop = p.tau_stop;
+  float tau[4], cr[4], cg[4], cb[4], cd[4];   // blend state of one walk; a pixel that does not take part holds tau = -1
+  int cont[4];                                // (cd: render extras, not on this path)
   // ROLE 2: the transmittance in front of the current segment; negative: the pixel is finished (or outside the image),
   // |Tf| its final transmittance.  ROLE 1: the transmittance in front of segment iseg for the pixels to blend again.
   float Tf[4];
@@ -317,7 +302,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 
     // the transmittance in FRONT of this segment, T_s = tau_0 tau_1 ... tau_(s-1) in that order (as COMPOSE forms it),
     // from the dense copies launch 0 left in st2: s x 1 KB per item, requested eight segments at a time
     const int qo = 64 * quad;            // this wave's block of the tile
-    const bool qin = (pxb[quad & 1] < p.W) && (pyb[quad >> 1] < p.H);
+    // (selects, not G.pxb[quad & 1]: an index known only at run time would put all of G into scratch)
+    const bool qin = ((quad & 1) ? G.pxb[1] : G.pxb[0]) < p.W && ((quad >> 1) ? G.pyb[1] : G.pyb[0]) < p.H;
     float T = qin ? 1.f : -1.f;
     constexpr int AHEAD = 8;
     for (int s0 = 0; s0 < iseg; s0 += AHEAD) {
@@ -407,77 +393,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 
       cr[k] = 0.f; cg[k] = 0.f; cb[k] = 0.f; cont[k] = 0;
       if (__any(tau[k] >= stop)) live |= 1 << k;
     }
-    // ---- the blend loop of k_draw over entries [e0, e1) ----
-    int gnext = (e0 + lane < e1) ? gsid[r0 + e0 + lane] : 0;
-    for (int base = e0; base < e1 && live != 0; base += 64) {
-      __syncthreads();
-      int mymask = 0;
-      const int gm = gnext;
-      const int g = p.masked ? (int)((uint32_t)gm & EGS_GSID_MASK) : gm;
-      if (base + 64 + lane < e1) gnext = gsid[r0 + base + 64 + lane];
-      if (base + lane < e1) {
-        float4 A = rec[3 * (size_t)g], B = rec[3 * (size_t)g + 1];
-        const float4 C = rec[3 * (size_t)g + 2];
-        const bool nanfix = p.nan_blend && nan_entry_fix(A, B);
-        if (C.w < INFINITY) mymask = p.masked ? (int)((uint32_t)gm >> EGS_GSID_BITS) : reach_mask<false>(A, C, tx0, ty0);
-        // (as k_draw: a NaN entry blends everywhere, its certain-miss box says nothing -- unmasked lists: the public
-        // splatB's rebuild, EGS_CULL_LISTS=0)
-        if (nanfix && !p.masked && C.w < INFINITY) mymask = 0xF;
-        const float la = lthr - C.w;
-        float cap = 3.0e38f;
-        if (FLOOR) cap = CLAMP ? fminf(la, L99) : la;
-        else if (CLAMP) cap = L99;
-        const float Dx = cx0 - A.x, Dy = cy0 - A.y;
-        const float c0 = la + (A.z * Dx * Dx + A.w * Dx * Dy + B.x * Dy * Dy);
-        const float c1 = 2.f * A.z * Dx + A.w * Dy, c2 = 2.f * B.x * Dy + A.w * Dx;
-        sA[lane] = make_float4(A.z, A.w, B.x, cap);
-        sB[lane] = make_float4(c0, c1, c2, B.z);
-        *reinterpret_cast<float2*>(&sC[lane]) = make_float2(B.w, C.x);
-      }
-      __syncthreads();
-      int pk = mymask;
-      pk |= __shfl_down(pk, 1, 64) << 4;
-      pk |= __shfl_down(pk, 2, 64) << 8;
-      pk |= __shfl_down(pk, 4, 64) << 16;
-      const int m = __builtin_amdgcn_readfirstlane(min(64, e1 - base));
-      for (int j0 = 0; j0 < m && live != 0; j0 += 8) {
-        const uint32_t act = (uint32_t)__builtin_amdgcn_readlane(pk, j0) & ((uint32_t)live * 0x11111111u);
-        if (act != 0u) {
-          const int vidx0 = base + j0 + 1;
-#pragma unroll
-          for (int t = 0; t < 8; ++t) {
-            const int reach = (int)((act >> (4 * t)) & 0xFu);
-            if (reach != 0) {
-              const int j = j0 + t;
-              const float4 Q = sA[j], Pq = sB[j];
-              const float2 gb = *reinterpret_cast<const float2*>(&sC[j]);
-              const int idx = vidx0 + t;
-#pragma unroll
-              for (int k = 0; k < 4; ++k) {
-                const int bx = k & 1, by = k >> 1;
-                if (reach & (1 << k)) {
-                  float e = fmaf(Pq.z, Y[by], Pq.x);
-                  e = fmaf(Pq.y, X[bx], e);
-                  e = fmaf(Q.z, YY[by], e);
-                  e = fmaf(Q.y, XY[k], e);
-                  e = fmaf(Q.x, XX[bx], e);
-                  if ((tau[k] >= stop) && (e >= lthr)) {
-                    if (FLOOR || CLAMP) e = min_hi(e, Q.w);
-                    const float w = tau[k] * __builtin_amdgcn_exp2f(e);
-                    cr[k] += w * Pq.w; cg[k] += w * gb.x; cb[k] += w * gb.y;
-                    tau[k] -= w;
-                    cont[k] = idx;
-                  }
-                }
-              }
-            }
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if ((live & (1 << k)) && !__any(tau[k] >= stop)) live &= ~(1 << k);
-        }
-      }
-    }
+    blend_range<false, FLOOR, CLAMP, true, false>(tau, cr, cg, cb, cd, cont, live, G, e0, e1, r0, tx0, ty0, lane, stop,
+                                                  p.lskip, p.masked, p.nan_blend, gsid, rec, nullptr, sA, sB, sC, nullptr);
     if (ROLE == 0 && kind == SEG_SPEC) {     // the segment's local state: (colour, tau) and its last contributor
       const size_t so = ((size_t)(slot0 + iseg)) * 256 + lane;
 #pragma unroll
@@ -573,15 +490,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROLE == 0 ? 
     }
   }
   {   // how far the tile was walked: the work measure of the dispatch orders and the backward pass's segment count
-    int w = 0, wmax = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      int mx = cfin[k];
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) mx = max(mx, __shfl_xor(mx, d, 64));
-      w += mx;
-      wmax = max(wmax, mx);
-    }
+    int w, wmax;
+    block_max(cfin, w, wmax);
     if (lane == 0) {
       if (p.work_out) p.work_out[tile] = w + 2 * wmax;
       if (!sg.rebuild) sg.walk[tile] = wmax;      // (rebuilding: the walk of the pass whose `contrib` was handed in stays)

@@ -1,5 +1,6 @@
-"""k_draw / k_draw_bwd and the segment kernels that share their bodies (csrc/egs_draw.hip) on HAND-BUILT one-tile lists
-(tests/draw_tile_ref.py): chosen list lengths (0 .. 300 around the 8-entry groups and the 64-entry chunks), chosen stop
+"""k_draw / k_draw_bwd (csrc/egs_draw.hip) and the segment kernels that share their bodies -- k_draw_seg walks its entries
+with k_draw's own blend loop (blend_range, csrc/egs_draw_device.h), the segment backward is k_draw_bwd<SEG> -- on
+HAND-BUILT one-tile lists (tests/draw_tile_ref.py): chosen list lengths (0 .. 300 around the 8-entry groups and the 64-entry chunks), chosen stop
 positions per 8x8 block, chosen runs of entries that reach a block and hit nothing, clamped / floored / steepest /
 500 px conics, ragged tiles -- against the float64 oracle, tightly:
 
@@ -18,7 +19,8 @@ positions per 8x8 block, chosen runs of entries that reach a block and hit nothi
   * the backward pass ALONE -- ``splatB`` fed the oracle's float64 contrib / final_tau (rounded to float32) and the
     oracle's lists -- is held to the same reference by the same rule and the same bound; its error against the distance
     of k_draw_bwd by itself, (a), (b), (d) below, is printed beside it.
-No pixel and no row is excluded anywhere.
+No pixel and no row is excluded anywhere.  ``test_unsplit_tiles_see_one_loop``: on the tiles of at most 64 entries (DIRECT
+items of the segment path) image, contrib and final_tau of ``seg-records-spec0`` equal those of ``records`` bit for bit.
 
 Paths: the seven-op pair with masked lists (default) and with plain lists + the per-entry box test, the records handle,
 policy forward_cpu (BOX instances, no skip, no stop), the segment path (segments of 64, every list above 64 split) with
@@ -124,15 +126,12 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).reshape(-1).view(np.int32)
 
 
-def run_path(gpu, name, path):
-    """one forward + backward of set ``name`` through ``path``, twice, and the backward alone where the path takes
-    tensors -> dict(fwd: image, contrib, final_tau, ranges, gsid; grads, grads_again, alone (or None), policy)"""
+def _configure(gpu, path):
+    """the library's knobs as ``path`` wants them -> (its options, its policy name)"""
     gsc, fused, lib, monkeypatch = gpu
     from easygaussiansplatting_amd import _lib
     opt = PATHS[path]
     pname = opt.get("policy", "gsplatcu")
-    c = D.case(name)
-    a = c.arrays
     gsc.set_policy(pname)
     monkeypatch.setattr(gsc, "MASKED_LISTS", opt.get("masked", True))
     fused.SEGMENTS = "1" if opt.get("seg") else "0"
@@ -140,6 +139,16 @@ def run_path(gpu, name, path):
         _lib.check(lib.egs_seg_config(64, 64, None))
         fused.SEG_SPECULATE = opt["spec"]
         gsc.set_pair_states(opt.get("pair", "content"))
+    return opt, pname
+
+
+def run_path(gpu, name, path):
+    """one forward + backward of set ``name`` through ``path``, twice, and the backward alone where the path takes
+    tensors -> dict(fwd: image, contrib, final_tau, ranges, gsid; grads, grads_again, alone (or None), policy)"""
+    gsc = gpu[0]
+    opt, pname = _configure(gpu, path)
+    c = D.case(name)
+    a = c.arrays
     us, cinv, alphas, colors, dl = (_t(a[k]) for k in ("us", "cinv2ds", "alphas", "colors", "dloss_dgammas"))
     out = dict(policy=pname)
 
@@ -262,3 +271,31 @@ def test_one_tile_lists(gpu, name, path):
         assert np.array_equal(_bits(a), _bits(b)), (name, path, k, "two runs differ")
     if failed:
         raise failed[0]
+
+
+@pytest.mark.parametrize("name", D.SETS)
+def test_unsplit_tiles_see_one_loop(gpu, name):
+    """A tile of at most 64 entries is a DIRECT item of the segment path (segment length 64, split minimum 64): k_draw_seg
+    walks it with the loop k_draw walks it with, so image, contrib and final_tau of ``seg-records-spec0`` equal those of
+    ``records`` bit for bit on every pixel of such a tile."""
+    gsc = gpu[0]
+    c = D.case(name)
+    a = c.arrays
+    fwd = {}
+    for path in ("records", "seg-records-spec0"):
+        _configure(gpu, path)
+        out, h = gsc.splat_with_records(D.H, D.W, *(_t(a[k]) for k in ("us", "cinv2ds", "alphas", "depths", "colors",
+                                                                        "areas")))
+        assert h is not None
+        torch.cuda.synchronize()
+        fwd[path] = _host(out[:3])
+    ls = D.lists(c, "gsplatcu")[0]
+    short = [t for t, l in enumerate(ls) if len(l) <= 64]
+    assert any(len(ls[t]) > 0 for t in short), (name, "no unsplit tile with entries")
+    for t in short:
+        tx, ty, x0, y0, ww, hh = D.geom(t)
+        for key, one, seg in zip(("image", "contrib", "final_tau"), fwd["records"], fwd["seg-records-spec0"]):
+            one, seg = one[..., y0:y0 + hh, x0:x0 + ww], seg[..., y0:y0 + hh, x0:x0 + ww]
+            diff = np.argwhere(one.view(np.int32) != seg.view(np.int32))
+            assert diff.size == 0, (name, key, "tile %d (%d entries): %d words differ, first at %s: %r against %r" % (
+                t, len(ls[t]), len(diff), diff[0], one[tuple(diff[0])], seg[tuple(diff[0])]))

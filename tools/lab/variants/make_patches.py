@@ -17,57 +17,66 @@ def mkpatch(name, edits, desc):
             out+=r
     open(os.path.join(HERE,name+'.patch'),'w').write(out)
 
-# 1. issue-port probes of k_draw
+# 1. issue-port probes of the forward blend loop (blend_range: k_draw and k_draw_seg)
 def draw_probes(s):
-    s=rep(s,'''  int gnext = (lane < n) ? gsid[r0 + lane] : 0;
-  for (int base = 0; base < n && live != 0; base += 64) {
-    __syncthreads();  // single-wave workgroup''','''  int gnext = (lane < n) ? gsid[r0 + lane] : 0;
+    s=rep(s,'''  int gnext = (e0 + lane < e1) ? gsid[r0 + e0 + lane] : 0;
+  for (int base = e0; base < e1 && live != 0; base += 64) {
+    __syncthreads();  // single-wave workgroup''','''  int gnext = (e0 + lane < e1) ? gsid[r0 + e0 + lane] : 0;
 #ifdef EGS_DRAW_DUMMY_SALU
   uint32_t dummy_s = 0;
 #endif
 #ifdef EGS_DRAW_DUMMY_VALU
   float dummy_v = 1.f;
 #endif
-  for (int base = 0; base < n && live != 0; base += 64) {
+  for (int base = e0; base < e1 && live != 0; base += 64) {
     __syncthreads();  // single-wave workgroup''')
-    s=rep(s,'''        const float4 Q = sA[j], P = sB[j];            // wave-uniform address: LDS broadcast
-        float4 K;
-        float zj = 0.f;
-        if constexpr (BOX) { K = sC[j]; if constexpr (EXTRA) zj = sZ[j]; }
-        else if constexpr (EXTRA) { const float4 gbz = sC[j]; K = make_float4(P.w, gbz.x, gbz.y, 0.f); zj = gbz.z; }
-        else { const float2 gb = *reinterpret_cast<const float2*>(&sC[j]); K = make_float4(P.w, gb.x, gb.y, 0.f); }
+    s=rep(s,'''          const float4 Q = sA[j], P = sB[j];            // wave-uniform address: LDS broadcast
+          float4 K;
+          float zj = 0.f;
+          if constexpr (BOX) { K = sC[j]; if constexpr (EXTRA) zj = sZ[j]; }
+          else if constexpr (EXTRA) { const float4 gbz = sC[j]; K = make_float4(P.w, gbz.x, gbz.y, 0.f); zj = gbz.z; }
+          else { const float2 gb = *reinterpret_cast<const float2*>(&sC[j]); K = make_float4(P.w, gb.x, gb.y, 0.f); }
 ''','''#ifdef EGS_DRAW_PROBE_NOK    // LDS probe: two broadcast reads per entry instead of three (timing only: the colours are constants)
-        const float4 Q = sA[j], P = sB[j], K = make_float4(0.5f, 0.25f, 0.125f, 0.f);
-        const float zj = 0.f;
+          const float4 Q = sA[j], P = sB[j], K = make_float4(0.5f, 0.25f, 0.125f, 0.f);
+          const float zj = 0.f;
 #else
-        const float4 Q = sA[j], P = sB[j];            // wave-uniform address: LDS broadcast
-        float4 K;
-        float zj = 0.f;
-        if constexpr (BOX) { K = sC[j]; if constexpr (EXTRA) zj = sZ[j]; }
-        else if constexpr (EXTRA) { const float4 gbz = sC[j]; K = make_float4(P.w, gbz.x, gbz.y, 0.f); zj = gbz.z; }
-        else { const float2 gb = *reinterpret_cast<const float2*>(&sC[j]); K = make_float4(P.w, gb.x, gb.y, 0.f); }
+          const float4 Q = sA[j], P = sB[j];            // wave-uniform address: LDS broadcast
+          float4 K;
+          float zj = 0.f;
+          if constexpr (BOX) { K = sC[j]; if constexpr (EXTRA) zj = sZ[j]; }
+          else if constexpr (EXTRA) { const float4 gbz = sC[j]; K = make_float4(P.w, gbz.x, gbz.y, 0.f); zj = gbz.z; }
+          else { const float2 gb = *reinterpret_cast<const float2*>(&sC[j]); K = make_float4(P.w, gb.x, gb.y, 0.f); }
 #endif
 #ifdef EGS_DRAW_DUMMY_SALU   // issue-limit probe (tools/lab/lab_issue_probe.sh): N extra scalar instructions per entry
 #pragma unroll
-        for (int q = 0; q < EGS_DRAW_DUMMY_SALU; ++q) asm volatile("s_add_u32 %0, %0, 1" : "+s"(dummy_s) : : "scc");
+          for (int q = 0; q < EGS_DRAW_DUMMY_SALU; ++q) asm volatile("s_add_u32 %0, %0, 1" : "+s"(dummy_s) : : "scc");
 #endif
 #ifdef EGS_DRAW_DUMMY_VALU   // ... or N extra full-rate vector instructions
 #pragma unroll
-        for (int q = 0; q < EGS_DRAW_DUMMY_VALU; ++q) asm volatile("v_add_f32 %0, %0, %0" : "+v"(dummy_v));
+          for (int q = 0; q < EGS_DRAW_DUMMY_VALU; ++q) asm volatile("v_add_f32 %0, %0, %0" : "+v"(dummy_v));
 #endif
 ''')
-    s=rep(s,'''  if (p.work_out) {   // what k_draw_bwd will walk: the largest contributor index of the tile and of its blocks''','''#ifdef EGS_DRAW_DUMMY_SALU
+    s=rep(s,'''        if ((live & (1 << k)) && !__any(tau[k] >= stop)) live &= ~(1 << k);
+      }
+    }
+  }
+}''','''        if ((live & (1 << k)) && !__any(tau[k] >= stop)) live &= ~(1 << k);
+      }
+    }
+  }
+#ifdef EGS_DRAW_DUMMY_SALU
   if (dummy_s == 0xFFFFFFFFu) cr[0] += 1.f;   // (keeps the probe's chain alive)
 #endif
 #ifdef EGS_DRAW_DUMMY_VALU
   if (dummy_v == 12345.f) cr[0] += 1.f;
 #endif
-  if (p.work_out) {   // what k_draw_bwd will walk: the largest contributor index of the tile and of its blocks''')
+}''')
     return s
-mkpatch('draw_issue_probes', {'egs_draw.hip': draw_probes}, '''Issue-port probes of k_draw (round 4, DESIGN 3.3 / LAB 3.3): -DEGS_DRAW_DUMMY_SALU=N / -DEGS_DRAW_DUMMY_VALU=N add N scalar /
-vector instructions per (tile, entry); -DEGS_DRAW_PROBE_NOK reads two LDS pieces per entry instead of three and blends
-constant colours (timing only, the image is not the scene's).  Apply, build a variant library, time it with
-tools/lab/lab_issue_probe.sh.  Not part of the product sources.
+mkpatch('draw_issue_probes', {'egs_draw_device.h': draw_probes}, '''Issue-port probes of k_draw's blend loop (blend_range of egs_draw_device.h, which k_draw_seg walks too; round 4,
+DESIGN 3.3 / LAB 3.3): -DEGS_DRAW_DUMMY_SALU=N / -DEGS_DRAW_DUMMY_VALU=N add N scalar / vector instructions per
+(tile, entry); -DEGS_DRAW_PROBE_NOK reads two LDS pieces per entry instead of three and blends constant colours (timing
+only, the image is not the scene's).  Apply, build a variant library, time it with tools/lab/lab_issue_probe.sh.  Not
+part of the product sources.
 
 ''')
 
