@@ -16,6 +16,7 @@
 // replica computes bit-identical new Gaussians without communicating (the reference draws from the
 // device RNG stream, gsmodel.py:274).
 #include "egs_common.h"
+#include "egs_adam_device.h"
 #include "egs_gaussian_math.h"
 #include "egs_rng.h"   // counter-based normals: bit-compatible with easygaussiansplatting_amd/scene.py
 
@@ -221,31 +222,7 @@ __global__ __launch_bounds__(256) void k_reset_alpha(int n, float raw_val, float
 }
 
 // ---- fused Adam ---------------------------------------------------------------------------------
-constexpr int ADAM_MAX_GROUPS = 8;
-constexpr int ADAM_PER_BLOCK = 256 * 4;           // floats per workgroup
-struct AdamGroupDev {
-  float* p; const float* g; float* m; float* v;
-  int64_t count;
-  float step_size, sqrt_bc2;                      // lr / (1 - b1^t), sqrt(1 - b2^t)
-  int first_block;
-};
-struct AdamArgs {
-  AdamGroupDev g[ADAM_MAX_GROUPS];
-  int n_groups;
-  float beta1, beta2, omb1, omb2, eps;            // omb = 1 - beta rounded from double, as torch does
-};
-
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamArgs& A, float step_size,
-                                      float sqrt_bc2) {
-  // (no contraction: torch's kernels round every product, and k_adam / k_adam_sh_factored must agree to the bit
-  // wherever the compiler inlines this)
-#pragma clang fp contract(off)
-  m = m + (g - m) * A.omb1;                       // exp_avg.lerp_(grad, 1 - beta1)
-  v = v * A.beta2 + g * g * A.omb2;               // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
-  const float denom = sqrtf(v) / sqrt_bc2 + A.eps;   // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-  p -= step_size * (m / denom);
-}
-
+// (AdamArgs, AdamGroupDev and the element update adam1: egs_adam_device.h, shared with libegs_adam.so's masked kernels)
 __global__ __launch_bounds__(256) void k_adam(AdamArgs A) {
   int gi = 0;
 #pragma unroll
@@ -277,13 +254,7 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs A) {
 // k_sh_grad_views, scale * sum_v dL/dcolour_v (x) basis(pw - twc_v) -- and all four waves run torch's Adam update over
 // the 64 x K contiguous elements of param / exp_avg / exp_avg_sq (7 x 4 B per element instead of 8 plus the rows'
 // write: 1344 + 12 V bytes per Gaussian at degree 3 where k_sh_grad_views + k_adam move 1728 + 12 V).
-constexpr int ASH_ROWS = 64;
-struct AdamShTensor {
-  float *p, *m, *v;                               // [N][width]
-  float step_size, sqrt_bc2;
-  int width;                                      // floats per Gaussian; 0: tensor absent
-  int col0;                                       // first column of the K-wide row it holds (0: low / whole, 3: high)
-};
+// (ASH_ROWS = 64 and AdamShTensor: egs_adam_device.h)
 template <int NC>
 __global__ __launch_bounds__(256) void k_adam_sh_factored(int n, int views, const float* __restrict__ pws,
                                                           const float* __restrict__ rows, int64_t stride, float scale,

@@ -7,12 +7,18 @@ public layout -- ``param_groups`` (dicts with ``params``, ``lr``, ``name``) and
 ``density.py`` (and any code written against the reference's optimizer) treats both
 interchangeably; only ``step()`` differs: all groups are updated by ``egs_adam_step``
 (7 x 4 B of HBM traffic per parameter, no temporaries).
+
+``step(visible=mask)`` is the visibility-masked step of Taming-3DGS (gsplat's ``SelectiveAdam``) on libegs_adam.so
+(include/egs_adam.h): a Gaussian the step's views did not see keeps parameters AND moments bit for bit and
+is neither read nor written; a Gaussian they saw gets the dense update.  The state layout is the same.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
-from . import _lib
+from . import _adamlib, _lib
 
 NAMES = ("pws", "low_shs", "high_shs", "alphas_raw", "scales_raw", "rots_raw")
 REFERENCE_LRS = (0.001, 0.001, 0.001 / 20, 0.05, 0.005, 0.001)          # gsmodel.py:114-127
@@ -48,12 +54,34 @@ class FusedAdam:
                     p.grad.zero_()
 
     @torch.no_grad()
-    def step(self, factored_sh=None):
+    def step(self, factored_sh=None, visible=None):
         """``factored_sh`` = ``(rows, scale, pws, low_shs, high_shs | None)``: the step's SH gradient in its factored
         form (``dist_views.FactoredShGrad.take()``: dL/dcolour [N,3] and camera centre per view; ``scale`` = 1 / ranks
         for a mean over ranks, 1 for a sum) -- the SH tensors (``.grad`` None) are then updated by
-        ``egs_adam_sh_factored``, which forms each Gaussian's gradient row in LDS instead of reading it from memory."""
+        ``egs_adam_sh_factored``, which forms each Gaussian's gradient row in LDS instead of reading it from memory.
+
+        ``visible``: a contiguous ``bool`` / ``uint8`` tensor with one entry per Gaussian, on the parameters' device.
+        Rows whose entry is zero keep parameter, ``exp_avg`` and ``exp_avg_sq`` bit for bit (their gradient is never
+        read); the others get exactly the dense update.  Every tensor the step updates must have ``visible.numel()``
+        rows.  ``step`` counts the calls for the tensor as a whole (gsplat's bias correction), visible or not."""
         lib = _lib.load()
+        alib = None
+        if visible is not None:
+            alib = _adamlib.load()
+            if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8)):
+                raise ValueError("FusedAdam.step(visible=...): expected a bool or uint8 tensor")
+            if not (visible.dim() == 1 and visible.is_contiguous()):
+                raise ValueError("FusedAdam.step(visible=...): expected a contiguous 1-D mask, one entry per Gaussian")
+
+        def check_rows(t):
+            if visible is None:
+                return
+            if t.dim() < 1 or t.shape[0] != visible.numel():
+                raise ValueError("FusedAdam.step(visible=...): a tensor of shape %s does not have the mask's %d rows"
+                                 % (tuple(t.shape), visible.numel()))
+            if t.device != visible.device:
+                raise ValueError("FusedAdam.step(visible=...): the mask is on %s, the parameters on %s"
+                                 % (visible.device, t.device))
         # 1. validate EVERYTHING first: nothing of the optimizer's state may move for a step that is then refused (a
         #    bumped ``step`` without an update would leave wrong bias corrections behind: ADVICE r4)
         plain, keep = [], []      # keep: contiguous gradient copies, alive until the launch is enqueued
@@ -61,6 +89,7 @@ class FusedAdam:
             for p in g["params"]:
                 if p.grad is None:
                     continue
+                check_rows(p)
                 if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                     raise ValueError("FusedAdam needs contiguous float32 device parameters")
                 grad = p.grad.contiguous()
@@ -72,6 +101,7 @@ class FusedAdam:
             for t in ((low, high) if (high is not None and high.shape[1] > 0) else (low,)):
                 if t.grad is not None:
                     raise ValueError("FusedAdam.step(factored_sh=...): an SH tensor already holds a .grad")
+                check_rows(t)
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                     raise ValueError("FusedAdam needs contiguous float32 device parameters")
                 lrs = [float(g["lr"]) for g in self.param_groups if any(q is t for q in g["params"])]
@@ -93,10 +123,16 @@ class FusedAdam:
         stream = torch.cuda.current_stream().cuda_stream
         try:
             recs = []
+            n_vis = visible.numel() if visible is not None else 0
             for p, grad, lr in plain:
                 st = state_of(p)
-                recs.append(_lib.EgsAdamGroup(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(),
-                                              st["exp_avg_sq"].data_ptr(), p.numel(), lr, st["step"]))
+                if visible is None:
+                    recs.append(_lib.EgsAdamGroup(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(),
+                                                  st["exp_avg_sq"].data_ptr(), p.numel(), lr, st["step"]))
+                else:
+                    recs.append(_adamlib.EgsSparseAdamGroup(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(),
+                                                            st["exp_avg_sq"].data_ptr(), math.prod(p.shape[1:]), lr,
+                                                            st["step"]))
             if factored_sh is not None:
                 n = pws.shape[0]
                 groups = []
@@ -105,14 +141,25 @@ class FusedAdam:
                     groups.append(_lib.EgsAdamGroup(t.data_ptr(), None, st["exp_avg"].data_ptr(),
                                                     st["exp_avg_sq"].data_ptr(), t.numel(), lr, st["step"]))
                 K = low.shape[1] + (high.shape[1] if high is not None else 0)
-                _lib.check(lib.egs_adam_sh_factored(
-                    n, K, rows.shape[0], pws.data_ptr(), rows.data_ptr(), rows.shape[1], float(scale), groups[0],
-                    groups[1] if len(groups) > 1 else None, self.betas[0], self.betas[1], self.eps, stream))
+                if visible is None:
+                    _lib.check(lib.egs_adam_sh_factored(
+                        n, K, rows.shape[0], pws.data_ptr(), rows.data_ptr(), rows.shape[1], float(scale), groups[0],
+                        groups[1] if len(groups) > 1 else None, self.betas[0], self.betas[1], self.eps, stream))
+                else:
+                    _adamlib.check(alib.egs_sparse_adam_sh_factored(
+                        n, K, rows.shape[0], pws.data_ptr(), rows.data_ptr(), rows.shape[1], float(scale), groups[0],
+                        groups[1] if len(groups) > 1 else None, visible.data_ptr(), self.betas[0], self.betas[1],
+                        self.eps, stream))
                 del bumped[len(plain):]          # enqueued: the SH tensors' counters stand
             for i in range(0, len(recs), 8):
                 chunk = recs[i:i + 8]
-                arr = (_lib.EgsAdamGroup * len(chunk))(*chunk)
-                _lib.check(lib.egs_adam_step(len(chunk), arr, self.betas[0], self.betas[1], self.eps, stream))
+                if visible is None:
+                    arr = (_lib.EgsAdamGroup * len(chunk))(*chunk)
+                    _lib.check(lib.egs_adam_step(len(chunk), arr, self.betas[0], self.betas[1], self.eps, stream))
+                else:
+                    arr = (_adamlib.EgsSparseAdamGroup * len(chunk))(*chunk)
+                    _adamlib.check(alib.egs_sparse_adam_step(len(chunk), arr, n_vis, visible.data_ptr(), self.betas[0],
+                                                             self.betas[1], self.eps, stream))
                 for j in range(i, i + len(chunk)):
                     bumped[j] = None             # enqueued
         except BaseException:

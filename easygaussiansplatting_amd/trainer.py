@@ -83,7 +83,7 @@ class Trainer:
                  fused_activations: bool = True, view_streams: int = 4, factored_sh: bool = True, mode: str = "fused",
                  antialiased: bool = False, absgrad: bool = False, grad_threshold: float = None,
                  pose_opt: bool = False, pose_lr=(_pose.LR_ROT, _pose.LR_TRANS), strategy: str = "default",
-                 cap_max: int = None, mcmc_options: dict = None):
+                 cap_max: int = None, mcmc_options: dict = None, sparse_adam: bool = False):
         """``strategy``: how Gaussians are added and removed.  "default" is the reference's clone / split / prune /
         alpha reset (``density.DensityControl``).  "mcmc" (needs ``cap_max``, the hard limit on the number
         of Gaussians) is ``density.MCMCControl``: every step adds the opacity / scale regularisers' gradient before the
@@ -99,12 +99,24 @@ class Trainer:
         found for frozen-map refinement on a synthetic scene and NOT tuned for joint training, which nobody has
         measured.  With ``pose_opt`` the views of one ``step`` must be distinct cameras (a twist takes one Adam step
         per optimizer step; ``ValueError`` otherwise -- ``fit`` draws from a permutation and never repeats one).
-        Without ``pose_opt`` nothing in a step differs: no pose node, no extra tensor."""
+        Without ``pose_opt`` nothing in a step differs: no pose node, no extra tensor.
+
+        ``sparse_adam``: the visibility-masked optimizer step (needs ``fused_adam`` and the "default"
+        strategy).  A Gaussian that no view of the step saw -- on any rank: the visibility count is taken after the
+        all-reduce -- keeps its parameters and both Adam moments bit for bit and is neither read nor written; dense
+        Adam, the reference's, keeps moving it on its old momentum.  With ``sparse_adam=False`` nothing in a step
+        differs."""
         self.device = device
         if strategy not in ("default", "mcmc"):
             raise ValueError("Trainer(strategy=%r): expected 'default' or 'mcmc'" % (strategy,))
         if strategy == "mcmc" and cap_max is None:
             raise ValueError("Trainer(strategy='mcmc') needs cap_max, the hard limit on the number of Gaussians")
+        if sparse_adam and not fused_adam:
+            raise ValueError("Trainer(sparse_adam=True) needs fused_adam=True (the masked step is FusedAdam's)")
+        if sparse_adam and strategy == "mcmc":
+            raise ValueError("Trainer(sparse_adam=True) with strategy='mcmc': MCMC's regularisers and noise act on every "
+                             "Gaussian every step; combining the two is not supported")
+        self.sparse_adam = bool(sparse_adam)
         # how THIS trainer's renders are evaluated (function.RenderOptions.mode; "ops" needs fused_activations=False):
         # carried by every call, never by a process-wide switch -- two trainers in one process may differ
         self.mode = mode
@@ -294,7 +306,9 @@ class Trainer:
         self.vis_count += count
         if self.mcmc is not None:     # after the all-reduce: identical on every rank
             self.mcmc.add_regularisers(self.params)
-        if sh_rows is not None:
+        if self.sparse_adam:          # (count: after the all-reduce, so the mask is identical on every rank)
+            self.opt.step(factored_sh=sh_rows, visible=count > 0)
+        elif sh_rows is not None:
             self.opt.step(factored_sh=sh_rows)
         else:
             self.opt.step()

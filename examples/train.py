@@ -41,6 +41,9 @@ def main():
                     help="densification: the reference's clone / split / prune / alpha reset, or MCMC relocation with "
                          "a hard cap on the number of Gaussians (DESIGN §3.11; needs --cap-max)")
     ap.add_argument("--cap-max", type=int, default=None, help="--strategy mcmc: the largest number of Gaussians")
+    ap.add_argument("--sparse-adam", action="store_true",
+                    help="visibility-masked Adam (DESIGN §3.14): a Gaussian no view of the step saw keeps its parameters "
+                         "and moments; not with --strategy mcmc")
     ap.add_argument("--prune-importance-at", default="", metavar="E[,E...]",
                     help="epochs at whose end Gaussians are pruned on their blending weight over all training views "
                          "(DESIGN §3.12); needs --prune-threshold or --prune-fraction")
@@ -51,6 +54,8 @@ def main():
     a = ap.parse_args()
     if a.strategy == "mcmc" and a.cap_max is None:
         ap.error("--strategy mcmc needs --cap-max")
+    if a.sparse_adam and a.strategy == "mcmc":
+        ap.error("--sparse-adam is not supported with --strategy mcmc")
     prune_at = sorted({int(e) for e in a.prune_importance_at.split(",") if e.strip()})
     if prune_at and (a.prune_threshold is None) == (a.prune_fraction is None):
         ap.error("--prune-importance-at needs exactly one of --prune-threshold / --prune-fraction")
@@ -76,7 +81,8 @@ def main():
     steps = (len(ds) // views_per_step) * a.epochs
     tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size, antialiased=a.antialiased,
                  absgrad=a.absgrad, grad_threshold=a.grad_threshold, pose_opt=a.pose_opt,
-                 pose_lr=(a.pose_lr_rot, a.pose_lr_trans), strategy=a.strategy, cap_max=a.cap_max)
+                 pose_lr=(a.pose_lr_rot, a.pose_lr_trans), strategy=a.strategy, cap_max=a.cap_max,
+                 sparse_adam=a.sparse_adam)
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]
