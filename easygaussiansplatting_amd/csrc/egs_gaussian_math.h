@@ -505,8 +505,9 @@ __device__ __forceinline__ uint32_t bin_count_one(const BinParams& p, float ux, 
 // (k_bin_emit: which ones): both evaluate these functions on the same stored BinRec, so they must be bit-reproducible
 // across kernels -- no FMA contraction (pragma below), hardware rcp / sqrt (one instruction each, the same bits
 // wherever they are issued).  Conservative by construction: the x-extent of {footprint ellipse} n {8-pixel slab} is
-// exact in real arithmetic, the slab is taken continuous in y, and every bound is widened by `eps` (1 % of the
-// extent + 0.05 px, the slack of the draw kernels' own certain-miss box) before it is rounded to pixel centres.
+// exact in real arithmetic, the slab is taken continuous in y, and the slab's two y-bounds and the x-extent's two ends
+// are each widened by `eps` (1 % of the extent + 0.05 px, the slack of the draw kernels' own certain-miss box) before
+// the result is rounded to pixel centres; the footprint's own y-extent +-ymax is NOT widened (see foot_slab).
 struct Foot {
   float ux, uy, A, Bh, C, m;
   float det, rA, ymax, k, eps;
@@ -535,8 +536,11 @@ __device__ __forceinline__ Foot foot_setup(const BinRec& b) {
 __device__ __forceinline__ SlabPx foot_slab(const Foot& f, int Y0) {
   SlabPx o;
   o.pl = 0x7fffffff; o.pr = (int)0x80000000;
-  const float ya = fmaxf((float)Y0 - f.uy - f.eps, -f.ymax - f.eps);
-  const float yb = fminf((float)(Y0 + 7) - f.uy + f.eps, f.ymax + f.eps);
+  // (the slab is widened by eps, the footprint's own y-extent is not widened again: eps >= 1 % of ymax covers its
+  //  rounding, and a slab kept for y beyond +-ymax would be given the pixels around the centre line there -- a block up
+  //  to 2 eps above the ellipse's top, tests/test_gpu_footprint_lists.py)
+  const float ya = fmaxf((float)Y0 - f.uy - f.eps, -f.ymax);
+  const float yb = fminf((float)(Y0 + 7) - f.uy + f.eps, f.ymax);
   if (!(ya <= yb)) return o;
   const float yr = fminf(fmaxf(-f.k, ya), yb), yl = fminf(fmaxf(f.k, ya), yb);
   const float Am = f.A * f.m;

@@ -369,8 +369,10 @@ int egs_chain_rule(int n, int sh_dim, const float* dloss_dus, const float* dloss
  * reference `continue`s on every pixel (kernel.cu:246), so images and gradients are unchanged, but list positions
  * (and with them `contrib`) refer to the culled lists -- and every list value carries, above the low 28 bits of the
  * Gaussian index, the 4-bit mask of the 8x8 pixel blocks of the tile the footprint reaches; the draw stage takes
- * EGS_DRAW_CULLED_LISTS.  Needs `rec`.  Internal to the fused path: the seven-op surface (egs_splat_bin /
- * egs_splat_draw) always produces the reference's lists. */
+ * EGS_DRAW_CULLED_LISTS.  `final_tau` differs in one place: a tile whose every entry the cull drops is drawn as a tile
+ * without patches, so its `final_tau` is 0 (the convention for such tiles) where the unculled walk of entries that blend
+ * nowhere leaves 1; on every other tile it is bit-identical.  Needs `rec`.  Internal to the fused path: the seven-op
+ * surface (egs_splat_bin / egs_splat_draw) always produces the reference's lists. */
 #define EGS_FUSED_CULLED_LISTS 32
 /* Anti-aliased rendering (the 2D filter of Mip-Splatting): every Gaussian is binned and drawn with opacity alpha comp,
  * comp = sqrt(det(Sigma) / det(Sigma + 0.3 I)), Sigma the 2D covariance before the +0.3 dilation (which, like the
