@@ -10,6 +10,7 @@ around it, on hand-written HIP kernels for gfx950 behind a C ABI (``include/egs_
     loss       gau_loss (0.8 L1 + 0.2 (1 - SSIM)) as HIP kernels
     optim      FusedAdam;  density  DensityControl (prune / clone / split / alpha reset on the device)
     features   per-Gaussian feature vectors rendered through a finished forward's tile lists, their adjoint, lifting
+    appearance per-image bilateral grids of affine colour transforms (exposure / white balance / vignetting)
     trainer    the train.py loop, one camera view per GPU;  dist_views  the RCCL gradient exchange
     gau_io, colmap, dataset, knn, viewer   file formats, COLMAP scenes, nearest neighbours, viewer preprocess
     scene      deterministic synthetic scenes (tests, bench.py)

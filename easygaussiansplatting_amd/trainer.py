@@ -36,6 +36,7 @@ from . import features as _features
 from . import importance as _importance
 from .density import DensityControl, MCMCControl, expon_lr
 from . import pose as _pose
+from . import appearance as _appearance
 from .function import (Camera, GSFunction, GSPoseFunction, GSRawFunction, GSRawPoseFunction,
                        RenderOptions)
 from .loss import gau_loss, gau_loss_with_grad
@@ -83,7 +84,9 @@ class Trainer:
                  fused_activations: bool = True, view_streams: int = 4, factored_sh: bool = True, mode: str = "fused",
                  antialiased: bool = False, absgrad: bool = False, grad_threshold: float = None,
                  pose_opt: bool = False, pose_lr=(_pose.LR_ROT, _pose.LR_TRANS), strategy: str = "default",
-                 cap_max: int = None, mcmc_options: dict = None, sparse_adam: bool = False):
+                 cap_max: int = None, mcmc_options: dict = None, sparse_adam: bool = False,
+                 bilagrid: bool = False, bilagrid_shape=_appearance.DEFAULT_SHAPE, bilagrid_lr: float = 2e-3,
+                 bilagrid_tv: float = 10.0):
         """``strategy``: how Gaussians are added and removed.  "default" is the reference's clone / split / prune /
         alpha reset (``density.DensityControl``).  "mcmc" (needs ``cap_max``, the hard limit on the number
         of Gaussians) is ``density.MCMCControl``: every step adds the opacity / scale regularisers' gradient before the
@@ -105,7 +108,19 @@ class Trainer:
         strategy).  A Gaussian that no view of the step saw -- on any rank: the visibility count is taken after the
         all-reduce -- keeps its parameters and both Adam moments bit for bit and is neither read nor written; dense
         Adam, the reference's, keeps moving it on its old momentum.  With ``sparse_adam=False`` nothing in a step
-        differs."""
+        differs.
+
+        ``bilagrid``: per-image appearance compensation (every ``mode``).  Every training image gets a
+        bilateral grid of 3 x 4 affine colour transforms (``appearance.GridTable``, ``bilagrid_shape`` = (Gw, Gh, L),
+        identity at the start); the loss of a view is taken on the render sliced through that view's grid
+        (``appearance.slice_forward`` / ``slice_backward``, HIP, no autograd node), and after the optimizer step the
+        grids of the views rendered in the step take a per-row Adam step on the gradient of image loss +
+        ``bilagrid_tv`` x total variation.  ``step`` returns the image loss on the corrected image; the TV term of the
+        step's grids is kept as ``last_tv``.  ``bilagrid_lr`` and ``bilagrid_tv`` are gsplat's defaults: NOT tuned here,
+        and nobody has measured them on this code.  The views of one ``step`` must be distinct (a grid takes one Adam
+        step per optimizer step; ``ValueError`` otherwise).  The grids belong to the training images: a novel view has
+        none (``corrected`` exists for inspection).  With ``bilagrid=False`` nothing in a step differs: no table, no
+        extra tensor, no extra launch."""
         self.device = device
         if strategy not in ("default", "mcmc"):
             raise ValueError("Trainer(strategy=%r): expected 'default' or 'mcmc'" % (strategy,))
@@ -117,6 +132,12 @@ class Trainer:
             raise ValueError("Trainer(sparse_adam=True) with strategy='mcmc': MCMC's regularisers and noise act on every "
                              "Gaussian every step; combining the two is not supported")
         self.sparse_adam = bool(sparse_adam)
+        self.bilagrid = bool(bilagrid)
+        if self.bilagrid:
+            try:
+                self.bilagrid_shape = _appearance._shape3(bilagrid_shape)
+            except (TypeError, ValueError) as e:
+                raise ValueError("Trainer(bilagrid_shape=%r): %s" % (bilagrid_shape, e)) from e
         # how THIS trainer's renders are evaluated (function.RenderOptions.mode; "ops" needs fused_activations=False):
         # carried by every call, never by a process-wide switch -- two trainers in one process may differ
         self.mode = mode
@@ -167,6 +188,13 @@ class Trainer:
             self.pose_table = _pose.PoseTable(self.cams, device, lr_rot=pose_lr[0], lr_trans=pose_lr[1])
             # dL/dtwist of the step, dense [V,6]: the rows of the views this rank rendered, zero elsewhere
             self.pose_grad = torch.zeros((len(self.cams), 6), device=device)
+        # appearance compensation: the table, the step's gradient rows [len(view_ids), 12, L, Gh, Gw] (row k belongs to
+        # view_ids[k]; this rank's rows, zero elsewhere -- never a dense [V, ...] tensor) and the TV term of the last step
+        self.grid_table = self.grid_grad = self.last_tv = None
+        self._grid_rows = {}
+        self.bilagrid_tv = float(bilagrid_tv)
+        if self.bilagrid:
+            self.grid_table = _appearance.GridTable(len(self.cams), self.bilagrid_shape, lr=bilagrid_lr, device=device)
 
     _KEYS = ("pws", "low_shs", "high_shs", "alphas_raw", "scales_raw", "rots_raw")
 
@@ -220,7 +248,13 @@ class Trainer:
                     image, mask = GSFunction.apply(*activate(p), us, self.cams[v], opts)
                 # loss / n_views (train.py:52-57 with the mean over the step's views): the loss kernels produce the
                 # scaled dL/dimage themselves, backward starts at the image
-                stats, dimage = gau_loss_with_grad(image.detach(), self.gts[v], grad_scale=1.0 / n_views)
+                if self.bilagrid:     # the loss sees the render through the view's grid; no autograd node
+                    raw, grid = image.detach(), self.grid_table.grids[v]
+                    stats, dcorrected = gau_loss_with_grad(_appearance.slice_forward(raw, grid), self.gts[v],
+                                                           grad_scale=1.0 / n_views)
+                    dimage = _appearance.slice_backward(raw, grid, dcorrected, dgrid=self.grid_grad[self._grid_rows[v]])
+                else:
+                    stats, dimage = gau_loss_with_grad(image.detach(), self.gts[v], grad_scale=1.0 / n_views)
                 image.backward(dimage)
                 if tw is not None:      # (per view, never accumulated in the kernel; one row per camera)
                     self.pose_grad[v] += tw.grad
@@ -250,9 +284,13 @@ class Trainer:
         if self.pose_opt and len(set(view_ids)) != len(view_ids):
             raise ValueError("step() with pose_opt: a camera appears twice in %r (its twist takes one step per step)"
                              % (list(view_ids),))
+        if self.bilagrid and len(set(view_ids)) != len(view_ids):
+            raise ValueError("step() with bilagrid: a view appears twice in %r (its grid takes one step per step)"
+                             % (list(view_ids),))
         mine = [view_ids[i] for i in DV.views_for_rank(len(view_ids), self.rank, self.world)]
         self.opt.zero_grad(set_to_none=True)
         self._clear_pose_grad()
+        self._clear_grid_grad(view_ids)
         # The views are rendered with deferred validation: the host does not wait for a patch count inside the
         # step.  commit() (one wait for the binning stage of the last view, while its draw and backward
         # kernels are still queued) tells whether some view outgrew the buffers sized from earlier renders;
@@ -284,6 +322,7 @@ class Trainer:
             self.redone_steps += 1
             self.opt.zero_grad(set_to_none=True)
             self._clear_pose_grad()
+            self._clear_grid_grad(view_ids)
             if fx is not None:
                 fx.restart()
             loss_sum, gnorm, count = self._render_views(mine, len(view_ids), opts)   # validated render by render
@@ -299,9 +338,15 @@ class Trainer:
             else:
                 fx.finish(self.params["pws"], self.params["low_shs"], self.params["high_shs"], average=False)
             others = {k: v for k, v in self.params.items() if k not in ("low_shs", "high_shs")}
+        if self.bilagrid:    # TV of the step's grids, added by the rank that rendered the view: once per row
+            self.last_tv = torch.zeros((), device=self.device)
+            for v in mine:
+                self.last_tv += _appearance.tv(self.grid_table.grids[v], self.bilagrid_tv,
+                                               self.grid_grad[self._grid_rows[v]])
         if self.world > 1:   # sum over ranks of (sum over local views)/V == mean over all views
             DV.allreduce_sum_(DV.coalesce_grads(list(others.values())) + [gnorm, count, loss_sum] +
-                              ([self.pose_grad] if self.pose_opt else []))
+                              ([self.pose_grad] if self.pose_opt else []) +
+                              ([self.grid_grad, self.last_tv] if self.bilagrid else []))
         self.grad_accum += gnorm
         self.vis_count += count
         if self.mcmc is not None:     # after the all-reduce: identical on every rank
@@ -316,6 +361,8 @@ class Trainer:
             self.mcmc.inject_noise(self.params, [g["lr"] for g in self.opt.param_groups if g["name"] == "pws"][0])
         if self.pose_opt:       # the cameras of this step only: the others keep twist, moments and step count
             self.pose_table.step(view_ids, self.pose_grad)
+        if self.bilagrid:       # the views of this step only: the other grids keep values, moments and step count
+            self.grid_table.step(view_ids, self.grid_grad)
         self.density.update_pws_lr(self.opt)                                     # gsmodel.py:180-183, 332-338
         self.iteration += 1
         mean = loss_sum / len(view_ids)
@@ -325,6 +372,35 @@ class Trainer:
         """the pose gradients of a step start from zero -- also when the step is redone"""
         if self.pose_grad is not None:
             self.pose_grad.zero_()
+
+    def _clear_grid_grad(self, view_ids):
+        """the grid gradients of a step start from zero -- also when the step is redone.  One row per view of the step
+        (kept across steps of the same size), and the view -> row map the renders use"""
+        if not self.bilagrid:
+            return
+        rows = (len(view_ids),) + tuple(self.grid_table.grids.shape[1:])
+        if self.grid_grad is None or tuple(self.grid_grad.shape) != rows:
+            self.grid_grad = torch.zeros(rows, device=self.device)
+        else:
+            self.grid_grad.zero_()
+        self._grid_rows = {int(v): k for k, v in enumerate(view_ids)}
+
+    def grids(self):
+        """-> [V,12,L,Gh,Gw]: the current bilateral grid of every training image (None without ``bilagrid``)"""
+        return None if self.grid_table is None else self.grid_table.grids
+
+    def save_grids(self, fn: str):
+        """The grids as an ``.npz``: ``ids`` [V] (``Camera.id``), ``grids`` [V,12,L,Gh,Gw], ``shape`` = (Gw, Gh, L)."""
+        if self.grid_table is None:
+            raise ValueError("save_grids: this trainer has no grids (bilagrid=False)")
+        self.grid_table.save(fn, ids=[getattr(c, "id", i) for i, c in enumerate(self.cams)])
+
+    def corrected(self, view_id: int, image):
+        """``image`` [3,H,W] through the grid of training image ``view_id`` -- what the loss of that view compares with
+        its photograph.  For inspection: a novel view has no grid."""
+        if self.grid_table is None:
+            raise ValueError("corrected: this trainer has no grids (bilagrid=False)")
+        return _appearance.slice_forward(image.detach(), self.grid_table.grids[int(view_id)])
 
     def poses(self):
         """-> (Rcw [V,3,3], tcw [V,3]): the current pose of every camera (the stored ones without ``pose_opt``)"""

@@ -44,6 +44,12 @@ def main():
     ap.add_argument("--sparse-adam", action="store_true",
                     help="visibility-masked Adam (DESIGN §3.14): a Gaussian no view of the step saw keeps its parameters "
                          "and moments; not with --strategy mcmc")
+    ap.add_argument("--bilagrid", action="store_true",
+                    help="per-image appearance compensation (DESIGN §3.15): a bilateral grid of affine colour transforms "
+                         "per training image absorbs exposure, white balance and vignetting; the grids are saved as "
+                         "grids.npz")
+    ap.add_argument("--bilagrid-shape", type=int, nargs=3, default=(16, 16, 8), metavar=("GW", "GH", "L"),
+                    help="--bilagrid: nodes of a grid along x, y and luminance (1 1 1 = exposure / white balance only)")
     ap.add_argument("--prune-importance-at", default="", metavar="E[,E...]",
                     help="epochs at whose end Gaussians are pruned on their blending weight over all training views "
                          "(DESIGN §3.12); needs --prune-threshold or --prune-fraction")
@@ -82,7 +88,7 @@ def main():
     tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size, antialiased=a.antialiased,
                  absgrad=a.absgrad, grad_threshold=a.grad_threshold, pose_opt=a.pose_opt,
                  pose_lr=(a.pose_lr_rot, a.pose_lr_trans), strategy=a.strategy, cap_max=a.cap_max,
-                 sparse_adam=a.sparse_adam)
+                 sparse_adam=a.sparse_adam, bilagrid=a.bilagrid, bilagrid_shape=tuple(a.bilagrid_shape))
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]
@@ -101,6 +107,8 @@ def main():
         tr.save(os.path.join(a.out, "final.npy"))
         if a.pose_opt:
             tr.save_poses(os.path.join(a.out, "poses.npz"))
+        if a.bilagrid:
+            tr.save_grids(os.path.join(a.out, "grids.npz"))
         print("Training is finished.")
     if world > 1:
         dist.destroy_process_group()
