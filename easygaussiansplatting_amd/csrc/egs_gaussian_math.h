@@ -275,6 +275,29 @@ __device__ __forceinline__ ShDir<NC> sh_basis_f(f3 pw, const float* __restrict__
   }
   return o;
 }
+// Gaussian i's SH gradient row from the FACTORED form of a step's SH gradient (dist_views.FactoredShGrad), added into
+// gsh[3 NC], which the caller has zeroed:  gsh[3 c + rgb] = scale * sum_v dL/dcolour_v[rgb] * basis_c(pw - twc_v)
+// -- per view the outer product of eq (5), gsmodel.py:84-85.  rows: [views][stride] floats, row v = {dL/dcolour [n][3],
+// twc[3], padding}.  The ONE place this arithmetic is written: k_sh_grad_views followed by Adam and the factored Adam
+// kernels (egs_adam_device.h) must agree to the bit, so they all call it.
+template <int NC>
+__device__ __forceinline__ void sh_grad_row(f3 pw, const float* rows, int64_t stride, int views, int n,
+                                            int i, float scale, float* gsh) {
+  for (int v = 0; v < views; ++v) {
+    const float* row = rows + (size_t)v * stride;
+    const f3 gc = ld3(row + 3 * (size_t)i);
+    if (gc.x == 0.f && gc.y == 0.f && gc.z == 0.f) continue;   // not drawn in this view
+    const ShDir<NC> d = sh_basis_f<NC>(pw, row + 3 * (size_t)n);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      gsh[3 * c] = __builtin_fmaf(gc.x, d.B[c], gsh[3 * c]);
+      gsh[3 * c + 1] = __builtin_fmaf(gc.y, d.B[c], gsh[3 * c + 1]);
+      gsh[3 * c + 2] = __builtin_fmaf(gc.z, d.B[c], gsh[3 * c + 2]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3 * NC; ++k) gsh[k] *= scale;
+}
 template <int NC>
 __device__ __forceinline__ void sh_color_f(const ShDir<NC>& o, const float* sh, float* col) {
   float cr = 0.5f, cg = 0.5f, cb = 0.5f;  // no clamp to >= 0 (kernel.cu:652,725)

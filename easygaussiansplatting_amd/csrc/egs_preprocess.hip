@@ -957,23 +957,7 @@ __global__ __launch_bounds__(256) void k_sh_grad_views(int n, int views, const f
   float gsh[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) gsh[k] = 0.f;
-  if (i < n) {
-    const f3 pw = ld3(pws + 3 * (size_t)i);
-    for (int v = 0; v < views; ++v) {
-      const float* row = rows + (size_t)v * stride;
-      const f3 g = ld3(row + 3 * (size_t)i);
-      if (g.x == 0.f && g.y == 0.f && g.z == 0.f) continue;   // not drawn in this view
-      const ShDir<NC> d = sh_basis_f<NC>(pw, row + 3 * (size_t)n);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        gsh[3 * c] = __builtin_fmaf(g.x, d.B[c], gsh[3 * c]);
-        gsh[3 * c + 1] = __builtin_fmaf(g.y, d.B[c], gsh[3 * c + 1]);
-        gsh[3 * c + 2] = __builtin_fmaf(g.z, d.B[c], gsh[3 * c + 2]);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) gsh[k] *= scale;
-  }
+  if (i < n) sh_grad_row<NC>(ld3(pws + 3 * (size_t)i), rows, stride, views, n, i, scale, gsh);
   if constexpr (RAW) {
     if (i < n) {
 #pragma unroll

@@ -64,14 +64,21 @@ class FusedAdam:
         Rows whose entry is zero keep parameter, ``exp_avg`` and ``exp_avg_sq`` bit for bit (their gradient is never
         read); the others get exactly the dense update.  Every tensor the step updates must have ``visible.numel()``
         rows.  ``step`` counts the calls for the tensor as a whole (gsplat's bias correction), visible or not."""
+        # dense or masked: the library's ``check``, its record type and its two entry points, chosen ONCE; the mask
+        # arguments (``mask_n`` after the groups of a plain step, ``mask`` after those of the factored one) are all else
+        # that differs
         lib = _lib.load()
-        alib = None
+        check, Group, step_fn, sh_fn = _lib.check, _lib.EgsAdamGroup, lib.egs_adam_step, lib.egs_adam_sh_factored
+        mask_n, mask = (), ()
         if visible is not None:
             alib = _adamlib.load()
+            check, Group = _adamlib.check, _adamlib.EgsSparseAdamGroup
+            step_fn, sh_fn = alib.egs_sparse_adam_step, alib.egs_sparse_adam_sh_factored
             if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8)):
                 raise ValueError("FusedAdam.step(visible=...): expected a bool or uint8 tensor")
             if not (visible.dim() == 1 and visible.is_contiguous()):
                 raise ValueError("FusedAdam.step(visible=...): expected a contiguous 1-D mask, one entry per Gaussian")
+            mask_n, mask = (visible.numel(), visible.data_ptr()), (visible.data_ptr(),)
 
         def check_rows(t):
             if visible is None:
@@ -123,16 +130,10 @@ class FusedAdam:
         stream = torch.cuda.current_stream().cuda_stream
         try:
             recs = []
-            n_vis = visible.numel() if visible is not None else 0
             for p, grad, lr in plain:
-                st = state_of(p)
-                if visible is None:
-                    recs.append(_lib.EgsAdamGroup(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(),
-                                                  st["exp_avg_sq"].data_ptr(), p.numel(), lr, st["step"]))
-                else:
-                    recs.append(_adamlib.EgsSparseAdamGroup(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(),
-                                                            st["exp_avg_sq"].data_ptr(), math.prod(p.shape[1:]), lr,
-                                                            st["step"]))
+                st = state_of(p)           # (a dense record counts floats, a masked one floats per Gaussian)
+                recs.append(Group(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                                  p.numel() if visible is None else math.prod(p.shape[1:]), lr, st["step"]))
             if factored_sh is not None:
                 n = pws.shape[0]
                 groups = []
@@ -141,25 +142,14 @@ class FusedAdam:
                     groups.append(_lib.EgsAdamGroup(t.data_ptr(), None, st["exp_avg"].data_ptr(),
                                                     st["exp_avg_sq"].data_ptr(), t.numel(), lr, st["step"]))
                 K = low.shape[1] + (high.shape[1] if high is not None else 0)
-                if visible is None:
-                    _lib.check(lib.egs_adam_sh_factored(
-                        n, K, rows.shape[0], pws.data_ptr(), rows.data_ptr(), rows.shape[1], float(scale), groups[0],
-                        groups[1] if len(groups) > 1 else None, self.betas[0], self.betas[1], self.eps, stream))
-                else:
-                    _adamlib.check(alib.egs_sparse_adam_sh_factored(
-                        n, K, rows.shape[0], pws.data_ptr(), rows.data_ptr(), rows.shape[1], float(scale), groups[0],
-                        groups[1] if len(groups) > 1 else None, visible.data_ptr(), self.betas[0], self.betas[1],
-                        self.eps, stream))
+                check(sh_fn(n, K, rows.shape[0], pws.data_ptr(), rows.data_ptr(), rows.shape[1], float(scale), groups[0],
+                            groups[1] if len(groups) > 1 else None, *mask, self.betas[0], self.betas[1], self.eps,
+                            stream))
                 del bumped[len(plain):]          # enqueued: the SH tensors' counters stand
             for i in range(0, len(recs), 8):
                 chunk = recs[i:i + 8]
-                if visible is None:
-                    arr = (_lib.EgsAdamGroup * len(chunk))(*chunk)
-                    _lib.check(lib.egs_adam_step(len(chunk), arr, self.betas[0], self.betas[1], self.eps, stream))
-                else:
-                    arr = (_adamlib.EgsSparseAdamGroup * len(chunk))(*chunk)
-                    _adamlib.check(alib.egs_sparse_adam_step(len(chunk), arr, n_vis, visible.data_ptr(), self.betas[0],
-                                                             self.betas[1], self.eps, stream))
+                check(step_fn(len(chunk), (Group * len(chunk))(*chunk), *mask_n, self.betas[0], self.betas[1], self.eps,
+                              stream))
                 for j in range(i, i + len(chunk)):
                     bumped[j] = None             # enqueued
         except BaseException:

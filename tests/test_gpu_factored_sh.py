@@ -188,17 +188,15 @@ def test_sh_grad_views_c_abi_against_the_oracle_basis():
     assert not out.any()
 
 
-@pytest.mark.parametrize("K", [48, 12, 3])
-@pytest.mark.parametrize("raw", [False, True])
-def test_fused_adam_from_factored_rows_equals_rows_then_adam(raw, K):
+def _factored_adam_equals_rows_then_adam(raw, K, n):
     """``FusedAdam.step(factored_sh=...)`` (``egs_adam_sh_factored``: every Gaussian's SH gradient row formed in LDS
     and consumed there) == ``egs_sh_grad_views`` into ``.grad`` followed by the ordinary step, on the same rows:
-    parameters and both moments, three steps, two views, a row count that is not a multiple of 64."""
+    parameters and both moments, bit for bit, three steps, two views."""
     from easygaussiansplatting_amd import _lib, dist_views as DV
     from easygaussiansplatting_amd.optim import FusedAdam
     lib = _lib.load()
     torch.manual_seed(3)
-    n, V = 4037, 2
+    V = 2
     stride = DV.FactoredShGrad.row_stride(n)
     pws = (torch.randn(n, 3, device="cuda") * 3).contiguous()
 
@@ -234,6 +232,23 @@ def test_fused_adam_from_factored_rows_equals_rows_then_adam(raw, K):
                 assert torch.equal(oa.state[a][key], ob.state[b][key]), (step, key)
             assert oa.state[a]["step"] == ob.state[b]["step"] == step + 1
     assert float((A[0].detach() - tensors()[0].detach()).abs().max()) > 1e-4      # the parameters did move
+
+
+@pytest.mark.parametrize("K", [48, 27, 12, 3])
+@pytest.mark.parametrize("raw", [False, True])
+def test_fused_adam_from_factored_rows_equals_rows_then_adam(raw, K):
+    """Every SH width (K = 27 included: NC = 9) at a row count that is not a multiple of 64."""
+    _factored_adam_equals_rows_then_adam(raw, K, 4037)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65])
+@pytest.mark.parametrize("K", [48, 27, 12, 3])
+@pytest.mark.parametrize("raw", [False, True])
+def test_fused_adam_from_factored_rows_at_workgroup_edges(raw, K, n):
+    """The same at a single row, a workgroup of 64 rows that is one short of full, exactly full, and one row into a
+    second workgroup: where ``here = min(64, n - base)`` and the float4 / scalar-tail split of a workgroup's elements
+    (``e0 + 4 <= cnt``) change."""
+    _factored_adam_equals_rows_then_adam(raw, K, n)
 
 
 @pytest.mark.parametrize("views", [[0], [0, 1, 2]])
