@@ -6,6 +6,12 @@ Gaussians (cached as ``points3D.npy`` next to the model, like the reference) and
 (sic) = 1.1 x the largest camera-centre distance from the mean centre (gausplat_dataset.py:67-69).
 PIL decodes the images (the reference goes through torchvision's ``to_tensor``: uint8 HWC -> float
 CHW / 255).
+
+``GSplatDataset(path, masks=True)`` also collects a per-pixel loss weight per image (``.weights[i]``: float32 [H,W] in
+[0,1] on the device, or None), for ``Trainer(pixel_weights=ds.weights)``.  Looked for in this order:
+``path/masks/<image file name>.png`` (COLMAP's convention: ``images/a.jpg`` -> ``masks/a.jpg.png``, 0 = ignore),
+``path/masks/<stem>.png``, the image's own alpha channel.  The mask is read as 8-bit grey, resized with the image and
+scaled by 1/255.
 """
 from __future__ import annotations
 
@@ -30,8 +36,20 @@ def _to_tensor(img, device):
     return torch.from_numpy(a).to(device).permute(2, 0, 1).to(torch.float32).div_(255.0).contiguous()
 
 
+def _weight_source(path, name, image):
+    """The image's mask as a PIL "L" image, or None: masks/<name>.png, masks/<stem>.png, the alpha channel."""
+    from PIL import Image
+    for cand in (name + ".png", os.path.splitext(name)[0] + ".png"):
+        fn = os.path.join(path, "masks", cand)
+        if os.path.exists(fn):
+            return Image.open(fn).convert("L")
+    if "A" in image.getbands():
+        return image.getchannel("A")
+    return None
+
+
 class GSplatDataset(torch.utils.data.Dataset):
-    def __init__(self, path, resize_rate=1, device="cuda") -> None:
+    def __init__(self, path, resize_rate=1, device="cuda", masks=False) -> None:
         super().__init__()
         from PIL import Image
         self.device = device
@@ -39,12 +57,16 @@ class GSplatDataset(torch.utils.data.Dataset):
         sparse = os.path.join(path, "sparse", "0")
         camera_params, image_params = colmap.read_model(sparse, ext=".bin")
         self.cameras, self.images = [], []
+        self.weights = [] if masks else None
         for ip in image_params.values():
             cp = camera_params[ip.camera_id]
             im_path = os.path.join(path, "images", ip.name)
             image = Image.open(im_path)
+            mask = _weight_source(path, ip.name, image) if masks else None
             if resize_rate != 1:
                 image = image.resize((int(image.width * resize_rate), int(image.height * resize_rate)))
+            if mask is not None and mask.size != image.size:      # (resized with the image; a mask of another size too)
+                mask = mask.resize(image.size)
             w_scale, h_scale = image.width / cp.width, image.height / cp.height
             # the reference reads params[0..3] as fx, fy, cx, cy, i.e. it assumes a PINHOLE-like model
             # (gausplat_dataset.py:50-53); SIMPLE_* models store (f, cx, cy)
@@ -60,6 +82,9 @@ class GSplatDataset(torch.utils.data.Dataset):
             self.cameras.append(Camera(ip.id, image.width, image.height, float(fx), float(fy), float(cx), float(cy),
                                        Rcw, tcw, im_path, device))
             self.images.append(_to_tensor(image, device))
+            if masks:
+                self.weights.append(None if mask is None else torch.from_numpy(np.array(mask, dtype=np.uint8)).to(device)
+                                    .to(torch.float32).div_(255.0).contiguous())
         cache = os.path.join(sparse, "points3D.npy")
         if os.path.exists(cache):
             self.gs = np.load(cache)

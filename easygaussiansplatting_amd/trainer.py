@@ -78,6 +78,38 @@ def make_optimizer(p, fused=True):
     return cls(adam_groups(p), lr=0.0, eps=1e-15)
 
 
+def _checked_pixel_weights(pixel_weights, gt_images, device):
+    """``Trainer(pixel_weights=...)``, checked once (host synchronisations are fine here) -> None, or a list with one
+    float32 [H,W] tensor on ``device`` or None per view.  ValueError names the view."""
+    if pixel_weights is None:
+        return None
+    weights, gts = list(pixel_weights), list(gt_images)
+    if len(weights) != len(gts):
+        raise ValueError("Trainer(pixel_weights=...): %d entries for %d views (one per camera; None for a view that "
+                         "counts every pixel)" % (len(weights), len(gts)))
+    out = []
+    for v, (w, gt) in enumerate(zip(weights, gts)):
+        if w is None:
+            out.append(None)
+            continue
+        what = "Trainer(pixel_weights=...): view %d" % v
+        if not isinstance(w, torch.Tensor) or w.dtype not in (torch.float32, torch.bool, torch.uint8):
+            raise ValueError("%s must be a float32, bool or uint8 tensor, got %s"
+                             % (what, w.dtype if isinstance(w, torch.Tensor) else type(w).__name__))
+        if tuple(w.shape) != tuple(gt.shape[-2:]):
+            raise ValueError("%s has shape %s, its ground-truth image is %s"
+                             % (what, list(w.shape), list(gt.shape[-2:])))
+        w = (w if w.dtype == torch.float32 else (w != 0)).to(device=device, dtype=torch.float32).contiguous()
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("%s holds a non-finite weight" % what)
+        if bool((w < 0).any()):
+            raise ValueError("%s holds a negative weight" % what)
+        if not bool((w > 0).any()):
+            raise ValueError("%s is all zero: the view would have no loss (drop the view instead)" % what)
+        out.append(w)
+    return out
+
+
 class Trainer:
     def __init__(self, scene, cameras: Sequence, gt_images: Sequence[torch.Tensor], max_steps: int,
                  scene_size: float = 1.0, device="cuda", fused_adam: bool = True, seed: int = 0,
@@ -86,7 +118,7 @@ class Trainer:
                  pose_opt: bool = False, pose_lr=(_pose.LR_ROT, _pose.LR_TRANS), strategy: str = "default",
                  cap_max: int = None, mcmc_options: dict = None, sparse_adam: bool = False,
                  bilagrid: bool = False, bilagrid_shape=_appearance.DEFAULT_SHAPE, bilagrid_lr: float = 2e-3,
-                 bilagrid_tv: float = 10.0):
+                 bilagrid_tv: float = 10.0, pixel_weights: Sequence = None):
         """``strategy``: how Gaussians are added and removed.  "default" is the reference's clone / split / prune /
         alpha reset (``density.DensityControl``).  "mcmc" (needs ``cap_max``, the hard limit on the number
         of Gaussians) is ``density.MCMCControl``: every step adds the opacity / scale regularisers' gradient before the
@@ -120,8 +152,19 @@ class Trainer:
         and nobody has measured them on this code.  The views of one ``step`` must be distinct (a grid takes one Adam
         step per optimizer step; ``ValueError`` otherwise).  The grids belong to the training images: a novel view has
         none (``corrected`` exists for inspection).  With ``bilagrid=False`` nothing in a step differs: no table, no
-        extra tensor, no extra launch."""
+        extra tensor, no extra launch.
+
+        ``pixel_weights``: per-pixel loss weights (masks; every ``mode``).  A sequence with one entry per
+        camera: a tensor [H,W] of the view's ground-truth size (float32 >= 0, or bool / uint8 read as 0 / 1), or None for
+        a view that counts every pixel (it takes the unweighted kernels).  Checked once, here (shape, finite, >= 0, not
+        all zero: ``ValueError`` naming the view).  A weighted view's loss is sum w |x - y| / (3 sum w) and
+        sum w S / (3 sum w): EVERY VIEW IS NORMALISED BY ITS OWN sum w, so a view that is 90 % masked counts as much in
+        the step's mean as an unmasked one.  A pixel with w = 0 still receives SSIM gradient from weighted pixels up to
+        5 px away; for a hard exclusion dilate the mask by 5 px.  With ``bilagrid`` the weighted loss is taken on the
+        corrected image.  ``step`` returns the mean of the (weighted) losses.  With ``pixel_weights=None`` nothing in a
+        step differs: no extra tensor, no extra launch, libegs_wloss.so is not loaded."""
         self.device = device
+        self.pixel_weights = _checked_pixel_weights(pixel_weights, gt_images, device)
         if strategy not in ("default", "mcmc"):
             raise ValueError("Trainer(strategy=%r): expected 'default' or 'mcmc'" % (strategy,))
         if strategy == "mcmc" and cap_max is None:
@@ -248,13 +291,15 @@ class Trainer:
                     image, mask = GSFunction.apply(*activate(p), us, self.cams[v], opts)
                 # loss / n_views (train.py:52-57 with the mean over the step's views): the loss kernels produce the
                 # scaled dL/dimage themselves, backward starts at the image
+                wv = None if self.pixel_weights is None else self.pixel_weights[v]    # (None: the unweighted kernels)
                 if self.bilagrid:     # the loss sees the render through the view's grid; no autograd node
                     raw, grid = image.detach(), self.grid_table.grids[v]
                     stats, dcorrected = gau_loss_with_grad(_appearance.slice_forward(raw, grid), self.gts[v],
-                                                           grad_scale=1.0 / n_views)
+                                                           grad_scale=1.0 / n_views, weight=wv)
                     dimage = _appearance.slice_backward(raw, grid, dcorrected, dgrid=self.grid_grad[self._grid_rows[v]])
                 else:
-                    stats, dimage = gau_loss_with_grad(image.detach(), self.gts[v], grad_scale=1.0 / n_views)
+                    stats, dimage = gau_loss_with_grad(image.detach(), self.gts[v], grad_scale=1.0 / n_views,
+                                                       weight=wv)
                 image.backward(dimage)
                 if tw is not None:      # (per view, never accumulated in the kernel; one row per camera)
                     self.pose_grad[v] += tw.grad

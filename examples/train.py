@@ -50,6 +50,9 @@ def main():
                          "grids.npz")
     ap.add_argument("--bilagrid-shape", type=int, nargs=3, default=(16, 16, 8), metavar=("GW", "GH", "L"),
                     help="--bilagrid: nodes of a grid along x, y and luminance (1 1 1 = exposure / white balance only)")
+    ap.add_argument("--masks", action="store_true",
+                    help="per-pixel loss weights (DESIGN §3.16): masks/<image file name>.png (COLMAP's convention, 0 = "
+                         "ignore), masks/<stem>.png or the image's alpha channel; an image without one counts every pixel")
     ap.add_argument("--prune-importance-at", default="", metavar="E[,E...]",
                     help="epochs at whose end Gaussians are pruned on their blending weight over all training views "
                          "(DESIGN §3.12); needs --prune-threshold or --prune-fraction")
@@ -79,7 +82,7 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     rank = dist.get_rank() if world > 1 else 0
     print("Try to training %s ..." % a.path) if rank == 0 else None
-    ds = GSplatDataset(a.path, resize_rate=a.resize)
+    ds = GSplatDataset(a.path, resize_rate=a.resize, masks=a.masks)
     gs = ds.gs
     start = S.Scene(gs["pw"].copy(), gs["rot"].copy(), gs["scale"].copy(), gs["alpha"].copy(), gs["sh"].copy(),
                     None)
@@ -88,7 +91,8 @@ def main():
     tr = Trainer(start, ds.cameras, ds.images, max_steps=steps, scene_size=ds.sence_size, antialiased=a.antialiased,
                  absgrad=a.absgrad, grad_threshold=a.grad_threshold, pose_opt=a.pose_opt,
                  pose_lr=(a.pose_lr_rot, a.pose_lr_trans), strategy=a.strategy, cap_max=a.cap_max,
-                 sparse_adam=a.sparse_adam, bilagrid=a.bilagrid, bilagrid_shape=tuple(a.bilagrid_shape))
+                 sparse_adam=a.sparse_adam, bilagrid=a.bilagrid, bilagrid_shape=tuple(a.bilagrid_shape),
+                 pixel_weights=ds.weights)
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]
