@@ -1,14 +1,19 @@
-// The fused training loss's device code as templates: one forward body and one gradient body with a `bool WEIGHTED`
-// parameter, wrapped in __global__ kernels by the source file that launches them.  The <false> instances are k_ssim_fwd /
-// k_ssim_bwd of egs_loss.hip (libegs_hip.so: egs_gau_loss, every pixel counts once) with the floating-point contractions
-// of that build written out; every weighted statement sits behind `if constexpr (WEIGHTED)`.  The <true> instances are
-// egs_wloss.hip's (libegs_wloss.so: egs_wloss, a weight per pixel).
+// Fused training loss for gfx950: gau_loss = (1-lambda) * L1 + lambda * (1 - SSIM)
+// (reference gsplat/pytorch_ssim.py:10-66: five depthwise 11x11 Gaussian-window conv2d
+// calls forward plus their autograd backward in PyTorch -- measured 10.9 ms per 1920x1080
+// image on MI355X).  Here: two tiled kernels, separable 11-tap window staged in LDS,
+// producing the loss AND dL/dimage (the input of splatB) directly.
 //
-// egs_loss.hip does NOT include this header yet and keeps its own text of the two kernels: built as wrappers around
-// the <false> bodies they came out with another scalar-register allocation and another grouping of the kernel-argument
-// loads than the kernels in the tree (same instruction count but for one load, same VGPR / SGPR / LDS figures), and
-// the kernels every training step runs are not to change in a commit that adds an option.  Until the two
-// texts are folded, tests/test_gpu_weighted_loss.py holds them together: w == 1 must give the bits of egs_gau_loss.
+// This header is the only text of that device code, and of the host side of a launch (window, grid, workspace): one
+// forward body and one gradient body with a `bool WEIGHTED` parameter, wrapped in __global__ kernels by the source file
+// that launches them.  Every weighted statement sits behind `if constexpr (WEIGHTED)`.
+//   <false> : k_ssim_fwd, k_ssim_bwd, k_loss_finalize of egs_loss.hip (libegs_hip.so: egs_gau_loss, every pixel counts
+//             once; the weighted arguments are nullptr / 0);
+//   <true>  : k_ssim_fwd_w, k_ssim_bwd_w, k_loss_finalize_w of egs_wloss.hip (libegs_wloss.so: egs_wloss, a weight per
+//             pixel).
+// Where a sum of two products leaves the compiler the choice of which one to fuse, the fused form is written out
+// (__builtin_fmaf), so that both instances round alike whatever is compiled around them: w == 1 gives the bits of
+// egs_gau_loss (tests/test_gpu_weighted_loss.py).
 //
 //   ssim_fwd_body : per 64x16 tile and channel: mu1, mu2, E[x^2], E[y^2], E[xy] -> SSIM map value,
 //                   per-tile partial sums of |x-y| and SSIM, and the three partial-derivative
@@ -42,7 +47,7 @@ static_assert(IH * HSEG <= 256 && TW * (TH / VRUN) == 256, "pass shapes are tied
 
 struct LossWin { float g[LW]; };          // normalised 1-D Gaussian, sigma = 1.5 (pytorch_ssim.py:11-13,17)
 
-// ---- host side of a launch: the window, the tile count, the persistent grid ----------------------------------------
+// ---- host side of a launch: the window, the tile count, the persistent grid, the workspace -------------------------
 static inline LossWin loss_window() {
   LossWin win;
   double sum = 0.0, g[LW];
@@ -60,6 +65,18 @@ static inline int loss_grid(int nb) {
     return 3 * cus;
   }();
   return nb < resident ? nb : resident;
+}
+// The workspace of a call, 256-B aligned pieces: the three derivative maps [3][H][W], the per-tile partials [nb][2] and,
+// for the weighted call, sum(w) of the channel-0 tiles [nb / 3].  `bytes` is what the *_ws_bytes entry points report (a
+// 256-B tail is part of it); ws == NULL asks for `bytes` alone.
+struct LossWs { float *Pm, *P11, *P12, *partials, *wparts; size_t bytes; };
+static inline LossWs loss_ws(void* ws, int H, int W, bool weighted) {
+  const size_t nb = (size_t)loss_blocks(H, W);
+  const size_t map = align_up((size_t)3 * H * W * 4, 256);
+  const size_t o_parts = 3 * map, o_w = o_parts + align_up(nb * 8, 256);
+  const size_t end = weighted ? o_w + align_up(nb / 3 * 4, 256) : o_w;
+  auto at = [ws](size_t o) { return ws ? (float*)((char*)ws + o) : nullptr; };
+  return {at(0), at(map), at(2 * map), at(o_parts), weighted ? at(o_w) : nullptr, end + 256};
 }
 
 #ifdef __HIPCC__
@@ -207,8 +224,8 @@ __device__ __forceinline__ void ssim_fwd_body(int H, int W, int gx, int gy, Loss
       const float s11 = e11 - mu1 * mu1, s22 = e22 - mu2 * mu2, s12 = e12 - mu1 * mu2;
       const float A1 = 2.f * mu1 * mu2 + C1, A2 = 2.f * s12 + C2;
       // Where a sum of two products leaves the compiler the choice of which one to fuse, the fused form is written out
-      // (fmaf): the one k_ssim_fwd of egs_loss.hip is built with, so that this body rounds as that kernel does whatever
-      // else is compiled around it (w == 1 gives the bits of egs_gau_loss).
+      // (fmaf), here and below, so that both instances round alike whatever else is compiled around them (w == 1 gives
+      // the bits of egs_gau_loss).
       const float B1 = __builtin_fmaf(mu1, mu1, mu2 * mu2) + C1, B2 = s11 + s22 + C2;
       // two v_rcp_f32 (1 ulp) instead of three IEEE divisions (~10 instructions each): B1, B2 >= C1, C2 > 0
       const float rB1 = __builtin_amdgcn_rcpf(B1), rB2 = __builtin_amdgcn_rcpf(B2);
@@ -438,7 +455,7 @@ __device__ __forceinline__ void ssim_bwd_body(int H, int W, int gx, int gy, Loss
       float sg = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);  // torch.abs' subgradient: sign(0) = 0
       // (w == 0: +0 whatever x - y is -- what lies outside the weighted region leaves no trace, not even a sign of zero)
       if constexpr (WEIGHTED) sg = pw[o] != 0.f ? pw[o] * sg : 0.f;
-      dimg[off] = __builtin_fmaf(c_l1, sg, c_ssim * dS);   // (the fused form k_ssim_bwd of egs_loss.hip is built with)
+      dimg[off] = __builtin_fmaf(c_l1, sg, c_ssim * dS);   // (written out: see ssim_fwd_body)
     }
   }
   __syncthreads();  // the next tile overwrites s / h

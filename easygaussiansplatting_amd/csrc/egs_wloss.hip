@@ -1,6 +1,6 @@
 // libegs_wloss.so (include/egs_wloss.h): the fused L1 / SSIM training loss with a weight per pixel.
-// The <true> instances of the two kernel bodies of egs_loss_device.h -- what egs_loss.hip launches with every pixel
-// counting once -- plus the reduction for a call without a gradient:
+// The <true> instances of the kernel bodies of egs_loss_device.h, which explains them (egs_loss.hip wraps the <false>
+// ones: every pixel counting once), plus the reduction for a call without a gradient:
 //
 //   k_ssim_fwd_w      : the forward maps times w, per-tile sums of w |x-y| and w S, and sum(w) of every channel-0 tile
 //   k_ssim_bwd_w      : every workgroup reduces the tile sums of w to sum(w) (fixed order, the same bits in each) and
@@ -55,9 +55,7 @@ extern "C" const char* egs_wloss_last_error_string(void) { return egs_side::g_er
 
 extern "C" size_t egs_wloss_ws_bytes(int H, int W) {
   if (H <= 0 || W <= 0 || (int64_t)H * W > EGS_WLOSS_MAX_PIXELS) return 256;
-  const int nb = loss_blocks(H, W);
-  return 3 * align_up((size_t)3 * H * W * 4, 256) + align_up((size_t)nb * 8, 256) + align_up((size_t)(nb / 3) * 4, 256) +
-         256;
+  return loss_ws(nullptr, H, W, true).bytes;
 }
 
 extern "C" int egs_wloss(int H, int W, const float* image, const float* gt, const float* weight, float lambda,
@@ -76,24 +74,18 @@ extern "C" int egs_wloss(int H, int W, const float* image, const float* gt, cons
     return EGS_ERR_WORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
-  Carver cv(ws, ws_bytes);
-  const size_t npix = (size_t)3 * H * W;
-  float* Pm = cv.take<float>(npix);
-  float* P11 = cv.take<float>(npix);
-  float* P12 = cv.take<float>(npix);
+  const LossWs m = loss_ws(ws, H, W, true);
   const int nb = loss_blocks(H, W), nw = nb / 3;
-  float* partials = cv.take<float>((size_t)nb * 2);
-  float* wparts = cv.take<float>((size_t)nw);
   const LossWin win = loss_window();
   const int gx = div_up(W, TW), gy = div_up(H, TH);
   const dim3 grid(loss_grid(nb));
-  hipLaunchKernelGGL(k_ssim_fwd_w, grid, dim3(256), 0, s, H, W, gx, gy, win, image, gt, weight, Pm, P11, P12, partials,
-                     wparts);
+  hipLaunchKernelGGL(k_ssim_fwd_w, grid, dim3(256), 0, s, H, W, gx, gy, win, image, gt, weight, m.Pm, m.P11, m.P12,
+                     m.partials, m.wparts);
   if (dloss_dimage)
-    hipLaunchKernelGGL(k_ssim_bwd_w, grid, dim3(256), 0, s, H, W, gx, gy, win, image, gt, weight, Pm, P11, P12,
-                       dloss_dimage, nb, partials, wparts, lambda, grad_scale, loss_out);
+    hipLaunchKernelGGL(k_ssim_bwd_w, grid, dim3(256), 0, s, H, W, gx, gy, win, image, gt, weight, m.Pm, m.P11, m.P12,
+                       dloss_dimage, nb, m.partials, m.wparts, lambda, grad_scale, loss_out);
   else
-    hipLaunchKernelGGL(k_loss_finalize_w, dim3(1), dim3(256), 0, s, nb, partials, nw, wparts, lambda, loss_out);
+    hipLaunchKernelGGL(k_loss_finalize_w, dim3(1), dim3(256), 0, s, nb, m.partials, nw, m.wparts, lambda, loss_out);
   SIDE_HIP(hipGetLastError());
   return 0;
 }

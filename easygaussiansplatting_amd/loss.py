@@ -2,7 +2,7 @@
 (gsplat/pytorch_ssim.py:63-66: 0.8 * L1 + 0.2 * (1 - SSIM), 11x11 Gaussian window).
 
 Same call, same value, same gradient; underneath two tiled HIP kernels
-(csrc/egs_loss.hip) that also produce dloss/dimage in the forward pass, so that
+(csrc/egs_loss_device.h, launched by csrc/egs_loss.hip) that also produce dloss/dimage in the forward pass, so that
 ``loss.backward()`` hands splatB its ``dloss_dgammas`` without running five
 depthwise conv2d backward passes (10.9 ms -> see DESIGN.md at 1920x1080).
 

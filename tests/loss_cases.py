@@ -1,4 +1,5 @@
-"""Image pairs, references and the comparison rule for the fused loss (csrc/egs_loss.hip: k_ssim_fwd / k_ssim_bwd).
+"""Image pairs, references and the comparison rule for the fused loss (k_ssim_fwd / k_ssim_bwd of csrc/egs_loss.hip, whose
+bodies are csrc/egs_loss_device.h's).
 
 The pairs.  ``make_pair(kind, H, W)`` -> (x, y), float32 [3,H,W], seeded from scene.normal / scene.uniform01:
 

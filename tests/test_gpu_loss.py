@@ -1,5 +1,5 @@
-"""The fused loss kernels (csrc/egs_loss.hip: k_ssim_fwd, k_ssim_bwd, k_loss_finalize) against float64, where float32 SSIM
-is hard and where the tile walk changes.
+"""The fused loss kernels (k_ssim_fwd, k_ssim_bwd, k_loss_finalize of csrc/egs_loss.hip: the unweighted instances of
+the kernel bodies of csrc/egs_loss_device.h) against float64, where float32 SSIM is hard and where the tile walk changes.
 
 Precision by regime: every pair kind of tests/loss_cases.py (noise is the only one the suite used to feed this kernel)
 at 70x150 and 1080x1920, under the rule stated there: the kernel may be as far from float64 as twice what the
@@ -11,7 +11,6 @@ XCD (G == nb), persistent workgroups (nb > 3 CUs); one-pixel and sub-window imag
 
 No buffer is ever smaller than the ABI asks for: the too-small workspace is an error code returned before any launch.
 """
-import ctypes as C
 import json
 import os
 
@@ -24,9 +23,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-GUARD = 256          # bytes on each side of a buffer the kernels write
-PATTERN = 0xA5
-EGS_ERR_WORKSPACE = 10002    # include/egs_hip.h
+from tests.loss_abi import EGS_ERR_WORKSPACE, abi_loss, bits, dev, nb_of  # noqa: E402  (the guarded C-ABI call; needs torch)
 
 
 @pytest.fixture(scope="module")
@@ -35,14 +32,6 @@ def lib():
         pytest.skip("no GPU")
     from easygaussiansplatting_amd import _lib
     return _lib.load()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def record(name, **figures):
@@ -97,40 +86,6 @@ def test_precision_by_regime(lib, kind, size):
 
 
 # --------------------------------------------------------------------------- every tile walk, every edge (C ABI)
-def guarded(nbytes):
-    """A buffer of ``nbytes`` between two guard bands.  -> (whole uint8 tensor, the inner bytes as a view)."""
-    whole = torch.full((nbytes + 2 * GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-    return whole, whole[GUARD:GUARD + nbytes]
-
-
-def guards_intact(whole):
-    return bool((whole[:GUARD] == PATTERN).all()) and bool((whole[-GUARD:] == PATTERN).all())
-
-
-def abi_loss(lib, x, y, lam=0.2, scale=1.0, ws_short=0):
-    """egs_gau_loss on buffers this test owns: workspace, gradient and stats NaN-filled between guard bands.
-    -> (rc, grad [3,H,W], stats [3]); asserts the guards."""
-    H, W = int(x.shape[1]), int(x.shape[2])
-    ws_bytes = int(lib.egs_gau_loss_ws_bytes(H, W))
-    assert ws_bytes % 4 == 0 and ws_bytes >= 3 * 12 * H * W + 8 * nb_of(H, W)
-    ws_all, ws = guarded(ws_bytes)
-    g_all, g = guarded(12 * H * W)
-    s_all, s = guarded(12)
-    for inner in (ws, g, s):
-        inner.view(torch.float32).fill_(float("nan"))
-    p = lambda t: C.c_void_p(t.data_ptr())
-    rc = lib.egs_gau_loss(H, W, p(x), p(y), float(lam), float(scale), p(ws), ws_bytes - ws_short, p(s), p(g),
-                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    for whole, nm in ((ws_all, "workspace"), (g_all, "dloss_dimage"), (s_all, "loss_out")):
-        assert guards_intact(whole), "%dx%d: the kernels wrote outside %s" % (H, W, nm)
-    return rc, g.view(torch.float32).reshape(3, H, W).clone(), s.view(torch.float32).clone()
-
-
-def nb_of(H, W):
-    return ((W + 63) // 64) * ((H + 15) // 16) * 3
-
-
 def check_shape(lib, H, W, tag=""):
     what = "%s%dx%d (nb %d)" % (tag, H, W, nb_of(H, W))
     xn, yn = LC.make_pair("noise", H, W)

@@ -9,8 +9,9 @@ for: the too-small workspace is an error code returned before any launch.
 Shapes, by nb = ceil(W/64) ceil(H/16) 3: 1x1, 5x200, 11x11 (below the window), 17x65 (nb 12: the strided walk, every
 tile-edge remainder), 33x129 (nb 27: one band per XCD), 272x1024 (nb 816 > 3 x 256 CUs: persistent workgroups).
 
-w == 1 against egs_gau_loss: bit-identical stats[0:3] and gradient, stats[3] == H W.  Every added operation is a
-multiplication by 1.0, the per-tile sum(w) <= 1024 is exact in float32 and the sum of the tile sums is exact in double.
+w == 1 against egs_gau_loss (the guarded call of tests/loss_abi.py): bit-identical stats[0:3] and gradient, stats[3] ==
+H W.  Both libraries instantiate the kernel bodies of csrc/egs_loss_device.h, so this pins that everything WEIGHTED adds is
+a multiplication by 1.0: the per-tile sum(w) <= 1024 is exact in float32 and the sum of the tile sums is exact in double.
 """
 import ctypes as C
 import functools
@@ -25,9 +26,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-GUARD = 256          # bytes on each side of a buffer the kernels write
-PATTERN = 0xA5
-EGS_ERR_WORKSPACE = 10002    # include/egs_hip.h
+from tests.loss_abi import EGS_ERR_WORKSPACE, abi_loss, bits, dev, guarded, guards_intact, nb_of  # noqa: E402  (needs torch)
+
 SHAPES = [(1, 1), (5, 200), (11, 11), (17, 65), (33, 129), (272, 1024)]
 sid = lambda s: "%dx%d" % s
 
@@ -46,28 +46,6 @@ def hiplib():
         pytest.skip("no GPU")
     from easygaussiansplatting_amd import _lib
     return _lib.load()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def nb_of(H, W):
-    return ((W + 63) // 64) * ((H + 15) // 16) * 3
-
-
-def guarded(nbytes):
-    """A buffer of ``nbytes`` between two guard bands.  -> (whole uint8 tensor, the inner bytes as a view)."""
-    whole = torch.full((nbytes + 2 * GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-    return whole, whole[GUARD:GUARD + nbytes]
-
-
-def guards_intact(whole):
-    return bool((whole[:GUARD] == PATTERN).all()) and bool((whole[-GUARD:] == PATTERN).all())
 
 
 def abi_wloss(lib, x, y, w, lam=0.2, scale=1.0, ws_short=0, need_grad=True, stream=None):
@@ -97,21 +75,6 @@ def abi_wloss(lib, x, y, w, lam=0.2, scale=1.0, ws_short=0, need_grad=True, stre
         assert bool(torch.isnan(grad).all()), "a gradient was written though none was asked for"
         grad = None
     return rc, grad, s.view(torch.float32).clone()
-
-
-def abi_unweighted(hiplib, x, y, lam=0.2, scale=1.0):
-    """egs_gau_loss of libegs_hip.so on the same pair -> (grad, stats[3])"""
-    H, W = int(x.shape[1]), int(x.shape[2])
-    ws_bytes = int(hiplib.egs_gau_loss_ws_bytes(H, W))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
-    g = torch.full((3, H, W), float("nan"), device="cuda")
-    s = torch.full((3,), float("nan"), device="cuda")
-    p = lambda t: C.c_void_p(t.data_ptr())
-    rc = hiplib.egs_gau_loss(H, W, p(x), p(y), float(lam), float(scale), p(ws), ws_bytes, p(s), p(g),
-                             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    assert rc == 0
-    return g, s
 
 
 @functools.lru_cache(maxsize=4)
@@ -196,7 +159,8 @@ def test_unit_weights_give_the_bits_of_the_unweighted_kernels(lib, hiplib, shape
     for lam, scale in ((0.2, 1.0), (1.0, 1.0 / 3.0), (0.0, 0.25)):
         rc, grad, stats = abi_wloss(lib, x, y, ones, lam, scale)
         assert rc == 0
-        grad0, stats0 = abi_unweighted(hiplib, x, y, lam, scale)
+        rc0, grad0, stats0 = abi_loss(hiplib, x, y, lam, scale)      # (guard bands of the unweighted call included)
+        assert rc0 == 0
         what = "%s %dx%d lambda %.1f scale %.3f" % (kind, H, W, lam, scale)
         assert float(stats[3]) == H * W, what
         assert torch.equal(bits(stats[:3]), bits(stats0)), (what, stats.tolist(), stats0.tolist())

@@ -168,7 +168,7 @@ def test_bad_arguments_and_a_short_workspace_are_refused_without_a_device(lib):
 
 
 def test_source_reads_no_environment_variable():
-    for name in ("egs_wloss.hip", "egs_loss_device.h"):
+    for name in ("egs_wloss.hip", "egs_loss.hip", "egs_loss_device.h"):
         assert "getenv" not in open(os.path.join(REPO, "easygaussiansplatting_amd", "csrc", name)).read()
 
 

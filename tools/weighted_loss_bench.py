@@ -3,6 +3,10 @@
 
     python tools/weighted_loss_bench.py [--height 1080 --width 1920] [--reps 20] [--rounds 9]
                                         [--parent-lib PATH/libegs_hip.so] [--out profiles/weighted_loss_bench.json]
+                                        [--append]
+
+``--append`` adds this process's run to the ``runs`` the output file already holds: a comparison against the parent
+commit's library takes several processes, and the spread of ``gau_loss/parent`` between them is its noise floor.
 
 Variants, all on one image pair (noise, as tests/loss_cases.py makes it) with the C entry points called directly on
 preallocated buffers, loss and gradient (lambda 0.2):
@@ -45,6 +49,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--parent-lib", default=None, help="libegs_hip.so of the parent commit")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "weighted_loss_bench.json"))
+    ap.add_argument("--append", action="store_true", help="add this process's run to the runs --out already holds")
     a = ap.parse_args()
 
     import torch
@@ -91,12 +96,16 @@ def main():
     base = res["gau_loss"]["median_us"]
     for k, r in res.items():
         r["over_gau_loss"] = round(r["median_us"] / base, 4)
-    out = {"what": "fused L1/SSIM loss + gradient, lambda 0.2: egs_wloss (libegs_wloss.so) against egs_gau_loss "
-                   "(libegs_hip.so, this commit's and the parent's) and the torch mask workaround; us per call, median / "
-                   "min / max over the rounds of HIP-event brackets",
-           "height": H, "width": W, "reps_per_bracket": a.reps, "rounds": a.rounds, "warmup_calls": a.warmup,
+    run = {"height": H, "width": W, "reps_per_bracket": a.reps, "rounds": a.rounds, "warmup_calls": a.warmup,
            "device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"),
            "parent_lib": bool(a.parent_lib), "results": res}
+    out = {"what": "fused L1/SSIM loss + gradient, lambda 0.2: egs_wloss (libegs_wloss.so) against egs_gau_loss "
+                   "(libegs_hip.so, this commit's and the parent's) and the torch mask workaround; us per call, median / "
+                   "min / max over the rounds of HIP-event brackets; one entry of `runs` per process",
+           "runs": [run]}
+    if a.append and os.path.exists(a.out):
+        with open(a.out) as f:
+            out["runs"] = json.load(f)["runs"] + [run]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
