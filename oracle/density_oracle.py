@@ -75,42 +75,57 @@ def classify(alphas_raw, scales_raw, grad_accum, cunt, th):
     return remain, idx[remain & by_grad & by_scale], idx[remain & by_grad & ~by_scale]
 
 
-def rotate_vector_by_quaternion(q, v):
+def rotate_vector_by_quaternion(q, v, dtype=np.float32):
     """utils.py:46-54 (q = (w, x, y, z), normalised inside)."""
-    q = q.astype(F)
-    q = q / np.maximum(np.linalg.norm(q, axis=1, keepdims=True), F(1e-12))
+    T = dtype
+    q = q.astype(T)
+    q = q / np.maximum(np.linalg.norm(q, axis=1, keepdims=True), T(1e-12))
     u, s = q[:, 1:], q[:, :1]
-    v = v.astype(F)
-    return (F(2) * u * (u * v).sum(1, keepdims=True) + v * (s * s - (u * u).sum(1, keepdims=True))
-            + F(2) * s * np.cross(u, v)).astype(F)
+    v = v.astype(T)
+    return (T(2) * u * (u * v).sum(1, keepdims=True) + v * (s * s - (u * u).sum(1, keepdims=True))
+            + T(2) * s * np.cross(u, v)).astype(T)
 
 
-def densify(params, m, v, grad_accum, cunt, unit_noise, th):
+def appended(params, unit_noise, sel, is_split, dtype=np.float32):
+    """the rows that the parents ``sel`` (ORIGINAL indices) append, gsmodel.py:257-288: clones as they are, split
+    children at ``pw + R(q) . (scale * unit_noise)`` with 0.6 x scale; activated, changed and taken back to raw in
+    ``dtype``.  -> dict name -> [len(sel), w]; the SH rows are the parents' stored rows."""
+    T = dtype
+    sig = lambda x: (T(1) / (T(1) + np.exp(-x.astype(T)))).astype(T)
+    norm = lambda q: (q.astype(T) / np.maximum(np.linalg.norm(q.astype(T), axis=1, keepdims=True), T(1e-12))).astype(T)
+    pws = params["pws"][sel].astype(T)
+    alphas = sig(params["alphas_raw"][sel])
+    scales = np.exp(params["scales_raw"][sel].astype(T)).astype(T)
+    rots = norm(params["rots_raw"][sel])
+    if is_split:
+        pws = pws + rotate_vector_by_quaternion(rots, scales * unit_noise[sel].astype(T), T)
+        scales = scales * T(F(0.6))             # the reference multiplies a float32 tensor: the constant is float32's
+    with np.errstate(divide="ignore"):          # sigmoid rounds to 1 for alphas_raw >~ 17 in float32: +inf, as in torch
+        alphas_raw = np.log(alphas / (T(1) - alphas)).astype(T)
+    return {"pws": pws.astype(T), "low_shs": params["low_shs"][sel], "high_shs": params["high_shs"][sel],
+            "alphas_raw": alphas_raw, "scales_raw": np.log(scales).astype(T), "rots_raw": rots}
+
+
+def densify(params, m, v, grad_accum, cunt, unit_noise, th, dtype=np.float32):
     """gsmodel.py:232-317.  ``params``/``m``/``v``: dicts name -> [N, w] float32 (Adam moments may be
     None = optimizer has not stepped yet).  ``unit_noise`` [N,3]: unit normals indexed by ORIGINAL
     Gaussian index (the reference draws torch.normal(0, scale) = scale * unit).  Returns
-    (params', m', v', info)."""
+    (params', m', v', info).
+
+    ``dtype``: the number format in which the APPENDED rows of pws / alphas_raw / scales_raw / rots_raw are
+    evaluated and in which all six tensors are returned (np.float64: the reference of the row-by-row GPU tests).
+    The classification stays in float32 on the stored values, whatever ``dtype``: it is the decision rule.  Moved
+    rows, copied SH rows and the moments are the stored float32 values in either mode."""
+    T = dtype
     remain, clone, split = classify(params["alphas_raw"], params["scales_raw"], grad_accum, cunt, th)
-    sig = lambda x: (F(1) / (F(1) + np.exp(-x.astype(F)))).astype(F)
-    norm = lambda q: (q / np.maximum(np.linalg.norm(q.astype(F), axis=1, keepdims=True), F(1e-12))).astype(F)
     new = {}
     for name in NAMES:
         new[name] = [params[name][remain]]
     for sel, is_split in ((clone, False), (split, True)):
-        pws = params["pws"][sel].astype(F)
-        alphas = sig(params["alphas_raw"][sel])
-        scales = np.exp(params["scales_raw"][sel].astype(F)).astype(F)
-        rots = norm(params["rots_raw"][sel])
-        if is_split:
-            pws = pws + rotate_vector_by_quaternion(rots, scales * unit_noise[sel].astype(F))
-            scales = scales * F(0.6)
-        new["pws"].append(pws.astype(F))
-        new["low_shs"].append(params["low_shs"][sel])
-        new["high_shs"].append(params["high_shs"][sel])
-        new["alphas_raw"].append(np.log(alphas / (F(1) - alphas)).astype(F))
-        new["scales_raw"].append(np.log(scales).astype(F))
-        new["rots_raw"].append(rots)
-    out = {k: np.concatenate(vv, axis=0).astype(F) for k, vv in new.items()}
+        rows = appended(params, unit_noise, sel, is_split, T)
+        for name in NAMES:
+            new[name].append(rows[name])
+    out = {k: np.concatenate(vv, axis=0).astype(T) for k, vv in new.items()}
     n_new = len(clone) + len(split)
 
     def surg(st):
