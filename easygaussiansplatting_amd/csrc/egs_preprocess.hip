@@ -518,21 +518,24 @@ __device__ __forceinline__ void stage_span_out(const float* row, float* __restri
     dst[(size_t)K * base + f] = lds[f] + (accum ? dst[(size_t)K * base + f] : 0.f);
 }
 
-// Occupancy: 20 KB of LDS per workgroup = exactly 8 workgroups per CU (8 waves per SIMD, which needs <= 64 VGPRs).
-// With 7 -- one VGPR or 16 bytes of LDS too many -- the 3906 workgroups of 1 M Gaussians run as 2.2 "rounds" of
-// 1792, i.e. the launch ends with a third round that is 20 % full.
 // forward.md steps 1-5 for one Gaussian in one pass (== gsmodel.py:21-35 minus splat):
 // writes exactly what splat / splatB / the backward pass consume.
 // RAW: rots/scales/alphas are the un-activated tensors, shs = low_shs [N,3], shs_high = high_shs [N,K-3]
-// JW: also write dcolor/dpw (dcolor_dpws) for the backward pass -- a training render; the SH Jacobian keeps ~40 more
-// registers alive, so these instances are not pinned to 8 waves per SIMD
-// (Tried: rotation / scale / opacity requested together with the position, which makes the unpinned JW instance hoist
-// all twelve SH loads -- 101 VGPRs, one round trip per row instead of six -- and measures equal within noise,
-// 0.860-0.868 ms per step either way: the kernel is bound by the memory system's queues; docs/LAB.md.)
-constexpr int PRE_JW_WAVES = 1;   // minimum waves per SIMD of the JW instances (register cap 512 / waves)
+// JW: also write dcolor/dpw (dcolor_dpws) for the backward pass -- a training render
+// Order inside a wave: the four small loads, the whole SH row, then everything that needs no SH coefficient (basis,
+// projection, cull, covariances, radius, binning and footprint records, the stores that are final) under the row's
+// flight, then colour and dcolor/dpw.  The first wait of the geometry is a counted one (vmcnt(14) .. (12) at SH degree
+// 3: the twelve row loads stay outstanding).  The row's 3 NC destination registers are live over the geometry: 101
+// VGPRs / 4 waves per SIMD with JW at degree 3, 95 / 5 without -- so no instance is pinned to 8 waves any more (at 64
+// VGPRs the degree-2 and degree-3 rows spill).  Measured 101 -> 90 us at 1 M Gaussians, the forward-only render
+// 0.353 -> 0.344 ms; docs/LAB.md, DESIGN 3.1, profiles/pre_wave_order_ab.txt.
+// (Loads alone do not do it: rotation / scale / opacity requested with the position and all twelve SH loads hoisted,
+// but the SH block still FIRST, measured equal to the six dependent round trips before it, 0.860-0.868 ms per step
+// either way -- what matters is which arithmetic runs while the row is in flight.)
+constexpr int PRE_FWD_WAVES = 1;   // minimum waves per SIMD of every instance (register cap 512 / waves)
 // AA (anti-aliased rendering): every Gaussian is binned and drawn with opacity alpha comp
 template <int NC, bool RAW, bool JW, bool AA>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (JW ? PRE_JW_WAVES : 8), 8))) void k_preprocess_fwd(int n, PreParams pp, const float* __restrict__ pws,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRE_FWD_WAVES, 8))) void k_preprocess_fwd(int n, PreParams pp, const float* __restrict__ pws,
                                                         const float* __restrict__ rots,
                                                         const float* __restrict__ scales,
                                                         const float* __restrict__ shs,
@@ -571,27 +574,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
   float jw[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   uint4 crec = make_uint4(0u, 0u, 0u, 0u);
   if (i < n) {
+    // Every input of the row is requested here, the four small ones first and the SH row behind them: the memory
+    // counter is in order, so the geometry below waits for the small loads only and runs while the row is in flight.
+    // (The near-cull decides what is used, not what is loaded: the addresses are valid for every i < n.)
     const f3 pw = ld3(pws + 3 * (size_t)i);
-    float col[3];
-    {  // colour has no depth test in the reference (kernel.cu:619-725)
-      if constexpr (RAW) {
-        sh[0] = shs[3 * (size_t)i]; sh[1] = shs[3 * (size_t)i + 1]; sh[2] = shs[3 * (size_t)i + 2];
-      } else {  // direct dwordx4 row loads: staging them through LDS measured 10 % slower here
-        load_sh_row<K>(shs + (size_t)K * i, sh);
-      }
-      const ShDir<NC> d = sh_basis_f<NC>(pw, twc);
-      sh_color_f<NC>(d, sh, col);
-      if (colors) st3(colors + 3 * (size_t)i, {col[0], col[1], col[2]});
-      if constexpr (JW) sh_jac_dpw<NC>(d, sh, jw);
+    float4 q = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
+    f3 sc = ld3(scales + 3 * (size_t)i);
+    const float alpha_in = (rec || bo.br) ? alphas[i] : 0.f;
+    if constexpr (RAW) {
+      sh[0] = shs[3 * (size_t)i]; sh[1] = shs[3 * (size_t)i + 1]; sh[2] = shs[3 * (size_t)i + 2];
+    } else {  // direct dwordx4 row loads: staging them through LDS measured 10 % slower here
+      load_sh_row<K>(shs + (size_t)K * i, sh);
     }
+    __builtin_amdgcn_sched_barrier(0);   // (no load sinks below this line, no arithmetic rises above it)
+    // ---- everything that needs no SH coefficient
+    const ShDir<NC> d = sh_basis_f<NC>(pw, twc);
     const Proj P = project_f(pw, Rcw, tcw, pp.fx, pp.fy, pp.cx, pp.cy);
     float u0 = 0.f, u1 = 0.f, depth = EGS_BAD_MARKER, ci[3] = {0.f, 0.f, 0.f};
     int rx = 0, ry = 0;
     float aa_comp = 0.f;   // (AA: the opacity compensation; 0 for near-culled Gaussians)
     if (!(pp.near_cull && P.pc.z < EGS_MIN_DEPTH)) {
       u0 = P.u0; u1 = P.u1; depth = P.pc.z;
-      float4 q = *reinterpret_cast<const float4*>(rots + 4 * (size_t)i);
-      f3 sc = ld3(scales + 3 * (size_t)i);
       if constexpr (RAW) { float nrm; q = act_rot(q, nrm); sc = act_scale(sc); }
       const Cov3 c3 = cov3d_f(q, sc);
       const Cov2 c2 = cov2d_f(c3.c, P.pc, Rcw, pp.fx, pp.fy, pp.limx, pp.limy, pp.clamp_fov);
@@ -603,7 +606,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
         radius_f(c2.c, pp.radius_mode, rx, ry);
       }
     }
-    float alpha_act = (rec || bo.br) ? (RAW ? act_alpha(alphas[i]) : alphas[i]) : 0.f;
+    float alpha_act = (rec || bo.br) ? (RAW ? act_alpha(alpha_in) : alpha_in) : 0.f;
     // AA: the Gaussian is binned and drawn with the compensated opacity alpha comp (the records carry it)
     if constexpr (AA) alpha_act *= aa_comp;
     if (bo.br) {  // getRects + depth key of the binning stage, straight from registers (no k_bin_count pass)
@@ -645,10 +648,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RAW ? 1 : (
     if (visible) visible[i] = depth > 0.2f;  // the mask GSFunction returns (gsmodel.py:50)
     if (cinv2ds) st3(cinv2ds + 3 * (size_t)i, {ci[0], ci[1], ci[2]});
     if (areas) { areas[2 * (size_t)i] = rx; areas[2 * (size_t)i + 1] = ry; }
-    // the packed 2D record of the draw kernels, straight from registers (no k_pack_records pass)
+    // the packed 2D record of the draw kernels, straight from registers (no k_pack_records pass): its geometry fields
     if (rec)
-      make_record(u0, u1, ci[0], ci[1], ci[2], alpha_act, col[0], col[1], col[2], rx, ry,
+      make_record(u0, u1, ci[0], ci[1], ci[2], alpha_act, 0.f, 0.f, 0.f, rx, ry,
                   pp.W, pp.H, pp.footprint, pp.alpha_skip, r);
+    // ---- the SH row is waited for here.  Colour has no depth test in the reference (kernel.cu:619-725)
+    float col[3];
+    sh_color_f<NC>(d, sh, col);
+    if (colors) st3(colors + 3 * (size_t)i, {col[0], col[1], col[2]});
+    if constexpr (JW) sh_jac_dpw<NC>(d, sh, jw);
+    if (rec) { r[1].z = col[0]; r[1].w = col[1]; r[2].x = col[2]; }
   }
   if (bo.br) {
     __syncthreads();   // (RAW: every wave is done with the rows staged in)
@@ -713,6 +722,9 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
       else if (i < n) load_sh_row<K>(shs + (size_t)K * i, sh);
     }
   }
+  // (Tried: the gsh rows formed and staged out right after the loads, the Jacobians and cov3d_vjp behind them, so that
+  // the rows' 192 B per Gaussian drain under the arithmetic -- 63 -> 66 us: the stage's barriers then stand between
+  // the loads and ALL of the arithmetic, and stores issued last never held a wave anyway; docs/LAB.md.)
   if constexpr (!POSE_ONLY) {
 #pragma unroll
     for (int k = 0; k < K; ++k) gsh[k] = 0.f;
