@@ -12,9 +12,19 @@ CHW / 255).
 ``path/masks/<image file name>.png`` (COLMAP's convention: ``images/a.jpg`` -> ``masks/a.jpg.png``, 0 = ignore),
 ``path/masks/<stem>.png``, the image's own alpha channel.  The mask is read as 8-bit grey, resized with the image and
 scaled by 1/255.
+
+``GSplatDataset(path, depths=True)`` also collects a depth prior per image (``.depth_priors[i]``: float32 [H,W]
+DISPARITY -- inverse depth, 0 = no data -- on the device, or None) and ``.depth_kind``, for
+``Trainer(depth_priors=ds.depth_priors, depth_kind=ds.depth_kind)``.  Looked for in this order:
+``path/depths/<stem>.npy`` (float32 disparity), ``path/depths/<stem>.png`` (16-bit grey, value / 65536: the convention of
+the official code's monocular depth maps).  A prior is resized with the image by NEAREST sampling, so that a no-data
+pixel never bleeds into its neighbours.  With ``path/sparse/0/depth_params.json`` (the official
+``{image stem: {"scale": s, "offset": o}}``) every prior becomes s q + o where it has data and ``depth_kind`` is
+"metric"; otherwise ``depth_kind`` is "affine" (scale and shift are fitted during training).
 """
 from __future__ import annotations
 
+import json
 import os
 
 import numpy as np
@@ -48,8 +58,37 @@ def _weight_source(path, name, image):
     return None
 
 
+def _nearest(a, width, height):
+    """``a`` [h,w] sampled to [height,width] at the nearest source pixel (pixel centres; no value is blended)"""
+    h, w = a.shape
+    if (h, w) == (height, width):
+        return a
+    rows = np.minimum(((np.arange(height) + 0.5) * h / height).astype(np.int64), h - 1)
+    cols = np.minimum(((np.arange(width) + 0.5) * w / width).astype(np.int64), w - 1)
+    return a[rows[:, None], cols[None, :]]
+
+
+def _depth_source(path, name):
+    """The image's depth prior as a float32 [h,w] disparity array, or None: depths/<stem>.npy, depths/<stem>.png."""
+    stem = os.path.splitext(name)[0]
+    fn = os.path.join(path, "depths", stem + ".npy")
+    if os.path.exists(fn):
+        a = np.load(fn)
+        if a.ndim != 2:
+            raise ValueError("%s: expected a [H,W] disparity array, got shape %s" % (fn, list(a.shape)))
+        return a.astype(np.float32)
+    fn = os.path.join(path, "depths", stem + ".png")
+    if os.path.exists(fn):
+        from PIL import Image
+        im = Image.open(fn)
+        if im.mode not in ("I;16", "I;16B", "I;16L", "I"):
+            raise ValueError("%s: expected a 16-bit grey image, got mode %s" % (fn, im.mode))
+        return (np.asarray(im).astype(np.float64) / 65536.0).astype(np.float32)
+    return None
+
+
 class GSplatDataset(torch.utils.data.Dataset):
-    def __init__(self, path, resize_rate=1, device="cuda", masks=False) -> None:
+    def __init__(self, path, resize_rate=1, device="cuda", masks=False, depths=False) -> None:
         super().__init__()
         from PIL import Image
         self.device = device
@@ -58,6 +97,15 @@ class GSplatDataset(torch.utils.data.Dataset):
         camera_params, image_params = colmap.read_model(sparse, ext=".bin")
         self.cameras, self.images = [], []
         self.weights = [] if masks else None
+        self.depth_priors = [] if depths else None
+        self.depth_kind = None
+        depth_params = None
+        if depths:
+            fn = os.path.join(sparse, "depth_params.json")
+            if os.path.exists(fn):
+                with open(fn) as f:
+                    depth_params = json.load(f)
+            self.depth_kind = "metric" if depth_params is not None else "affine"
         for ip in image_params.values():
             cp = camera_params[ip.camera_id]
             im_path = os.path.join(path, "images", ip.name)
@@ -85,6 +133,19 @@ class GSplatDataset(torch.utils.data.Dataset):
             if masks:
                 self.weights.append(None if mask is None else torch.from_numpy(np.array(mask, dtype=np.uint8)).to(device)
                                     .to(torch.float32).div_(255.0).contiguous())
+            if depths:
+                q = _depth_source(path, ip.name)
+                if q is not None:
+                    q = _nearest(q, image.width, image.height)
+                    if depth_params is not None:
+                        dp = depth_params.get(os.path.splitext(ip.name)[0])
+                        if dp is None:      # (no alignment for this image: it cannot be used as a metric prior)
+                            q = None
+                        else:
+                            q = np.where(q > 0, np.float32(dp["scale"]) * q + np.float32(dp["offset"]),
+                                         np.float32(0)).astype(np.float32)
+                self.depth_priors.append(None if q is None else
+                                         torch.from_numpy(np.ascontiguousarray(q, np.float32)).to(device))
         cache = os.path.join(sparse, "points3D.npy")
         if os.path.exists(cache):
             self.gs = np.load(cache)

@@ -23,6 +23,7 @@ What is new (the reference renders one view per optimizer step on one GPU)
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import math
 from typing import Dict, List, Sequence
 
@@ -110,6 +111,48 @@ def _checked_pixel_weights(pixel_weights, gt_images, device):
     return out
 
 
+def _checked_depth_priors(depth_priors, gt_images, device):
+    """``Trainer(depth_priors=...)``, checked once (host synchronisations are fine here) -> None, or a list with one
+    float32 [H,W] disparity plane on ``device`` or None per view.  ValueError names the view."""
+    if depth_priors is None:
+        return None
+    priors, gts = list(depth_priors), list(gt_images)
+    if len(priors) != len(gts):
+        raise ValueError("Trainer(depth_priors=...): %d entries for %d views (one per camera; None for a view without "
+                         "a prior)" % (len(priors), len(gts)))
+    out = []
+    for v, (q, gt) in enumerate(zip(priors, gts)):
+        if q is None:
+            out.append(None)
+            continue
+        what = "Trainer(depth_priors=...): view %d" % v
+        if not isinstance(q, torch.Tensor) or q.dtype != torch.float32:
+            raise ValueError("%s must be a float32 tensor (disparity; 0 = no data), got %s"
+                             % (what, q.dtype if isinstance(q, torch.Tensor) else type(q).__name__))
+        if tuple(q.shape) != tuple(gt.shape[-2:]):
+            raise ValueError("%s has shape %s, its ground-truth image is %s"
+                             % (what, list(q.shape), list(gt.shape[-2:])))
+        q = q.to(device=device).contiguous()
+        if not bool(((q > 0) & torch.isfinite(q)).any()):
+            raise ValueError("%s has no positive finite pixel: the view would have no depth term (pass None instead)"
+                             % what)
+        out.append(q)
+    return out
+
+
+def _checked_depth_weight(depth_weight):
+    """-> (init, final) of the depth term's weight; a single float is constant"""
+    try:
+        pair = (float(depth_weight),) * 2 if isinstance(depth_weight, (int, float)) else \
+            tuple(float(x) for x in depth_weight)
+    except (TypeError, ValueError):
+        pair = ()
+    if len(pair) != 2 or not all(math.isfinite(x) and x >= 0 for x in pair) or \
+            (pair[0] != pair[1] and min(pair) <= 0):
+        raise ValueError("Trainer(depth_weight=%r): expected a float >= 0 or (init, final), both > 0" % (depth_weight,))
+    return pair
+
+
 class Trainer:
     def __init__(self, scene, cameras: Sequence, gt_images: Sequence[torch.Tensor], max_steps: int,
                  scene_size: float = 1.0, device="cuda", fused_adam: bool = True, seed: int = 0,
@@ -118,7 +161,8 @@ class Trainer:
                  pose_opt: bool = False, pose_lr=(_pose.LR_ROT, _pose.LR_TRANS), strategy: str = "default",
                  cap_max: int = None, mcmc_options: dict = None, sparse_adam: bool = False,
                  bilagrid: bool = False, bilagrid_shape=_appearance.DEFAULT_SHAPE, bilagrid_lr: float = 2e-3,
-                 bilagrid_tv: float = 10.0, pixel_weights: Sequence = None):
+                 bilagrid_tv: float = 10.0, pixel_weights: Sequence = None, depth_priors: Sequence = None,
+                 depth_kind: str = "affine", depth_weight=(1.0, 0.01), depth_alpha_min: float = 0.05):
         """``strategy``: how Gaussians are added and removed.  "default" is the reference's clone / split / prune /
         alpha reset (``density.DensityControl``).  "mcmc" (needs ``cap_max``, the hard limit on the number
         of Gaussians) is ``density.MCMCControl``: every step adds the opacity / scale regularisers' gradient before the
@@ -162,9 +206,45 @@ class Trainer:
         the step's mean as an unmasked one.  A pixel with w = 0 still receives SSIM gradient from weighted pixels up to
         5 px away; for a hard exclusion dilate the mask by 5 px.  With ``bilagrid`` the weighted loss is taken on the
         corrected image.  ``step`` returns the mean of the (weighted) losses.  With ``pixel_weights=None`` nothing in a
-        step differs: no extra tensor, no extra launch, libegs_wloss.so is not loaded."""
+        step differs: no extra tensor, no extra launch, libegs_wloss.so is not loaded.
+
+        ``depth_priors``: depth supervision (fused path only).  A sequence with one entry per camera: a
+        float32 tensor [H,W] of the view's ground-truth size holding the prior DISPARITY (inverse depth; 0, negative or
+        non-finite: no data), or None for a view without a prior (it renders exactly as without the option).  Checked
+        once, here (shape, dtype, at least one positive finite pixel: ``ValueError`` naming the view).  A view with a
+        prior also renders its depth and opacity maps, ``depthloss.depth_loss_with_grad`` (``depth_kind``: "metric",
+        "affine" -- scale and shift fitted per view and step, on the device -- or "pearson") turns them into
+        dL/ddepth and dL/dalpha, and ONE backward pass takes these and dL/dimage.  The term enters the step with the
+        weight init (final / init)^(iteration / max_steps) for ``depth_weight`` = (init, final) -- (1.0, 0.01) are the
+        official code's values, NOT tuned here -- or a constant for a single float; ``pixel_weights[v]`` weights its
+        pixels too.  ``depth_alpha_min`` = 0.05 (pixels with less opacity do not count) guards the 1 / depth^2 factor
+        of the gradient; nobody has tuned it.  ``step`` still returns the image loss; the mean unweighted depth term of
+        the step's views that have a prior is kept as ``last_depth_loss`` (a device tensor).  Not with ``absgrad`` (the
+        draw kernel has no instance for absolute gradients and render extras) nor with ``mode`` other than "fused".
+        A render with the maps takes the unsplit draw kernels.  With ``depth_priors=None`` nothing in a step differs: no
+        extra tensor, no extra launch, libegs_depthloss.so is not loaded."""
         self.device = device
         self.pixel_weights = _checked_pixel_weights(pixel_weights, gt_images, device)
+        self.depth_priors = _checked_depth_priors(depth_priors, gt_images, device)
+        self.last_depth_loss = None
+        self._depth_sum = None
+        if self.depth_priors is not None:
+            from . import depthloss as _depthloss
+            if depth_kind not in _depthloss.KINDS:
+                raise ValueError("Trainer(depth_kind=%r): expected one of %s" % (depth_kind, list(_depthloss.KINDS)))
+            if absgrad:
+                raise ValueError("Trainer(depth_priors=...) with absgrad=True: a view with a prior renders its depth and "
+                                 "opacity maps, and the draw kernel has no instance for absolute gradients and render "
+                                 "extras")
+            if mode != "fused":
+                raise ValueError("Trainer(depth_priors=...) needs mode='fused' (the depth and opacity maps are the "
+                                 "fused path's), got %r" % (mode,))
+            self.depth_kind = depth_kind
+            self.depth_weight = _checked_depth_weight(depth_weight)
+            self.depth_alpha_min = float(depth_alpha_min)
+            if not 0.0 <= self.depth_alpha_min < float("inf"):
+                raise ValueError("Trainer(depth_alpha_min=%r): expected a finite value >= 0" % (depth_alpha_min,))
+            self._depth_loss_with_grad = _depthloss.depth_loss_with_grad
         if strategy not in ("default", "mcmc"):
             raise ValueError("Trainer(strategy=%r): expected 'default' or 'mcmc'" % (strategy,))
         if strategy == "mcmc" and cap_max is None:
@@ -241,6 +321,14 @@ class Trainer:
 
     _KEYS = ("pws", "low_shs", "high_shs", "alphas_raw", "scales_raw", "rots_raw")
 
+    def depth_weight_at(self, iteration: int) -> float:
+        """The weight of the depth term at optimizer step ``iteration``: init (final / init)^(iteration / max_steps),
+        held at ``final`` from ``max_steps`` on.  Host arithmetic."""
+        init, final = self.depth_weight
+        if init == final:
+            return init
+        return init * (final / init) ** (min(max(int(iteration), 0), self.max_steps) / max(self.max_steps, 1))
+
     def _us_leaf(self, lane, n):
         """The zero ``us`` leaf of gsmodel.py:198-199, one per lane, kept across steps (only its ``.grad`` matters:
         dL/du of the view just rendered); a fresh ``torch.zeros`` per view is a fill kernel per view."""
@@ -264,6 +352,12 @@ class Trainer:
             vs = self._vs
             vs.begin()
         loss_sum = [torch.zeros((), device=self.device) for _ in range(lanes)]
+        depth_sum = depth_opts = None
+        if self.depth_priors is not None and any(self.depth_priors[v] is not None for v in mine):
+            depth_sum = [torch.zeros((), device=self.device) for _ in range(lanes)]
+            depth_opts = dataclasses.replace(opts if opts is not None else RenderOptions(mode=self.mode), depth=True,
+                                             alpha=True)
+            depth_scale = self.depth_weight_at(self.iteration) / n_views
         gnorm = [torch.zeros(n, device=self.device) for _ in range(lanes)]
         count = [torch.zeros(n, dtype=torch.int32, device=self.device) for _ in range(lanes)]
         if vs is not None:      # the accumulators above were zeroed on the caller's stream: the lanes start after that
@@ -275,20 +369,23 @@ class Trainer:
                 p = dict(zip(self._KEYS, lv)) if lv is not None else self.params
                 us = self._us_leaf(k, n)                                             # gsmodel.py:198-199
                 tw = None
+                # a view with a depth prior also renders its depth and opacity maps (outputs 3 and 4 of the node)
+                qv = None if self.depth_priors is None else self.depth_priors[v]
+                vopts = opts if qv is None else depth_opts
                 if self.pose_opt:     # the view's camera: its stored pose under its twist (a leaf of this render)
                     tw = self.pose_table.leaf(v)
                     Rcw, tcw = self.pose_table.pose(v, tw)
                     if self.fused_activations:
-                        image, mask = GSRawPoseFunction.apply(p["pws"], p["low_shs"], p["high_shs"], p["alphas_raw"],
-                                                              p["scales_raw"], p["rots_raw"], us, Rcw, tcw, self.cams[v],
-                                                              opts)
+                        out = GSRawPoseFunction.apply(p["pws"], p["low_shs"], p["high_shs"], p["alphas_raw"],
+                                                      p["scales_raw"], p["rots_raw"], us, Rcw, tcw, self.cams[v], vopts)
                     else:
-                        image, mask = GSPoseFunction.apply(*activate(p), us, Rcw, tcw, self.cams[v], opts)
+                        out = GSPoseFunction.apply(*activate(p), us, Rcw, tcw, self.cams[v], vopts)
                 elif self.fused_activations:
-                    image, mask = GSRawFunction.apply(p["pws"], p["low_shs"], p["high_shs"], p["alphas_raw"],
-                                                      p["scales_raw"], p["rots_raw"], us, self.cams[v], opts)
+                    out = GSRawFunction.apply(p["pws"], p["low_shs"], p["high_shs"], p["alphas_raw"],
+                                              p["scales_raw"], p["rots_raw"], us, self.cams[v], vopts)
                 else:
-                    image, mask = GSFunction.apply(*activate(p), us, self.cams[v], opts)
+                    out = GSFunction.apply(*activate(p), us, self.cams[v], vopts)
+                image, mask = out[0], out[1]
                 # loss / n_views (train.py:52-57 with the mean over the step's views): the loss kernels produce the
                 # scaled dL/dimage themselves, backward starts at the image
                 wv = None if self.pixel_weights is None else self.pixel_weights[v]    # (None: the unweighted kernels)
@@ -300,7 +397,14 @@ class Trainer:
                 else:
                     stats, dimage = gau_loss_with_grad(image.detach(), self.gts[v], grad_scale=1.0 / n_views,
                                                        weight=wv)
-                image.backward(dimage)
+                if qv is None:
+                    image.backward(dimage)
+                else:      # the depth term's gradients join dL/dimage: one fused backward pass
+                    dstats, ddepth, dalpha = self._depth_loss_with_grad(
+                        out[2].detach(), out[3].detach(), qv, self.depth_kind, weight=wv,
+                        alpha_min=self.depth_alpha_min, grad_scale=depth_scale)
+                    torch.autograd.backward([image, out[2], out[3]], [dimage, ddepth, dalpha])
+                    depth_sum[k] += dstats[0]
                 if tw is not None:      # (per view, never accumulated in the kernel; one row per camera)
                     self.pose_grad[v] += tw.grad
                 loss_sum[k] += stats[0]
@@ -314,6 +418,12 @@ class Trainer:
                 for t in (loss_sum[k], gnorm[k], count[k]):
                     t.record_stream(torch.cuda.current_stream())
                 loss_sum[0] += loss_sum[k]; gnorm[0] += gnorm[k]; count[0] += count[k]
+                if depth_sum is not None:
+                    depth_sum[k].record_stream(torch.cuda.current_stream())
+                    depth_sum[0] += depth_sum[k]
+        # (the depth terms of this rank's views; a rank whose views have no prior still takes part in the all-reduce)
+        self._depth_sum = None if self.depth_priors is None else \
+            (depth_sum[0] if depth_sum is not None else torch.zeros((), device=self.device))
         return loss_sum[0], gnorm[0], count[0]
 
     def step(self, view_ids: Sequence[int], sync: bool = True):
@@ -391,7 +501,8 @@ class Trainer:
         if self.world > 1:   # sum over ranks of (sum over local views)/V == mean over all views
             DV.allreduce_sum_(DV.coalesce_grads(list(others.values())) + [gnorm, count, loss_sum] +
                               ([self.pose_grad] if self.pose_opt else []) +
-                              ([self.grid_grad, self.last_tv] if self.bilagrid else []))
+                              ([self.grid_grad, self.last_tv] if self.bilagrid else []) +
+                              ([self._depth_sum] if self.depth_priors is not None else []))
         self.grad_accum += gnorm
         self.vis_count += count
         if self.mcmc is not None:     # after the all-reduce: identical on every rank
@@ -410,6 +521,9 @@ class Trainer:
             self.grid_table.step(view_ids, self.grid_grad)
         self.density.update_pws_lr(self.opt)                                     # gsmodel.py:180-183, 332-338
         self.iteration += 1
+        if self.depth_priors is not None:   # the mean unweighted depth term over the step's views that have a prior
+            with_prior = sum(1 for v in view_ids if self.depth_priors[v] is not None)
+            self.last_depth_loss = self._depth_sum / max(with_prior, 1)
         mean = loss_sum / len(view_ids)
         return float(mean) if sync else mean
 

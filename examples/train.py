@@ -53,6 +53,15 @@ def main():
     ap.add_argument("--masks", action="store_true",
                     help="per-pixel loss weights (DESIGN §3.16): masks/<image file name>.png (COLMAP's convention, 0 = "
                          "ignore), masks/<stem>.png or the image's alpha channel; an image without one counts every pixel")
+    ap.add_argument("--depths", action="store_true",
+                    help="depth supervision (DESIGN §3.17): depths/<stem>.npy (float32 disparity, 0 = no data) or "
+                         "depths/<stem>.png (16-bit, value / 65536); sparse/0/depth_params.json makes the priors metric")
+    ap.add_argument("--depth-kind", choices=("metric", "affine", "pearson"), default=None,
+                    help="--depths: the loss (default: metric with depth_params.json, else affine: scale and shift fitted "
+                         "per view and step)")
+    ap.add_argument("--depth-weight", type=float, nargs=2, default=(1.0, 0.01), metavar=("INIT", "FINAL"),
+                    help="--depths: the weight of the depth term decays exponentially from INIT to FINAL (the official "
+                         "code's values; not tuned here)")
     ap.add_argument("--prune-importance-at", default="", metavar="E[,E...]",
                     help="epochs at whose end Gaussians are pruned on their blending weight over all training views "
                          "(DESIGN §3.12); needs --prune-threshold or --prune-fraction")
@@ -65,6 +74,8 @@ def main():
         ap.error("--strategy mcmc needs --cap-max")
     if a.sparse_adam and a.strategy == "mcmc":
         ap.error("--sparse-adam is not supported with --strategy mcmc")
+    if a.depths and a.absgrad:
+        ap.error("--depths is not supported with --absgrad")
     prune_at = sorted({int(e) for e in a.prune_importance_at.split(",") if e.strip()})
     if prune_at and (a.prune_threshold is None) == (a.prune_fraction is None):
         ap.error("--prune-importance-at needs exactly one of --prune-threshold / --prune-fraction")
@@ -82,7 +93,7 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     rank = dist.get_rank() if world > 1 else 0
     print("Try to training %s ..." % a.path) if rank == 0 else None
-    ds = GSplatDataset(a.path, resize_rate=a.resize, masks=a.masks)
+    ds = GSplatDataset(a.path, resize_rate=a.resize, masks=a.masks, depths=a.depths)
     gs = ds.gs
     start = S.Scene(gs["pw"].copy(), gs["rot"].copy(), gs["scale"].copy(), gs["alpha"].copy(), gs["sh"].copy(),
                     None)
@@ -92,7 +103,8 @@ def main():
                  absgrad=a.absgrad, grad_threshold=a.grad_threshold, pose_opt=a.pose_opt,
                  pose_lr=(a.pose_lr_rot, a.pose_lr_trans), strategy=a.strategy, cap_max=a.cap_max,
                  sparse_adam=a.sparse_adam, bilagrid=a.bilagrid, bilagrid_shape=tuple(a.bilagrid_shape),
-                 pixel_weights=ds.weights)
+                 pixel_weights=ds.weights, depth_priors=ds.depth_priors,
+                 depth_kind=a.depth_kind or ds.depth_kind or "affine", depth_weight=tuple(a.depth_weight))
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]
