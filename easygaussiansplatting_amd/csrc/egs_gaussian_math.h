@@ -456,22 +456,6 @@ __device__ __forceinline__ void sh_color_and_jac_dpw(const ShDir<NC>& o, const f
   }
 }
 
-// (tried: streaming (non-temporal) loads of the SH rows -- k_preprocess_fwd 99 -> 172 us, k_sh2color 86 -> 132 us: the
-// twelve loads of a lane re-touch its lines and live on the cache hits; docs/LAB.md)
-template <int K>
-__device__ __forceinline__ void load_sh_row(const float* __restrict__ row, float* sh) {
-  if constexpr (K % 4 == 0) {  // 48- or 192-B rows: dwordx4 loads
-#pragma unroll
-    for (int j = 0; j < K / 4; ++j) {
-      const float4 v = reinterpret_cast<const float4*>(row)[j];
-      sh[4 * j] = v.x; sh[4 * j + 1] = v.y; sh[4 * j + 2] = v.z; sh[4 * j + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < K; ++j) sh[j] = row[j];
-  }
-}
-
 // ---- packed 2D record of the draw kernels (layout: see egs_bin.hip k_pack_records) ----
 #define EGS_NHL2E (-0.72134752044f)  // -0.5 * log2(e)
 // saturating float -> int (v_cvt_i32_f32 semantics; NaN -> 0)

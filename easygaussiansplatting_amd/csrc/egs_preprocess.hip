@@ -7,89 +7,16 @@
 //     k_preprocess_bwd (re-derives the Jacobians in registers and applies the chain rule:
 //     236 + 48 B read, 244 B written, instead of 436 B of Jacobians written then re-read).
 //
-// The math lives in egs_gaussian_math.h (one source of truth for both paths).
+// The math lives in egs_gaussian_math.h (one source of truth for both paths), the row traffic
+// in egs_rows.h: rows_in / rows_out move a workgroup's 256 rows through LDS as one coalesced
+// span, load_row is a lane's own vector loads.
 // All kernels: one Gaussian per lane, 256-thread workgroups (4 waves), >= 3900
 // workgroups at N = 1 M so all 256 CUs are covered many times over.  They are
 // HBM-bound streaming kernels; algorithmic bytes per Gaussian are listed in DESIGN.md.
 #include "egs_gaussian_math.h"
+#include "egs_rows.h"
 
 namespace egs {
-
-// ---- row stores of the seven-op kernels ---------------------------------------------------------------------
-// The reference's ops hand back per-Gaussian rows of K floats (K = 3 ... 24: values and Jacobians, 832 B per
-// Gaussian with calc_J).  A lane that stores its own row issues K dword (or K/4 dwordx4) stores whose 64 lanes are
-// 4K bytes apart: every instruction touches 64 different lines and fills 4 or 16 bytes of each -- the AoS store
-// pattern that kept these kernels at 3.0-3.7 TB/s.  The workgroup's 256 rows are ONE contiguous, 16-B aligned span
-// of the output (256 * K * 4 bytes), so the rows are deposited in LDS -- row stride padded to an odd number of words
-// (of 16-B units for K % 4 == 0): conflict-free -- and the span leaves as coalesced dwordx4 stores, full lines.
-// EVERY row is written, culled Gaussians as zeros: the callers allocate with torch.empty, not torch.zeros (the
-// reference's zero-filled outputs, gausplat.cu:170-178 etc., cost 528 B per Gaussian and step of pure fill here).
-// (the same layout serves the staged row LOADS of the fused kernels, stage_rows_in / stage_rows_out below)
-template <int K>
-struct RowStage {
-  static constexpr bool V4 = (K % 4 == 0);
-  static constexpr int Q = K / 4;                                      // float4 per row (V4)
-  static constexpr int STRIDE = V4 ? 4 * ((Q + 1) | 1) : (K | 1);      // floats
-  static constexpr int LDS_FLOATS = 256 * STRIDE;
-  // rows_out only: rows of one or two floats leave directly and need no LDS
-  static constexpr bool DIRECT = (K <= 2);
-  static constexpr int OUT_LDS_FLOATS = DIRECT ? 1 : LDS_FLOATS;
-};
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
-
-// all 256 threads of the workgroup call this (barriers inside); `row` of lanes past n is ignored
-template <int K>
-__device__ __forceinline__ void rows_out(const float* row, float* __restrict__ dst, int n, int base, float* lds) {
-  using RO = RowStage<K>;
-  const int tid = threadIdx.x;
-  const int rows = min(256, n - base);
-  if constexpr (RO::DIRECT) {
-    if (tid < rows) {
-      if constexpr (K == 2) reinterpret_cast<float2*>(dst)[base + tid] = make_float2(row[0], row[1]);
-      else dst[base + tid] = row[0];
-    }
-  } else {
-    __syncthreads();   // the previous user of `lds` is done with it
-    if constexpr (RO::V4) {
-#pragma unroll
-      for (int j = 0; j < K / 4; ++j)
-        *reinterpret_cast<float4*>(lds + tid * RO::STRIDE + 4 * j) =
-            make_float4(row[4 * j], row[4 * j + 1], row[4 * j + 2], row[4 * j + 3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < K; ++j) lds[tid * RO::STRIDE + j] = row[j];
-    }
-    __syncthreads();
-    float4* __restrict__ d4 = reinterpret_cast<float4*>(dst + (size_t)K * base);
-    const int total = rows * K, nq = total >> 2;
-#pragma unroll
-    for (int j = 0; j < (K + 3) / 4; ++j) {
-      const int f = tid + 256 * j;
-      if (f < nq) {
-        if constexpr (RO::V4) {
-          const int r = f / (K / 4), c = f - r * (K / 4);
-          d4[f] = *reinterpret_cast<const float4*>(lds + r * RO::STRIDE + 4 * c);
-        } else {
-          int r = (4 * f) / K, c = 4 * f - r * K;
-          float v[4];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            v[t] = lds[r * RO::STRIDE + c];
-            if (++c == K) { c = 0; ++r; }
-          }
-          d4[f] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-      }
-    }
-    if constexpr (!RO::V4) {   // <= 3 floats when the last workgroup's row count is not a multiple of four
-      const int f = 4 * nq + tid;
-      if (f < total) {
-        const int r = f / K, c = f - r * K;
-        dst[(size_t)K * base + f] = lds[r * RO::STRIDE + c];
-      }
-    }
-  }
-}
 
 // ---- project                                          (reference kernel.cu:553-617)
 // (60 B per Gaussian: too little to pay for a trip through LDS -- measured 20 us direct, 23 us staged; every row is
@@ -217,7 +144,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SH2COLOR_WA
   for (int c = 0; c < NC; ++c) d.B[c] = 0.f;
   d.d0 = 0.f; d.d1 = 0.f; d.d2 = 0.f; d.ninv = 0.f; d.x = 0.f; d.y = 0.f; d.z = 0.f;
   if (i < n) {   // colour has no depth test in the reference (kernel.cu:619-725)
-    load_sh_row<K>(shs + (size_t)K * i, sh);
+    load_row<K>(shs + (size_t)K * i, sh);
     d = sh_basis_f<NC>(ld3(pws + 3 * (size_t)i), twc);
   }
   if (jac) {
@@ -261,28 +188,6 @@ __global__ __launch_bounds__(256) void k_inv_cov2d(int n, const float* __restric
   rows_out<3>(ci, cinv2ds, n, base, stage);
   rows_out<2>(ar, reinterpret_cast<float*>(areas), n, base, stage);
   if (dcinv2d_dcov2ds) rows_out<9>(J, dcinv2d_dcov2ds, n, base, stage);
-}
-
-// row loads of the chain-rule kernel: the widest vector load the row's alignment allows (a dword load per float
-// costs one L1 lookup per lane and float: 24 instructions x 64 lookups for a dcov3d/drot row, 6 x 64 as dwordx4)
-template <int K>
-__device__ __forceinline__ void load_row(const float* __restrict__ row, float* out) {
-  if constexpr (K % 4 == 0) {
-#pragma unroll
-    for (int j = 0; j < K / 4; ++j) {
-      const float4 v = reinterpret_cast<const float4*>(row)[j];
-      out[4 * j] = v.x; out[4 * j + 1] = v.y; out[4 * j + 2] = v.z; out[4 * j + 3] = v.w;
-    }
-  } else if constexpr (K % 2 == 0) {
-#pragma unroll
-    for (int j = 0; j < K / 2; ++j) {
-      const float2 v = reinterpret_cast<const float2*>(row)[j];
-      out[2 * j] = v.x; out[2 * j + 1] = v.y;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < K; ++j) out[j] = row[j];
-  }
 }
 
 // ----------------------------------------------------------------------------
@@ -369,7 +274,6 @@ __global__ __launch_bounds__(256) void k_chain_rule(
 struct PreParams {
   float fx, fy, cx, cy, limx, limy, det_eps, alpha_skip;
   int clamp_fov, near_cull, nan_cull, radius_mode, footprint, W, H;
-  int stage_in;   // always 0 (experiment, lost: k_preprocess_bwd also stages the SH rows it reads; docs/LAB.md)
 };
 
 // ---- activations of the raw training parameters (reference gsplat/utils.py:121-150) -------------
@@ -384,138 +288,23 @@ __device__ __forceinline__ float4 act_rot(const float4& r, float& norm) {       
   return make_float4(r.x / norm, r.y / norm, r.z / norm, r.w / norm);
 }
 
-// ---- cooperative row staging through LDS --------------------------------------------------
-// A lane-per-Gaussian kernel that reads its own K-float SH row issues K/4 dwordx4 loads whose 64
-// lanes are 4K bytes apart (64 different cache lines per instruction).  Staged instead: the
-// workgroup's 256 rows are one contiguous span, fetched with fully coalesced dwordx4 loads into LDS,
-// then every lane reads its row from LDS (row stride padded to an odd number of 16-B units:
-// conflict-free ds_read_b128: RowStage above).  Same for the dL/dsh rows on the way out.
-template <int K>
-__device__ __forceinline__ void stage_rows_in(const float* __restrict__ src, int n, int base, float* lds, float* row) {
-  using RS = RowStage<K>;
-  const int rows = min(256, n - base);
-  const int tid = threadIdx.x;
-  if constexpr (RS::V4) {
-    const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src + (size_t)K * base);
+// The SH gradient rows of a workgroup on their way out (k_preprocess_bwd, k_sh_grad_views): dL_dsh [N][K], or for RAW the
+// low part dL_dsh [N][3] from its lane and the high part dL_dsh_high [N][K-3] as a span; accum: added to what is there.
+// All 256 threads call this (`stage` holds RowStage<K or K-3>::LDS_FLOATS floats).
+template <int NC, bool RAW>
+__device__ __forceinline__ void sh_grad_rows_out(const float* gsh, float* dL_dsh, float* dL_dsh_high, int n, int base,
+                                                 float* stage, bool accum) {
+  constexpr int K = 3 * NC, KH = K - 3;
+  if constexpr (RAW) {
+    const int i = base + threadIdx.x;
+    if (i < n) {
 #pragma unroll
-    for (int j = 0; j < RS::Q; ++j) {
-      const int f = tid + 256 * j;
-      const int r = f / RS::Q, c = f - r * RS::Q;
-      if (r < rows) *reinterpret_cast<float4*>(lds + r * RS::STRIDE + 4 * c) = s4[f];
+      for (int k = 0; k < 3; ++k) dL_dsh[3 * (size_t)i + k] = gsh[k] + (accum ? dL_dsh[3 * (size_t)i + k] : 0.f);
     }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < RS::Q; ++j) {
-      const float4 v = *reinterpret_cast<const float4*>(lds + tid * RS::STRIDE + 4 * j);
-      row[4 * j] = v.x; row[4 * j + 1] = v.y; row[4 * j + 2] = v.z; row[4 * j + 3] = v.w;
-    }
+    if constexpr (KH > 0) rows_out<KH>(gsh + 3, dL_dsh_high, n, base, stage, accum);
   } else {
-    const float* __restrict__ s1 = src + (size_t)K * base;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      const int f = tid + 256 * j;
-      const int r = f / K, c = f - r * K;
-      if (r < rows) lds[r * RS::STRIDE + c] = s1[f];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < K; ++j) row[j] = lds[tid * RS::STRIDE + j];
+    rows_out<K>(gsh, dL_dsh, n, base, stage, accum);
   }
-}
-
-// the inverse: every lane deposits its row, the workgroup stores the span coalesced
-// accum: dst += rows (a read-modify-write of the same coalesced span) instead of dst = rows
-template <int K>
-__device__ __forceinline__ void stage_rows_out(const float* row, float* __restrict__ dst, int n, int base, float* lds,
-                                               bool accum = false) {
-  using RS = RowStage<K>;
-  const int rows = min(256, n - base);
-  const int tid = threadIdx.x;
-  __syncthreads();   // everyone is done reading the staged input rows
-  if constexpr (RS::V4) {
-#pragma unroll
-    for (int j = 0; j < RS::Q; ++j)
-      *reinterpret_cast<float4*>(lds + tid * RS::STRIDE + 4 * j) =
-          make_float4(row[4 * j], row[4 * j + 1], row[4 * j + 2], row[4 * j + 3]);
-    __syncthreads();
-    float4* __restrict__ d4 = reinterpret_cast<float4*>(dst + (size_t)K * base);
-    // accum: the old values of all the thread's pieces are requested first (clamped addresses, no branches) -- read
-    // at its use inside the loop below, each piece waited for its own load AND for the previous piece's store
-    float4 o[RS::Q];
-    if (accum) {
-      const int flast = rows * RS::Q - 1;
-#pragma unroll
-      for (int j = 0; j < RS::Q; ++j) o[j] = d4[min(tid + 256 * j, flast)];
-    }
-#pragma unroll
-    for (int j = 0; j < RS::Q; ++j) {
-      const int f = tid + 256 * j;
-      const int r = f / RS::Q, c = f - r * RS::Q;
-      if (r < rows) {
-        float4 v = *reinterpret_cast<const float4*>(lds + r * RS::STRIDE + 4 * c);
-        if (accum) { v.x += o[j].x; v.y += o[j].y; v.z += o[j].z; v.w += o[j].w; }
-        d4[f] = v;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < K; ++j) lds[tid * RS::STRIDE + j] = row[j];
-    __syncthreads();
-    float* __restrict__ d1 = dst + (size_t)K * base;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      const int f = tid + 256 * j;
-      const int r = f / K, c = f - r * K;
-      if (r < rows) d1[f] = lds[r * RS::STRIDE + c] + (accum ? d1[f] : 0.f);
-    }
-  }
-}
-
-// Rows whose width is not a multiple of 4 floats (the 45-float high_shs rows): the workgroup's 256 rows
-// are still ONE contiguous, 16-B aligned span (256 * K * 4 bytes), so the span moves as dwordx4 and lands
-// in LDS unpadded; lane t then owns lds[t*K .. t*K+K) -- an odd K makes the dword reads conflict-free.
-template <int K>
-__device__ __forceinline__ void stage_span_in(const float* __restrict__ src, int n, int base, float* lds, float* row) {
-  static_assert(K % 2 == 1, "odd row width expected (conflict-free LDS rows)");
-  const int rows = min(256, n - base);
-  const int tid = threadIdx.x;
-  const int total = rows * K, nq = total >> 2;
-  const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src + (size_t)K * base);
-  for (int f = tid; f < nq; f += 256) reinterpret_cast<float4*>(lds)[f] = s4[f];
-  for (int f = 4 * nq + tid; f < total; f += 256) lds[f] = src[(size_t)K * base + f];   // <= 3 tail floats
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < K; ++j) row[j] = lds[tid * K + j];
-}
-
-template <int K>
-__device__ __forceinline__ void stage_span_out(const float* row, float* __restrict__ dst, int n, int base, float* lds,
-                                               bool accum = false) {
-  const int rows = min(256, n - base);
-  const int tid = threadIdx.x;
-  __syncthreads();   // everyone is done reading the staged input rows
-#pragma unroll
-  for (int j = 0; j < K; ++j) lds[tid * K + j] = row[j];
-  __syncthreads();
-  const int total = rows * K, nq = total >> 2;
-  float4* __restrict__ d4 = reinterpret_cast<float4*>(dst + (size_t)K * base);
-  constexpr int NI = (K + 3) / 4;            // pieces per thread: 256 K / 4 float4 over 256 threads
-  float4 o[NI];
-  if (accum && nq > 0) {                     // (old values first, as in stage_rows_out)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) o[j] = d4[min(tid + 256 * j, nq - 1)];
-  }
-#pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    const int f = tid + 256 * j;
-    if (f < nq) {
-      float4 v = reinterpret_cast<const float4*>(lds)[f];
-      if (accum) { v.x += o[j].x; v.y += o[j].y; v.z += o[j].z; v.w += o[j].w; }
-      d4[f] = v;
-    }
-  }
-  for (int f = 4 * nq + tid; f < total; f += 256)
-    dst[(size_t)K * base + f] = lds[f] + (accum ? dst[(size_t)K * base + f] : 0.f);
 }
 
 // forward.md steps 1-5 for one Gaussian in one pass (== gsmodel.py:21-35 minus splat):
@@ -565,10 +354,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRE_FWD_WAV
   uint32_t dkey = 0u;
   float sh[K];
   if constexpr (RAW) {   // 180-B high_shs rows cannot be dwordx4-loaded per lane: the workgroup's span through LDS
-    if constexpr (KH > 0) {
-      if constexpr (KH % 2 == 1) stage_span_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
-      else stage_rows_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
-    }
+    if constexpr (KH > 0) rows_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
   }
   float4 r[3] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
   float jw[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -584,7 +370,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRE_FWD_WAV
     if constexpr (RAW) {
       sh[0] = shs[3 * (size_t)i]; sh[1] = shs[3 * (size_t)i + 1]; sh[2] = shs[3 * (size_t)i + 2];
     } else {  // direct dwordx4 row loads: staging them through LDS measured 10 % slower here
-      load_sh_row<K>(shs + (size_t)K * i, sh);
+      load_row<K>(shs + (size_t)K * i, sh);
     }
     __builtin_amdgcn_sched_barrier(0);   // (no load sinks below this line, no arithmetic rises above it)
     // ---- everything that needs no SH coefficient
@@ -665,7 +451,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRE_FWD_WAV
     if (i < n) bo.cr[i] = crec;     // (16 B per lane, consecutive lanes: full lines)
   }
   // 48-B records leave as full lines (lane-strided 16-B pieces cost 3x the write requests)
-  if (rec) stage_rows_out<12>(reinterpret_cast<const float*>(r), reinterpret_cast<float*>(rec), n, blockIdx.x * 256, stage);
+  if (rec) rows_out<12>(reinterpret_cast<const float*>(r), reinterpret_cast<float*>(rec), n, blockIdx.x * 256, stage);
   if constexpr (JW) rows_out<9>(jw, dcolor_dpws, n, blockIdx.x * 256, stage);
 }
 
@@ -682,7 +468,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRE_FWD_WAV
 // POSE_ONLY (with POSE; EGS_BWD_POSE_ONLY): the partial row in pose_ws is the ONLY output -- the same 15 per-lane
 // terms and the same reduction as the POSE instance, but no old gradients, no cov3d_vjp, no J3 product, no gsh rows, and
 // the seven dL_d* pointers (NULL or not) are never dereferenced; `mode` is ignored.  With JW the SH rows are never
-// touched; without it they are still staged in (W needs them)
+// touched; without it they are still read (W needs them)
 template <int NC, bool RAW, bool JW, bool EXTRA, bool POSE, bool AA, bool POSE_ONLY>
 __global__ __launch_bounds__(256) void k_preprocess_bwd(
     int n, PreParams pp, const float* __restrict__ pws, const float* __restrict__ rots,
@@ -712,14 +498,10 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
   float sh[JW ? 1 : K], gsh[POSE_ONLY ? 1 : K];
   if constexpr (!JW) {
     if constexpr (RAW) {
-      if constexpr (KH > 0) {
-        if constexpr (KH % 2 == 1) stage_span_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
-        else stage_rows_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
-      }
+      if constexpr (KH > 0) rows_in<KH>(shs_high, n, blockIdx.x * 256, stage, sh + 3);
       if (i < n) { sh[0] = shs[3 * (size_t)i]; sh[1] = shs[3 * (size_t)i + 1]; sh[2] = shs[3 * (size_t)i + 2]; }
-    } else {
-      if (pp.stage_in) stage_rows_in<K>(shs, n, blockIdx.x * 256, stage, sh);
-      else if (i < n) load_sh_row<K>(shs + (size_t)K * i, sh);
+    } else if (i < n) {   // (direct row loads: rows_in measured 10 % slower, reads do not pay for partial lines)
+      load_row<K>(shs + (size_t)K * i, sh);
     }
   }
   // (Tried: the gsh rows formed and staged out right after the loads, the Jacobians and cov3d_vjp behind them, so that
@@ -898,18 +680,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     if (dL_dsh_high && blockIdx.x == 0 && threadIdx.x < 3) dL_dsh_high[threadIdx.x] = twc[threadIdx.x];
     return;
   }
-  if constexpr (RAW) {
-    if (i < n) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) dL_dsh[3 * (size_t)i + k] = gsh[k] + (accum ? dL_dsh[3 * (size_t)i + k] : 0.f);
-    }
-    if constexpr (KH > 0) {
-      if constexpr (KH % 2 == 1) stage_span_out<KH>(gsh + 3, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
-      else stage_rows_out<KH>(gsh + 3, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
-    }
-  } else {
-    stage_rows_out<K>(gsh, dL_dsh, n, blockIdx.x * 256, stage, accum != 0);
-  }
+  sh_grad_rows_out<NC, RAW>(gsh, dL_dsh, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
 }
 
 // The camera pose gradient from the partial rows of k_preprocess_bwd<.., POSE>: ONE workgroup of 1024 threads, thread t sums
@@ -970,18 +741,7 @@ __global__ __launch_bounds__(256) void k_sh_grad_views(int n, int views, const f
 #pragma unroll
   for (int k = 0; k < K; ++k) gsh[k] = 0.f;
   if (i < n) sh_grad_row<NC>(ld3(pws + 3 * (size_t)i), rows, stride, views, n, i, scale, gsh);
-  if constexpr (RAW) {
-    if (i < n) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) dL_dsh[3 * (size_t)i + k] = gsh[k] + (accum ? dL_dsh[3 * (size_t)i + k] : 0.f);
-    }
-    if constexpr (KH > 0) {
-      if constexpr (KH % 2 == 1) stage_span_out<KH>(gsh + 3, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
-      else stage_rows_out<KH>(gsh + 3, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
-    }
-  } else {
-    stage_rows_out<K>(gsh, dL_dsh, n, blockIdx.x * 256, stage, accum != 0);
-  }
+  sh_grad_rows_out<NC, RAW>(gsh, dL_dsh, dL_dsh_high, n, blockIdx.x * 256, stage, accum != 0);
 }
 
 }  // namespace egs
@@ -1114,7 +874,6 @@ static PreParams make_pre_params(const EgsPolicy* pol, float fx, float fy, float
   pp.footprint = pol->footprint; pp.W = width; pp.H = height;
   pp.clamp_fov = pol->fov_mode != 2; pp.near_cull = pol->near_cull; pp.nan_cull = pol->nan_cull;
   pp.radius_mode = pol->radius_mode;
-  pp.stage_in = 0;
   return pp;
 }
 
