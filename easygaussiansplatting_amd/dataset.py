@@ -21,6 +21,13 @@ the official code's monocular depth maps).  A prior is resized with the image by
 pixel never bleeds into its neighbours.  With ``path/sparse/0/depth_params.json`` (the official
 ``{image stem: {"scale": s, "offset": o}}``) every prior becomes s q + o where it has data and ``depth_kind`` is
 "metric"; otherwise ``depth_kind`` is "affine" (scale and shift are fitted during training).
+
+``GSplatDataset(path, normals=True)`` also collects a normal prior per image (``.normal_priors[i]``: float32 [3,H,W]
+CAMERA-frame unit normals -- x right, y down, z forward; all zero = no data -- on the device, or None), for
+``Trainer(normal_priors=ds.normal_priors)``.  Looked for in this order: ``path/normals/<stem>.npy``
+(float, [H,W,3] or [3,H,W]), ``path/normals/<stem>.png`` (8-bit RGB, n = rgb / 127.5 - 1).  ``normals_convention``:
+"opencv" (the frame above, the default) or "opengl" (y up, z towards the viewer: y and z are flipped on reading).
+Resized with the image by NEAREST sampling.
 """
 from __future__ import annotations
 
@@ -87,8 +94,34 @@ def _depth_source(path, name):
     return None
 
 
+NORMALS_CONVENTIONS = ("opencv", "opengl")
+
+
+def _normal_source(path, name):
+    """The image's normal prior as a float32 [3,h,w] array, or None: normals/<stem>.npy, normals/<stem>.png."""
+    stem = os.path.splitext(name)[0]
+    fn = os.path.join(path, "normals", stem + ".npy")
+    if os.path.exists(fn):
+        a = np.load(fn)
+        if a.ndim == 3 and a.shape[2] == 3:      # ([H,W,3]; a [3,H,3] array is read as this form too)
+            a = a.transpose(2, 0, 1)
+        elif a.ndim != 3 or a.shape[0] != 3:
+            raise ValueError("%s: expected a [H,W,3] or [3,H,W] array of normals, got shape %s" % (fn, list(a.shape)))
+        return a.astype(np.float32)
+    fn = os.path.join(path, "normals", stem + ".png")
+    if os.path.exists(fn):
+        from PIL import Image
+        im = Image.open(fn)
+        if im.mode not in ("RGB", "RGBA"):
+            raise ValueError("%s: expected an 8-bit RGB image, got mode %s" % (fn, im.mode))
+        rgb = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        return (rgb.astype(np.float32) / np.float32(127.5) - np.float32(1)).transpose(2, 0, 1)
+    return None
+
+
 class GSplatDataset(torch.utils.data.Dataset):
-    def __init__(self, path, resize_rate=1, device="cuda", masks=False, depths=False) -> None:
+    def __init__(self, path, resize_rate=1, device="cuda", masks=False, depths=False, normals=False,
+                 normals_convention="opencv") -> None:
         super().__init__()
         from PIL import Image
         self.device = device
@@ -99,6 +132,10 @@ class GSplatDataset(torch.utils.data.Dataset):
         self.weights = [] if masks else None
         self.depth_priors = [] if depths else None
         self.depth_kind = None
+        self.normal_priors = [] if normals else None
+        if normals_convention not in NORMALS_CONVENTIONS:
+            raise ValueError("normals_convention must be one of %s, got %r" % (list(NORMALS_CONVENTIONS),
+                                                                               normals_convention))
         depth_params = None
         if depths:
             fn = os.path.join(sparse, "depth_params.json")
@@ -146,6 +183,14 @@ class GSplatDataset(torch.utils.data.Dataset):
                                          np.float32(0)).astype(np.float32)
                 self.depth_priors.append(None if q is None else
                                          torch.from_numpy(np.ascontiguousarray(q, np.float32)).to(device))
+            if normals:
+                nq = _normal_source(path, ip.name)
+                if nq is not None:
+                    nq = np.stack([_nearest(c, image.width, image.height) for c in nq])
+                    if normals_convention == "opengl":      # (y up, z towards the viewer -> y down, z forward)
+                        nq = nq * np.array([1, -1, -1], np.float32)[:, None, None]
+                self.normal_priors.append(None if nq is None else
+                                          torch.from_numpy(np.ascontiguousarray(nq, np.float32)).to(device))
         cache = os.path.join(sparse, "points3D.npy")
         if os.path.exists(cache):
             self.gs = np.load(cache)

@@ -140,6 +140,34 @@ def _checked_depth_priors(depth_priors, gt_images, device):
     return out
 
 
+def _checked_normal_priors(normal_priors, gt_images, device):
+    """``Trainer(normal_priors=...)``, checked once (host synchronisations are fine here) -> None, or a list with one
+    float32 [3,H,W] camera-frame normal map on ``device`` or None per view.  ValueError names the view."""
+    if normal_priors is None:
+        return None
+    priors, gts = list(normal_priors), list(gt_images)
+    if len(priors) != len(gts):
+        raise ValueError("Trainer(normal_priors=...): %d entries for %d views (one per camera; None for a view without "
+                         "a prior)" % (len(priors), len(gts)))
+    out = []
+    for v, (q, gt) in enumerate(zip(priors, gts)):
+        if q is None:
+            out.append(None)
+            continue
+        what = "Trainer(normal_priors=...): view %d" % v
+        if not isinstance(q, torch.Tensor) or q.dtype != torch.float32:
+            raise ValueError("%s must be a float32 tensor (camera-frame normals; all zero = no data), got %s"
+                             % (what, q.dtype if isinstance(q, torch.Tensor) else type(q).__name__))
+        if tuple(q.shape) != (3,) + tuple(gt.shape[-2:]):
+            raise ValueError("%s has shape %s, its ground-truth image is %s"
+                             % (what, list(q.shape), list(gt.shape[-2:])))
+        q = q.to(device=device).contiguous()
+        if not bool((torch.isfinite(q).all(0) & ((q * q).sum(0) > 0)).any()):
+            raise ValueError("%s has no pixel with data: the view would have no prior term (pass None instead)" % what)
+        out.append(q)
+    return out
+
+
 def _checked_depth_weight(depth_weight):
     """-> (init, final) of the depth term's weight; a single float is constant"""
     try:
@@ -162,7 +190,9 @@ class Trainer:
                  cap_max: int = None, mcmc_options: dict = None, sparse_adam: bool = False,
                  bilagrid: bool = False, bilagrid_shape=_appearance.DEFAULT_SHAPE, bilagrid_lr: float = 2e-3,
                  bilagrid_tv: float = 10.0, pixel_weights: Sequence = None, depth_priors: Sequence = None,
-                 depth_kind: str = "affine", depth_weight=(1.0, 0.01), depth_alpha_min: float = 0.05):
+                 depth_kind: str = "affine", depth_weight=(1.0, 0.01), depth_alpha_min: float = 0.05,
+                 normal_priors: Sequence = None, normal_weight: float = 0.05, normal_smooth: float = 0.0,
+                 normal_alpha_min: float = 0.05, normal_edge_gamma: float = 10.0):
         """``strategy``: how Gaussians are added and removed.  "default" is the reference's clone / split / prune /
         alpha reset (``density.DensityControl``).  "mcmc" (needs ``cap_max``, the hard limit on the number
         of Gaussians) is ``density.MCMCControl``: every step adds the opacity / scale regularisers' gradient before the
@@ -222,7 +252,22 @@ class Trainer:
         the step's views that have a prior is kept as ``last_depth_loss`` (a device tensor).  Not with ``absgrad`` (the
         draw kernel has no instance for absolute gradients and render extras) nor with ``mode`` other than "fused".
         A render with the maps takes the unsplit draw kernels.  With ``depth_priors=None`` nothing in a step differs: no
-        extra tensor, no extra launch, libegs_depthloss.so is not loaded."""
+        extra tensor, no extra launch, libegs_depthloss.so is not loaded.
+
+        ``normal_priors``, ``normal_smooth``: surface-normal terms on the rendered depth map (fused path
+        only).  ``normal_priors``: a sequence with one entry per camera: a float32 tensor [3,H,W] of the view's
+        ground-truth size holding CAMERA-frame normals (x right, y down, z forward; a pixel that is all zero or
+        non-finite has no data), or None for a view without one.  Checked once, here (shape, dtype, at least one pixel
+        with data: ``ValueError`` naming the view).  ``normal_smooth`` > 0 adds the edge-aware smoothness of the normal
+        for EVERY view, guided by the view's ground-truth image; it needs no prior.  A view with either term also renders
+        its depth and opacity maps, ``normalloss.normal_loss_with_grad`` turns them into dL/ddepth and dL/dalpha -- added
+        to those of the depth term when both are on -- and ONE backward pass takes these and dL/dimage.  The terms enter
+        the step as ``normal_weight`` x prior term + ``normal_smooth`` x smoothness term; ``pixel_weights[v]`` weights
+        their pixels too.  ``normal_weight`` = 0.05, ``normal_alpha_min`` = 0.05 and ``normal_edge_gamma`` = 10 are
+        defaults nobody has tuned.  ``step`` still returns the image loss; ``last_normal_loss`` is a device tensor [2]:
+        the mean unweighted prior term over the step's views that have a prior, and the mean smoothness term over the
+        step's views.  Not with ``absgrad`` nor with ``mode`` other than "fused", as for ``depth_priors``.  Without the two
+        arguments nothing in a step differs: no extra tensor, no extra launch, libegs_normalloss.so is not loaded."""
         self.device = device
         self.pixel_weights = _checked_pixel_weights(pixel_weights, gt_images, device)
         self.depth_priors = _checked_depth_priors(depth_priors, gt_images, device)
@@ -245,6 +290,33 @@ class Trainer:
             if not 0.0 <= self.depth_alpha_min < float("inf"):
                 raise ValueError("Trainer(depth_alpha_min=%r): expected a finite value >= 0" % (depth_alpha_min,))
             self._depth_loss_with_grad = _depthloss.depth_loss_with_grad
+        self.normal_priors = _checked_normal_priors(normal_priors, gt_images, device)
+        self.normal_smooth = float(normal_smooth)
+        if not 0.0 <= self.normal_smooth < float("inf"):
+            raise ValueError("Trainer(normal_smooth=%r): expected a finite value >= 0" % (normal_smooth,))
+        self.normals_on = self.normal_priors is not None or self.normal_smooth > 0
+        self.last_normal_loss = None
+        self._normal_sum = None
+        if self.normals_on:
+            what = "normal_priors=..." if self.normal_priors is not None else "normal_smooth=%r" % (normal_smooth,)
+            if absgrad:
+                raise ValueError("Trainer(%s) with absgrad=True: a view with a normal term renders its depth and "
+                                 "opacity maps, and the draw kernel has no instance for absolute gradients and render "
+                                 "extras" % what)
+            if mode != "fused":
+                raise ValueError("Trainer(%s) needs mode='fused' (the depth and opacity maps are the "
+                                 "fused path's), got %r" % (what, mode))
+            self.normal_weight = float(normal_weight)
+            if not 0.0 <= self.normal_weight < float("inf"):
+                raise ValueError("Trainer(normal_weight=%r): expected a finite value >= 0" % (normal_weight,))
+            self.normal_alpha_min = float(normal_alpha_min)
+            if not 0.0 <= self.normal_alpha_min < float("inf"):
+                raise ValueError("Trainer(normal_alpha_min=%r): expected a finite value >= 0" % (normal_alpha_min,))
+            self.normal_edge_gamma = float(normal_edge_gamma)
+            if not 0.0 <= self.normal_edge_gamma < float("inf"):
+                raise ValueError("Trainer(normal_edge_gamma=%r): expected a finite value >= 0" % (normal_edge_gamma,))
+            from . import normalloss as _normalloss
+            self._normal_loss_with_grad = _normalloss.normal_loss_with_grad
         if strategy not in ("default", "mcmc"):
             raise ValueError("Trainer(strategy=%r): expected 'default' or 'mcmc'" % (strategy,))
         if strategy == "mcmc" and cap_max is None:
@@ -352,12 +424,18 @@ class Trainer:
             vs = self._vs
             vs.begin()
         loss_sum = [torch.zeros((), device=self.device) for _ in range(lanes)]
-        depth_sum = depth_opts = None
-        if self.depth_priors is not None and any(self.depth_priors[v] is not None for v in mine):
-            depth_sum = [torch.zeros((), device=self.device) for _ in range(lanes)]
+        depth_sum = depth_opts = normal_sum = None
+        with_depth = self.depth_priors is not None and any(self.depth_priors[v] is not None for v in mine)
+        with_normals = self.normals_on and (self.normal_smooth > 0 or
+                                            any(self.normal_priors[v] is not None for v in mine))
+        if with_depth or with_normals:
             depth_opts = dataclasses.replace(opts if opts is not None else RenderOptions(mode=self.mode), depth=True,
                                              alpha=True)
+        if with_depth:
+            depth_sum = [torch.zeros((), device=self.device) for _ in range(lanes)]
             depth_scale = self.depth_weight_at(self.iteration) / n_views
+        if with_normals:     # (L_p, L_s) summed over the views of a lane
+            normal_sum = [torch.zeros(2, device=self.device) for _ in range(lanes)]
         gnorm = [torch.zeros(n, device=self.device) for _ in range(lanes)]
         count = [torch.zeros(n, dtype=torch.int32, device=self.device) for _ in range(lanes)]
         if vs is not None:      # the accumulators above were zeroed on the caller's stream: the lanes start after that
@@ -371,7 +449,10 @@ class Trainer:
                 tw = None
                 # a view with a depth prior also renders its depth and opacity maps (outputs 3 and 4 of the node)
                 qv = None if self.depth_priors is None else self.depth_priors[v]
-                vopts = opts if qv is None else depth_opts
+                # ... and so does a view with a normal term (a prior of its own, or the smoothness term of every view)
+                nv = None if self.normal_priors is None else self.normal_priors[v]
+                with_n = self.normals_on and (nv is not None or self.normal_smooth > 0)
+                vopts = opts if qv is None and not with_n else depth_opts
                 if self.pose_opt:     # the view's camera: its stored pose under its twist (a leaf of this render)
                     tw = self.pose_table.leaf(v)
                     Rcw, tcw = self.pose_table.pose(v, tw)
@@ -397,14 +478,25 @@ class Trainer:
                 else:
                     stats, dimage = gau_loss_with_grad(image.detach(), self.gts[v], grad_scale=1.0 / n_views,
                                                        weight=wv)
-                if qv is None:
+                if qv is None and not with_n:
                     image.backward(dimage)
-                else:      # the depth term's gradients join dL/dimage: one fused backward pass
-                    dstats, ddepth, dalpha = self._depth_loss_with_grad(
-                        out[2].detach(), out[3].detach(), qv, self.depth_kind, weight=wv,
-                        alpha_min=self.depth_alpha_min, grad_scale=depth_scale)
+                else:      # the map terms' gradients join dL/dimage: one fused backward pass
+                    ddepth = dalpha = None
+                    if qv is not None:
+                        dstats, ddepth, dalpha = self._depth_loss_with_grad(
+                            out[2].detach(), out[3].detach(), qv, self.depth_kind, weight=wv,
+                            alpha_min=self.depth_alpha_min, grad_scale=depth_scale)
+                        depth_sum[k] += dstats[0]
+                    if with_n:
+                        nstats, ndepth, nalpha = self._normal_loss_with_grad(
+                            out[2].detach(), out[3].detach(), self.cams[v], normals=nv, guide=self.gts[v],
+                            smooth=self.normal_smooth > 0, weight=wv, alpha_min=self.normal_alpha_min,
+                            edge_gamma=self.normal_edge_gamma, prior_scale=self.normal_weight / n_views,
+                            smooth_scale=self.normal_smooth / n_views)
+                        normal_sum[k] += nstats[:2]
+                        ddepth = ndepth if ddepth is None else ddepth.add_(ndepth)
+                        dalpha = nalpha if dalpha is None else dalpha.add_(nalpha)
                     torch.autograd.backward([image, out[2], out[3]], [dimage, ddepth, dalpha])
-                    depth_sum[k] += dstats[0]
                 if tw is not None:      # (per view, never accumulated in the kernel; one row per camera)
                     self.pose_grad[v] += tw.grad
                 loss_sum[k] += stats[0]
@@ -421,9 +513,14 @@ class Trainer:
                 if depth_sum is not None:
                     depth_sum[k].record_stream(torch.cuda.current_stream())
                     depth_sum[0] += depth_sum[k]
+                if normal_sum is not None:
+                    normal_sum[k].record_stream(torch.cuda.current_stream())
+                    normal_sum[0] += normal_sum[k]
         # (the depth terms of this rank's views; a rank whose views have no prior still takes part in the all-reduce)
         self._depth_sum = None if self.depth_priors is None else \
             (depth_sum[0] if depth_sum is not None else torch.zeros((), device=self.device))
+        self._normal_sum = None if not self.normals_on else \
+            (normal_sum[0] if normal_sum is not None else torch.zeros(2, device=self.device))
         return loss_sum[0], gnorm[0], count[0]
 
     def step(self, view_ids: Sequence[int], sync: bool = True):
@@ -502,7 +599,8 @@ class Trainer:
             DV.allreduce_sum_(DV.coalesce_grads(list(others.values())) + [gnorm, count, loss_sum] +
                               ([self.pose_grad] if self.pose_opt else []) +
                               ([self.grid_grad, self.last_tv] if self.bilagrid else []) +
-                              ([self._depth_sum] if self.depth_priors is not None else []))
+                              ([self._depth_sum] if self.depth_priors is not None else []) +
+                              ([self._normal_sum] if self.normals_on else []))
         self.grad_accum += gnorm
         self.vis_count += count
         if self.mcmc is not None:     # after the all-reduce: identical on every rank
@@ -524,6 +622,11 @@ class Trainer:
         if self.depth_priors is not None:   # the mean unweighted depth term over the step's views that have a prior
             with_prior = sum(1 for v in view_ids if self.depth_priors[v] is not None)
             self.last_depth_loss = self._depth_sum / max(with_prior, 1)
+        if self.normals_on:     # (L_p over the step's views that have a prior, L_s over the step's views)
+            with_prior = 0 if self.normal_priors is None else \
+                sum(1 for v in view_ids if self.normal_priors[v] is not None)
+            self.last_normal_loss = torch.stack([self._normal_sum[0] / max(with_prior, 1),
+                                                 self._normal_sum[1] / len(view_ids)])
         mean = loss_sum / len(view_ids)
         return float(mean) if sync else mean
 

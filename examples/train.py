@@ -62,6 +62,17 @@ def main():
     ap.add_argument("--depth-weight", type=float, nargs=2, default=(1.0, 0.01), metavar=("INIT", "FINAL"),
                     help="--depths: the weight of the depth term decays exponentially from INIT to FINAL (the official "
                          "code's values; not tuned here)")
+    ap.add_argument("--normals", action="store_true",
+                    help="surface-normal supervision (DESIGN §3.18): normals/<stem>.npy ([H,W,3] or [3,H,W], camera frame, "
+                         "all zero = no data) or normals/<stem>.png (8-bit RGB, n = rgb / 127.5 - 1)")
+    ap.add_argument("--normals-convention", choices=("opencv", "opengl"), default="opencv",
+                    help="--normals: the frame of the files: opencv (x right, y down, z forward) or opengl (y up, z "
+                         "towards the viewer)")
+    ap.add_argument("--normal-weight", type=float, default=0.05, metavar="W",
+                    help="--normals: the weight of the prior term (not tuned here)")
+    ap.add_argument("--normal-smooth", type=float, default=0.0, metavar="S",
+                    help="the weight of the edge-aware smoothness of the rendered depth's normal, for every view; needs "
+                         "no prior (0: off; not tuned here)")
     ap.add_argument("--prune-importance-at", default="", metavar="E[,E...]",
                     help="epochs at whose end Gaussians are pruned on their blending weight over all training views "
                          "(DESIGN §3.12); needs --prune-threshold or --prune-fraction")
@@ -76,6 +87,8 @@ def main():
         ap.error("--sparse-adam is not supported with --strategy mcmc")
     if a.depths and a.absgrad:
         ap.error("--depths is not supported with --absgrad")
+    if (a.normals or a.normal_smooth > 0) and a.absgrad:
+        ap.error("--normals / --normal-smooth are not supported with --absgrad")
     prune_at = sorted({int(e) for e in a.prune_importance_at.split(",") if e.strip()})
     if prune_at and (a.prune_threshold is None) == (a.prune_fraction is None):
         ap.error("--prune-importance-at needs exactly one of --prune-threshold / --prune-fraction")
@@ -93,7 +106,8 @@ def main():
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     rank = dist.get_rank() if world > 1 else 0
     print("Try to training %s ..." % a.path) if rank == 0 else None
-    ds = GSplatDataset(a.path, resize_rate=a.resize, masks=a.masks, depths=a.depths)
+    ds = GSplatDataset(a.path, resize_rate=a.resize, masks=a.masks, depths=a.depths, normals=a.normals,
+                       normals_convention=a.normals_convention)
     gs = ds.gs
     start = S.Scene(gs["pw"].copy(), gs["rot"].copy(), gs["scale"].copy(), gs["alpha"].copy(), gs["sh"].copy(),
                     None)
@@ -104,7 +118,8 @@ def main():
                  pose_lr=(a.pose_lr_rot, a.pose_lr_trans), strategy=a.strategy, cap_max=a.cap_max,
                  sparse_adam=a.sparse_adam, bilagrid=a.bilagrid, bilagrid_shape=tuple(a.bilagrid_shape),
                  pixel_weights=ds.weights, depth_priors=ds.depth_priors,
-                 depth_kind=a.depth_kind or ds.depth_kind or "affine", depth_weight=tuple(a.depth_weight))
+                 depth_kind=a.depth_kind or ds.depth_kind or "affine", depth_weight=tuple(a.depth_weight),
+                 normal_priors=ds.normal_priors, normal_weight=a.normal_weight, normal_smooth=a.normal_smooth)
     os.makedirs(a.out, exist_ok=True)
     for epoch in range(a.epochs):
         loss = tr.fit(1, views_per_step=views_per_step, rng_seed=epoch, densify_until=-1)[0]
