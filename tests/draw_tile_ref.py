@@ -20,7 +20,15 @@ A Gaussian that violates one is RE-DRAWN from its next counter stream (bounded);
 is left out of any comparison.  ``report(name)`` states the re-draws, list lengths, per-block stop indices and the hit /
 clamp / floor counts; ``check_claims`` asserts that every scenario still is what it says.
 
-``extras`` (render extras, absgrad) are not covered: ``case`` takes ``extras=None`` for a later change to add them."""
+Render extras (``case(name, seed, extras=True)``; tests/test_gpu_draw_tiles_extras.py runs the EXTRA instances of the
+kernels on them).  No decision of the blend depends on z, the background or the upstream gradients of the depth and
+opacity maps, so the geometry, the lists and every claim are those of the plain case: nothing is re-drawn.  Added, all
+from the counter generator: a per-Gaussian camera-space ``z`` (log-uniform over 0.2 .. 100, independent of the list-order
+``depths``: a z taken from the wrong entry is orders of magnitude off), ``dloss_ddepth`` / ``dloss_dalpha`` drawn like
+``dloss_dgammas`` and zero on the same block, and the background BG.  ``reference``, ``distances`` and ``pixel_floor``
+with ``extras=True`` also cover ``depth``, ``alpha`` and ``dz``; ``blend`` and ``backward_hw`` restate the EXTRA kernels'
+own operations (cd += w z, alpha = 1 - tau, fmaf(tau, bg, c); dq = fmaf(dL/ddepth, z, ..) - lq, dz += dL/ddepth w).
+``distances`` also carries ``dus_abs``: the rows of the absolute screen-space gradient (tests/absgrad_ref.py)."""
 import functools
 
 import numpy as np
@@ -41,6 +49,7 @@ NU = 12                                      # uniforms per (Gaussian, retry)
 f32 = np.float32
 NHL2E = f32(-0.72134752044)                  # -0.5 log2(e): the record's pre-scaled conic (egs_gaussian_math.h)
 STEEP = 1.0 / 0.3                            # the steepest legal conic: cov2d carries the +0.3 dilation
+BG = (0.2, 0.5, 0.9)                         # the background of the extras cases
 
 
 def geom(t):
@@ -345,7 +354,7 @@ def poly_exponent(qxx, qxy, qyy, ux, uy, la, tx, ty, fma=False):
     return (qxx * (X * X).astype(f32) + e).astype(f32)
 
 
-def blend(arrays, lists, policy, dtype=np.float64, poly=False, diag=None, hw=None, fma=False):
+def blend(arrays, lists, policy, dtype=np.float64, poly=False, diag=None, hw=None, fma=False, extras=None):
     """``O.draw`` restated tile by tile (tests/test_draw_tile_ref_cpu.py pins it to ``O.draw`` bit for bit) with two
     additions.  ``poly``: float32, alpha' = exp2(e) of ``poly_exponent`` capped as k_draw caps it (min(e, log2 alpha)
     where the floor applies, log2 0.99 where the clamp does), the skip test in the exponent domain, tau -= tau alpha'.
@@ -353,7 +362,15 @@ def blend(arrays, lists, policy, dtype=np.float64, poly=False, diag=None, hw=Non
     operations of k_draw that NumPy rounds correctly, each moved by its ulp in that direction -- the derived log2(alpha)
     and the exponential (v_exp_f32).  ``diag``: a dict
     that receives, per Gaussian, hits / clamped / floored pixel counts, the smallest relative distance of a live alpha'
-    from alpha_skip and of a post-blend tau from tau_stop.  -> image, contrib, final_tau"""
+    from alpha_skip and of a post-blend tau from tau_stop.  -> image, contrib, final_tau
+    ``extras``: the background [3]; z is ``arrays["z"]`` -> image over the background, contrib, final_tau, depth, alpha.  In
+    float64 (no ``poly``) in the way of the oracle's composition -- ``O.draw`` on the colours (z, 1, 0), then image +
+    (1 - alpha) bg; tests/test_draw_tile_ref_cpu.py pins it bit for bit --, in float32 in k_draw's own way: cd += w z
+    (``fma``: contracted), alpha = 1 - tau, image = fmaf(tau, bg, c), an empty tile the background itself."""
+    kway = extras is not None and (poly or dtype != np.float64)
+    if extras is not None:
+        zs = np.asarray(arrays["z"], dtype); bgv = np.asarray(extras, dtype)
+        depth = np.zeros((H, W), dtype); alpha = np.zeros((H, W), dtype)
     us = np.asarray(arrays["us"], dtype); cinv = np.asarray(arrays["cinv2ds"], dtype)
     alphas = np.asarray(arrays["alphas"], dtype).reshape(-1); colors = np.asarray(arrays["colors"], dtype)
     n = us.shape[0]
@@ -370,6 +387,7 @@ def blend(arrays, lists, policy, dtype=np.float64, poly=False, diag=None, hw=Non
         py, px = np.meshgrid(np.arange(y0, y0 + hh, dtype=dtype), np.arange(x0, x0 + ww, dtype=dtype), indexing="ij")
         tau = np.ones((hh, ww), dtype); col = np.zeros((3, hh, ww), dtype)
         cont = np.zeros((hh, ww), np.int32); done = np.zeros((hh, ww), bool)
+        cd = np.zeros((hh, ww), dtype); ca = np.zeros((hh, ww), dtype)
         for k, g in enumerate(ids):
             if done.all():
                 break
@@ -412,6 +430,11 @@ def blend(arrays, lists, policy, dtype=np.float64, poly=False, diag=None, hw=Non
             act = act & ~skip
             w = np.where(act, tau * ap, 0)
             col += w[None] * colors[g][:, None, None]
+            if extras is not None:
+                if kway:
+                    cd = _fma(w, zs[g], cd) if fma else cd + w * zs[g]
+                else:
+                    cd += w * zs[g]; ca += w * dtype(1)
             cont = np.where(act, k + 1, cont)
             tau = np.where(act, (tau - w) if poly else tau * (1 - ap), tau)
             if policy.tau_stop > 0:
@@ -430,14 +453,29 @@ def blend(arrays, lists, policy, dtype=np.float64, poly=False, diag=None, hw=Non
         image[:, y0:y0 + hh, x0:x0 + ww] = col
         contrib[y0:y0 + hh, x0:x0 + ww] = cont
         final_tau[y0:y0 + hh, x0:x0 + ww] = tau
-    return image, contrib, final_tau
+        if extras is not None:
+            depth[y0:y0 + hh, x0:x0 + ww] = cd
+            alpha[y0:y0 + hh, x0:x0 + ww] = (dtype(1) - tau) if kway else ca
+            if kway:
+                image[:, y0:y0 + hh, x0:x0 + ww] = np.stack([_fma(tau, bgv[ch], col[ch]) for ch in range(3)]).astype(dtype)
+    if extras is None:
+        return image, contrib, final_tau
+    if kway:
+        for t, ids in enumerate(lists):
+            if len(ids) == 0:
+                tx, ty, x0, y0, ww, hh = geom(t)
+                image[:, y0:y0 + hh, x0:x0 + ww] = bgv[:, None, None]
+    else:
+        image = image + (1.0 - alpha)[None] * bgv[:, None, None]
+    return image, contrib, final_tau, depth, alpha
 
 
 def perturbed(arrays, j):
-    """the four float tensors of the draw moved by one ulp (``pergaussian_ref.perturbed``); lists, areas and depths stay"""
+    """the four float tensors of the draw (and ``z`` of an extras case: sorted behind them, their streams stay) moved by
+    one ulp (``pergaussian_ref.perturbed``); lists, areas and depths stay"""
     from tests.pergaussian_ref import perturbed as P
     out = dict(arrays)
-    out.update(P({k: arrays[k] for k in ("us", "cinv2ds", "alphas", "colors")}, j))
+    out.update(P({k: arrays[k] for k in ("us", "cinv2ds", "alphas", "colors", "z") if k in arrays}, j))
     return out
 
 
@@ -471,12 +509,28 @@ def _violators(arrays, lists):
     return bad
 
 
-@functools.lru_cache(maxsize=None)
+def _normalised(f):
+    """``f(name, [pname,] seed=0, extras=False)`` cached on its full argument tuple, however the caller spelt it"""
+    cached = functools.lru_cache(maxsize=None)(f)
+    npos = f.__code__.co_argcount - 2
+
+    @functools.wraps(f)
+    def g(*args, seed=0, extras=False):
+        args = args + (seed, extras)[len(args) - npos:] if len(args) < npos + 2 else args
+        return cached(*args[:npos], int(args[npos]), bool(args[npos + 1]))
+    g.__wrapped__ = f
+    return g
+
+
+@_normalised
 def case(name, seed=0, extras=None):
     """-> Case of set ``name``: ``arrays`` (us, cinv2ds, alphas, colors, depths, areas, dloss_dgammas; read-only),
     ``lists`` (intended Gaussian ids per tile, policy G), ``tile_of`` / ``pos_of`` per Gaussian, ``scenarios``,
-    ``redrawn`` (how many Gaussians were drawn again) -- a pure function of its arguments."""
-    assert extras is None, "render extras are not covered yet"
+    ``redrawn`` (how many Gaussians were drawn again) -- a pure function of its arguments.
+    ``extras`` true: the same Case object's arrays (nothing is re-drawn) plus ``z`` [N], ``dloss_ddepth`` and
+    ``dloss_dalpha`` [H, W]; ``bg`` = float32(BG), ``extras`` = True."""
+    if extras:
+        return _with_extras(case(name, seed))
     n = sum(len(s["entries"]) for s in _scenarios(name))
     retry = np.zeros(n, np.int64)
     for _ in range(MAX_ROUNDS):
@@ -497,6 +551,27 @@ def case(name, seed=0, extras=None):
     c = Case()
     c.name, c.seed, c.arrays, c.lists, c.tile_of, c.pos_of, c.scenarios = name, seed, arrays, lists, tile_of, pos_of, sc
     c.redrawn, c.retries, c.n = int((retry > 0).sum()), int(retry.sum()), n
+    c.extras, c.bg = False, None
+    return c
+
+
+def _with_extras(base):
+    """the Case ``base`` with what the render extras add, from counter streams of their own"""
+    c = Case()
+    c.__dict__.update(base.__dict__)
+    s = _seed_of(base.name, base.seed)
+    arrays = dict(base.arrays)
+    arrays["z"] = (0.2 * 500.0 ** S.uniform01(s, 79, (base.n,))).astype(f32)
+    zt, zb = _zero_block(base.name)
+    tx, ty, x0, y0, _, _ = geom(zt)
+    for key, stream in (("dloss_ddepth", 80), ("dloss_dalpha", 82)):
+        w = S.normal(s, stream, (H, W)) * 10.0 ** (-6.0 * S.uniform01(s, stream + 1, (H, W)))
+        w[y0 + 8 * (zb >> 1):y0 + 8 * (zb >> 1) + 8, x0 + 8 * (zb & 1):x0 + 8 * (zb & 1) + 8] = 0.0
+        arrays[key] = w.astype(f32)
+    for v in arrays.values():
+        v.setflags(write=False)
+    c.arrays, c.extras, c.bg = arrays, True, np.array(BG, f32)
+    c.bg.setflags(write=False)
     return c
 
 
@@ -508,21 +583,46 @@ def lists(c, pname):
 
 # --------------------------------------------------------------------------------------------------------- reference
 def forward(c, pname, dtype=np.float64, arrays=None):
-    """image, contrib, final_tau of ``O.draw`` on the lists of the case"""
+    """image, contrib, final_tau of ``O.draw`` on the lists of the case; an extras case: image over the background,
+    contrib, final_tau, depth, alpha by the composition of tests/test_gpu_render_extras.py::oracle -- ``O.draw`` on the
+    colours (z, 1, 0), then image + (1 - alpha) bg"""
     a = c.arrays if arrays is None else arrays
     _, rg, gs = lists(c, pname)
-    return O.draw(W, H, rg, gs, a["us"], a["cinv2ds"], a["alphas"], a["colors"], a["areas"], POLICIES[pname], dtype)
+    img, cont, tau = O.draw(W, H, rg, gs, a["us"], a["cinv2ds"], a["alphas"], a["colors"], a["areas"], POLICIES[pname],
+                            dtype)
+    if not c.extras:
+        return img, cont, tau
+    ez = O.draw(W, H, rg, gs, a["us"], a["cinv2ds"], a["alphas"], _zcolors(a["z"], dtype), a["areas"], POLICIES[pname],
+                dtype)[0]
+    return img + (1.0 - ez[1])[None] * np.asarray(c.bg, dtype)[:, None, None], cont, tau, ez[0], ez[1]
+
+
+def _zcolors(z, dtype):
+    z = np.asarray(z, dtype)
+    return np.stack([z, np.ones_like(z), np.zeros_like(z)], 1)
 
 
 def backward(c, pname, contrib, final_tau, dtype=np.float64, arrays=None):
-    """dloss_dus [N,2], dloss_dcinv2ds [N,3], dloss_dalphas [N], dloss_dcolors [N,3] of ``O.draw_backward``"""
+    """dloss_dus [N,2], dloss_dcinv2ds [N,3], dloss_dalphas [N], dloss_dcolors [N,3] of ``O.draw_backward``; an extras
+    case: the gradient of <Wi, image> + <Wd, depth> + <Wa, alpha> -- ``O.draw_backward`` on the real colours with Wi plus
+    ``O.draw_backward`` on the colours (z, 1, 0) with (Wd, Wa - Wi . bg, 0) --, and dz [N], the first column of the second
+    call's colour gradient"""
     a = c.arrays if arrays is None else arrays
     _, rg, gs = lists(c, pname)
-    return O.draw_backward(W, H, rg, gs, a["us"], a["cinv2ds"], a["alphas"], a["colors"], contrib, final_tau,
-                           c.arrays["dloss_dgammas"], a["areas"], POLICIES[pname], dtype)
+    g1 = O.draw_backward(W, H, rg, gs, a["us"], a["cinv2ds"], a["alphas"], a["colors"], contrib, final_tau,
+                         c.arrays["dloss_dgammas"], a["areas"], POLICIES[pname], dtype)
+    if not c.extras:
+        return g1
+    Wi = np.asarray(c.arrays["dloss_dgammas"], dtype)
+    Wd, Wa = np.asarray(c.arrays["dloss_ddepth"], dtype), np.asarray(c.arrays["dloss_dalpha"], dtype)
+    dl2 = np.stack([Wd, Wa - (Wi * np.asarray(c.bg, dtype)[:, None, None]).sum(0), np.zeros_like(Wd)])
+    g2 = O.draw_backward(W, H, rg, gs, a["us"], a["cinv2ds"], a["alphas"], _zcolors(a["z"], dtype), contrib, final_tau,
+                         dl2, a["areas"], POLICIES[pname], dtype)
+    return g1[0] + g2[0], g1[1] + g2[1], g1[2] + g2[2], g1[3], g2[3][:, 0].copy()
 
 
 GRADS = ("dus", "dcinv2ds", "dalphas", "dcolors")
+GRADS_X = GRADS + ("dz",)                                    # an extras case
 HW_MODES = ((1, 1), (1, -1), (-1, 1), (-1, -1), (0, 0))      # (sign of the rcp ulp, sign of the exp ulp); 0: random
 
 
@@ -533,7 +633,7 @@ def _ulp(x, sign, key):
     return np.where(up, np.nextafter(x, f32(np.inf)), np.nextafter(x, f32(-np.inf))).astype(f32)
 
 
-def backward_hw(c, pname, contrib, final_tau, mode=None, arrays=None):
+def backward_hw(c, pname, contrib, final_tau, mode=None, arrays=None, abs_out=None):
     """``O.draw_backward`` restated in float32 (``mode`` None: bit for bit, tests/test_draw_tile_ref_cpu.py); with a
     ``mode`` the Gaussian is formed as k_draw_bwd forms it (pre-scaled conic, fmaf, exp2), gamma_cur2last is carried as
     the kernel's scalar lq, and the two operations it does NOT round correctly are an ulp off: it recovers the transmittance as tau * v_rcp_f32(1 - alpha') where
@@ -541,7 +641,11 @@ def backward_hw(c, pname, contrib, final_tau, mode=None, arrays=None):
     correctly rounded to the last bit or so.  Both instructions are accurate to ONE ulp, in a direction nobody
     documents; ``mode`` = (sign of the reciprocal's ulp, sign of the exponential's ulp), 0 = a random sign per use.
     The same sign at every use is the systematic drift a 1-ulp instruction is entitled to: over a walk of 120 entries the
-    recovered tau then leaves the float64 one by 120 ulps, which a cancelling dL/dalpha row magnifies."""
+    recovered tau then leaves the float64 one by 120 ulps, which a cancelling dL/dalpha row magnifies.
+    An extras case (-> the four tensors and dz [N]): without a ``mode`` the oracle's walk over the five colours (c, z, 1)
+    with dL/dgamma = (Wi, Wd, Wa - Wi . bg); with one, k_draw_bwd<EXTRA>'s own operations: lq starts at Wi . bg - Wa,
+    dq = fmaf(Wd, z, Wi . c) - lq, dz += Wd w.
+    ``abs_out`` ([N, 2], added to): the sums of |t_x|, |t_y| whose signed sums are dus (tests/absgrad_ref.py)."""
     a = c.arrays if arrays is None else arrays
     policy = POLICIES[pname]
     ls, _, _ = lists(c, pname)
@@ -550,6 +654,10 @@ def backward_hw(c, pname, contrib, final_tau, mode=None, arrays=None):
     dLdg = np.asarray(c.arrays["dloss_dgammas"], f32)
     n = us.shape[0]
     dus = np.zeros((n, 2), f32); dcinv = np.zeros((n, 3), f32); dalpha = np.zeros(n, f32); dcolor = np.zeros((n, 3), f32)
+    x = c.extras
+    if x:
+        zs = np.asarray(a["z"], f32); bg = np.asarray(c.bg, f32); dz = np.zeros(n, f32)
+        Wd, Wa = np.asarray(c.arrays["dloss_ddepth"], f32), np.asarray(c.arrays["dloss_dalpha"], f32)
     if policy.footprint == O.FOOT_BOX:
         bx0, bx1, by0, by1 = O.pixel_box(us, a["areas"], W, H)
     for t, ids in enumerate(ls):
@@ -560,8 +668,13 @@ def backward_hw(c, pname, contrib, final_tau, mode=None, arrays=None):
         tau = np.array(final_tau[y0:y0 + hh, x0:x0 + ww], f32)
         cont = np.asarray(contrib[y0:y0 + hh, x0:x0 + ww])
         dl = dLdg[:, y0:y0 + hh, x0:x0 + ww]
-        gcl = np.zeros((3, hh, ww), f32)
+        gcl = np.zeros((5 if x else 3, hh, ww), f32)
         lq = np.zeros((hh, ww), f32)
+        dlx = dl
+        if x:
+            ld, la = Wd[y0:y0 + hh, x0:x0 + ww], Wa[y0:y0 + hh, x0:x0 + ww]
+            dlx = np.concatenate([dl, ld[None], (la - (dl * bg[:, None, None]).sum(0))[None]]).astype(f32)
+            lq = (((dl[0] * bg[0] + dl[1] * bg[1]).astype(f32) + dl[2] * bg[2]).astype(f32) - la).astype(f32)
         for k in range(int(cont.max()) - 1, -1, -1):
             g = int(ids[k])
             ap, gg, dx, dy = O._alpha_prime(alphas[g], cinv[g], us[g], px, py, policy, f32)
@@ -590,38 +703,57 @@ def backward_hw(c, pname, contrib, final_tau, mode=None, arrays=None):
                 else:
                     tau_n = np.where(act, tau * _ulp(f32(1) / (1 - ap), mode[0], 500000 + 1000 * t + k), tau)
             col = colors[g][:, None, None]
+            colx = np.concatenate([colors[g], f32([zs[g], 1])])[:, None, None] if x else col
             if mode is None:
-                dgam_dap = tau_n[None] * (col - gcl)
-                dl_dap = np.where(act, (dl * dgam_dap).sum(0), 0)
+                dgam_dap = tau_n[None] * (colx - gcl)
+                dl_dap = np.where(act, (dlx * dgam_dap).sum(0), 0)
             else:
                 # k_draw_bwd carries gamma_cur2last as ONE scalar, lq = dL/dgamma . gamma_cur2last: dq = dL/dgamma . c - lq
                 # is a difference of two rounded dot products, where the oracle subtracts the colours first
-                dq = (_fma(dl[2], col[2], _fma(dl[1], col[1], (dl[0] * col[0]).astype(f32))) - lq).astype(f32)
+                dq = _fma(dl[2], col[2], _fma(dl[1], col[1], (dl[0] * col[0]).astype(f32)))
+                if x:
+                    dq = _fma(ld, zs[g], dq)
+                dq = (dq - lq).astype(f32)
                 dl_dap = np.where(act, tau_n * dq, 0).astype(f32)
                 lq = np.where(act, _fma(ap, dq, lq), lq)
             dalpha[g] += (dl_dap * gg).sum()
             dcolor[g] += (np.where(act, ap * tau_n, 0)[None] * dl).sum((1, 2))
+            if x:
+                dz[g] += (np.where(act, ap * tau_n, 0) * ld).sum()
             ci = cinv[g]
-            dus[g, 0] += (dl_dap * (-ci[0] * dx - ci[1] * dy) * ap).sum()
-            dus[g, 1] += (dl_dap * (-ci[1] * dx - ci[2] * dy) * ap).sum()
+            t_x, t_y = dl_dap * (-ci[0] * dx - ci[1] * dy) * ap, dl_dap * (-ci[1] * dx - ci[2] * dy) * ap
+            dus[g, 0] += t_x.sum()
+            dus[g, 1] += t_y.sum()
+            if abs_out is not None:
+                abs_out[g, 0] += np.abs(t_x).sum(); abs_out[g, 1] += np.abs(t_y).sum()
             dcinv[g, 0] += (dl_dap * (-0.5 * ap * dx * dx)).sum()
             dcinv[g, 1] += (dl_dap * (-1.0 * ap * dx * dy)).sum()
             dcinv[g, 2] += (dl_dap * (-0.5 * ap * dy * dy)).sum()
-            gcl = np.where(act[None], ap[None] * col + (1 - ap)[None] * gcl, gcl)
+            gcl = np.where(act[None], ap[None] * colx + (1 - ap)[None] * gcl, gcl)
             tau = tau_n
-    return dus, dcinv, dalpha, dcolor
+    return (dus, dcinv, dalpha, dcolor, dz) if x else (dus, dcinv, dalpha, dcolor)
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name, pname, seed=0):
+@_normalised
+def reference(name, pname, seed=0, extras=False):
     """the float64 result of set ``name`` under policy ``pname``, computed once -> dict: image, contrib, final_tau, the
     four gradient tensors (GRADS), ``diag`` (per-Gaussian hits / clamped / floored counts), ``walked`` [N] (entries
-    between a Gaussian's own and the largest contrib of its tile)"""
-    c = case(name, seed)
+    between a Gaussian's own and the largest contrib of its tile); without ``extras`` also ``dus_abs`` [N, 2], the absolute
+    screen-space gradient (tests/absgrad_ref.py); with ``extras`` the image over the background, ``depth``, ``alpha`` and
+    the five tensors GRADS_X (``dz`` [N])"""
+    c = case(name, seed, True if extras else None)
     ls, rg, gs = lists(c, pname)
-    image, contrib, tau = forward(c, pname)
+    fwd = forward(c, pname)
+    image, contrib, tau = fwd[:3]
     out = dict(image=image, contrib=contrib, final_tau=tau)
-    out.update(zip(GRADS, backward(c, pname, contrib, tau)))
+    out.update(zip(GRADS_X, backward(c, pname, contrib, tau)))
+    if extras:
+        out.update(depth=fwd[3], alpha=fwd[4])
+    else:
+        from tests.absgrad_ref import draw_backward_abs
+        a = c.arrays
+        out["dus_abs"] = draw_backward_abs(W, H, rg, gs, a["us"], a["cinv2ds"], a["alphas"], a["colors"], contrib, tau,
+                                           a["dloss_dgammas"], a["areas"], POLICIES[pname])[1]
     d = {}
     blend(c.arrays, ls, POLICIES[pname], np.float64, diag=d)
     out["diag"] = d
@@ -644,8 +776,8 @@ def _rows(got, ref):
     return np.where(scale == 0, 0.0, np.abs(got - ref).max(1) / np.where(scale == 0, 1.0, scale))
 
 
-@functools.lru_cache(maxsize=None)
-def distances(name, pname, seed=0):
+@_normalised
+def distances(name, pname, seed=0, extras=False):
     """How far the number format and the kernels' legitimate operations move the result, without any kernel -> dict:
     per PIXEL for image (largest of the three channels) and final_tau the largest absolute distance from the float64
     reference of
@@ -662,57 +794,83 @@ def distances(name, pname, seed=0):
           operations (derived log2(alpha), v_exp_f32) an ulp off: k_draw_bwd forms alpha' directly, k_draw by the
           polynomial, so the transmittance the backward divides its way up from belongs to slightly different alpha' --
           a difference that 1 / (1 - alpha') magnifies 100-fold next to the clamp (forward and backward signs opposed)
-    -- what bounds the pair.  ``contrib_equal``: every one of these evaluations gave the reference's contrib."""
-    c = case(name, seed)
-    ref = reference(name, pname, seed)
+    -- what bounds the pair.  ``contrib_equal``: every one of these evaluations gave the reference's contrib.
+    Without ``extras`` also the rows ``dus_abs`` (and ``dus_abs_alone``) of the absolute screen-space gradient, from the
+    same float32 walks ((a), (b) are then ``backward_hw`` without a mode, which IS the float32 ``O.draw_backward``).
+    With ``extras`` (an extras case; z is moved by its ulp in (b) too) also ``depth`` and ``alpha`` per pixel and the rows
+    ``dz``: (a), (b) are the float32 compositions of ``forward`` / ``backward``, (c) - (e) carry the EXTRA kernels' own
+    operations -- cd += w z with two roundings and contracted, alpha = 1 - tau, fmaf(tau, bg, c); fmaf(dL/ddepth, z, ..)."""
+    c = case(name, seed, True if extras else None)
+    ref = reference(name, pname, seed, extras)
     ls, rg, gs = lists(c, pname)
-    d = dict(image=np.zeros((H, W)), final_tau=np.zeros((H, W)), contrib_equal=True)
-    d.update({k: np.zeros(c.n) for k in GRADS})
+    pix = ("image", "final_tau") + (("depth", "alpha") if extras else ())
+    keys = GRADS_X if extras else GRADS + ("dus_abs",)
+    d = dict(contrib_equal=True)
+    d.update({k: np.zeros((H, W)) for k in pix})
+    d.update({k: np.zeros(c.n) for k in keys})
+    bg = c.bg if extras else None
 
-    def take(img, cont, tau):
+    def take(img, cont, tau, depth=None, alpha=None):
         d["contrib_equal"] &= bool(np.array_equal(cont, ref["contrib"]))
         d["image"] = np.maximum(d["image"], np.abs(img.astype(np.float64) - ref["image"]).max(0))
-        d["final_tau"] = np.maximum(d["final_tau"], np.abs(tau.astype(np.float64) - ref["final_tau"]))
+        for k, v in (("final_tau", tau), ("depth", depth), ("alpha", alpha)):
+            if v is not None:
+                d[k] = np.maximum(d[k], np.abs(v.astype(np.float64) - ref[k]))
 
     def rows(grads):
-        for k, g in zip(GRADS, grads):
+        for k, g in zip(keys, grads):
             d[k] = np.maximum(d[k], _rows(g, ref[k]))
+
+    def hw_rows(cont, tau, mode, arrays=None):
+        ab = None if extras else np.zeros((c.n, 2), f32)
+        rows(backward_hw(c, pname, cont, tau, mode, arrays, abs_out=ab) + (() if extras else (ab,)))
 
     for j in range(N_PERT + 1):                                                                     # (a), (b)
         a = c.arrays if j == 0 else perturbed(c.arrays, j)
-        img, cont, tau = forward(c, pname, np.float32, a)
-        take(img, cont, tau)
-        rows(backward(c, pname, cont, tau, np.float32, a))
+        fwd = forward(c, pname, np.float32, a)
+        take(*fwd)
+        cont, tau = fwd[1], fwd[2]
+        if extras:
+            rows(backward(c, pname, cont, tau, np.float32, a))
+        else:
+            hw_rows(cont, tau, None, a)
         if j == 0:                                                                                  # (d)
             for mode in HW_MODES:
-                rows(backward_hw(c, pname, cont, tau, mode))
-    d.update({k + "_alone": d[k].copy() for k in GRADS})
+                hw_rows(cont, tau, mode)
+    d.update({k + "_alone": d[k].copy() for k in keys})
     for fma in (False, True):                                                                       # (c)
-        img, cont, tau = blend(c.arrays, ls, POLICIES[pname], np.float32, poly=True, fma=fma)
-        take(img, cont, tau)
-        rows(backward_hw(c, pname, cont, tau, (0, 0)))
+        fwd = blend(c.arrays, ls, POLICIES[pname], np.float32, poly=True, fma=fma, extras=bg)
+        take(*fwd)
+        hw_rows(fwd[1], fwd[2], (0, 0))
     for hw, modes in ((0, ((0, 0),)), (1, ((1, -1), (-1, -1))), (-1, ((1, 1), (-1, 1)))):             # (e)
-        img, cont, tau = blend(c.arrays, ls, POLICIES[pname], np.float32, poly=True, hw=hw, fma=True)
-        d["contrib_equal"] &= bool(np.array_equal(cont, ref["contrib"]))
+        fwd = blend(c.arrays, ls, POLICIES[pname], np.float32, poly=True, hw=hw, fma=True, extras=bg)
+        d["contrib_equal"] &= bool(np.array_equal(fwd[1], ref["contrib"]))
         for mode in modes:
-            rows(backward_hw(c, pname, cont, tau, mode))
+            hw_rows(fwd[1], fwd[2], mode)
     for v in d.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
     return d
 
 
-def pixel_floor(name, pname, seed=0):
+def pixel_floor(name, pname, seed=0, extras=False):
     """one float32 ulp of a pixel's largest running magnitude per blended entry: 2^-23 (2 + contrib) max(1, max |colour|
-    of the tile's list) -- a count of the roundings of the accumulation, not a measurement"""
-    c = case(name, seed)
-    ref = reference(name, pname, seed)
-    cmax = np.ones((H, W))
+    of the tile's list) -- a count of the roundings of the accumulation, not a measurement.  ``extras``: -> dict, the same
+    form per output: image with the background's magnitude among the colours', final_tau as without extras, depth with
+    max(1, max |z| of the tile's list), alpha with 1"""
+    c = case(name, seed, True if extras else None)
+    ref = reference(name, pname, seed, extras)
+    cmax = np.ones((H, W)); zmax = np.ones((H, W))
     for t, l in enumerate(lists(c, pname)[0]):
         tx, ty, x0, y0, ww, hh = geom(t)
         if len(l):
             cmax[y0:y0 + hh, x0:x0 + ww] = max(1.0, float(np.abs(c.arrays["colors"][l]).max()))
-    return 2.0 ** -23 * (2 + ref["contrib"]) * cmax
+            if extras:
+                zmax[y0:y0 + hh, x0:x0 + ww] = max(1.0, float(np.abs(c.arrays["z"][l]).max()))
+    one = 2.0 ** -23 * (2 + ref["contrib"])
+    if not extras:
+        return one * cmax
+    return dict(image=one * np.maximum(cmax, float(np.abs(c.bg).max())), final_tau=one * cmax, depth=one * zmax, alpha=one)
 
 
 # ------------------------------------------------------------------------------------------------------------ claims
