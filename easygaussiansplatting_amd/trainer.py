@@ -739,6 +739,60 @@ class Trainer:
                              poses[1][int(view_id)].detach(), self.device, id=cam.id, path=cam.path)
             return _features.render(feats, *args, cam, high_shs=high, antialiased=self.antialiased)
 
+    def extract_mesh(self, view_ids: Sequence[int] = None, voxel_size: float = None, bounds=None, trunc: float = None,
+                     min_weight: float = None, color: bool = True, **integrate_kwargs):
+        """-> (vertices [V,3] float32, faces [F,3] int64, colors [V,3] float32 or None): the scene's surface as a triangle
+        mesh (``mesh.TSDFVolume``).  Every view of ``view_ids`` (default: all cameras) is rendered with its
+        depth and opacity maps, forward only, with this trainer's ``antialiased`` and -- with ``pose_opt`` -- the current
+        poses, and fused into one volume with the rendered image as colour; the zero level set is then extracted.
+        ``bounds`` = ((x0, y0, z0), (x1, y1, z1)) defaults to the 1st-99th percentile box of the Gaussian centres padded by
+        the truncation distance, ``voxel_size`` to the longest side of that box / 256, ``trunc`` to 4 voxels,
+        ``min_weight`` to 1; ``integrate_kwargs`` (``alpha_min`` = 0.5, ``near``, ``depth_max``, ``clip_to_frustum``) go to
+        ``TSDFVolume.integrate``.  These defaults are values NOBODY HAS TUNED.  Parameters, gradients and optimizer state
+        are left as they are; every rank that calls this fuses all the views itself."""
+        from . import mesh as _mesh
+        view_ids = list(range(len(self.cams))) if view_ids is None else [int(v) for v in view_ids]
+        p = self.params
+        with torch.no_grad():
+            if bounds is None:
+                pw = p["pws"].detach()
+                n = pw.shape[0]
+                if n == 0:
+                    raise ValueError("extract_mesh needs bounds: the scene has no Gaussian")
+                srt = torch.sort(pw, dim=0).values
+                lo = srt[min(n - 1, int(0.01 * (n - 1)))].double().cpu().numpy()
+                hi = srt[int(math.ceil(0.99 * (n - 1)))].double().cpu().numpy()
+                pad = None
+            else:
+                lo, hi = (np.asarray(b, np.float64).reshape(3) for b in bounds)
+                pad = 0.0
+            if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+                raise ValueError("bounds must be a finite box with a positive extent, got %r, %r" % (lo, hi))
+            voxel = float(voxel_size) if voxel_size is not None else float((hi - lo).max()) / 256.0
+            if not (math.isfinite(voxel) and voxel > 0):
+                raise ValueError("voxel_size must be finite and > 0, got %r" % (voxel_size,))
+            trunc = _mesh.TRUNC_VOXELS * voxel if trunc is None else float(trunc)
+            pad = trunc if pad is None else pad
+            lo, hi = lo - pad, hi + pad
+            dims = tuple(int(math.ceil((h - l) / voxel - 1e-9)) + 1 for l, h in zip(lo, hi))
+            vol = _mesh.TSDFVolume(tuple(lo), voxel, dims, trunc=trunc, color=color, device=self.device)
+            if self.fused_activations:
+                args, fn = (p["pws"], p["low_shs"], p["high_shs"], p["alphas_raw"], p["scales_raw"], p["rots_raw"]), \
+                    GSRawFunction
+            else:
+                args, fn = activate(p), GSFunction
+            opts = RenderOptions(mode=self.mode, depth=True, alpha=True, antialiased=self.antialiased)
+            poses = self.pose_table.poses() if self.pose_table is not None else None
+            us = torch.zeros((p["pws"].shape[0], 2), device=self.device)
+            for v in view_ids:
+                cam = self.cams[v]
+                if poses is not None:
+                    cam = Camera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy, poses[0][v].detach(),
+                                 poses[1][v].detach(), self.device, id=cam.id, path=cam.path)
+                out = fn.apply(*args, us, cam, opts)
+                vol.integrate(out[2], out[3], cam, image=out[0].contiguous() if color else None, **integrate_kwargs)
+            return vol.extract(_mesh.MIN_WEIGHT if min_weight is None else min_weight)
+
     def prune_by_importance(self, score: str = "max", threshold=None, fraction=None, view_ids: Sequence[int] = None,
                             verbose: bool = False):
         """Remove the Gaussians whose ``score`` ("max", "sum" or "hits" of ``importance()``) lies below ``threshold``,

@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""From a saved scene to a triangle mesh: render the depth map of every camera of a COLMAP model, fuse them
+into a TSDF volume, write the zero level set.
+
+    python examples/extract_mesh.py --gs data/final.npy --path /data/tandt/train [--out mesh.ply] [--voxel S]
+                                    [--alpha-min 0.5] [--trunc T] [--min-weight 1] [--depth-max D] [--no-color]
+
+``--gs`` is a checkpoint of ``examples/train.py`` (.npy record array) or a 3DGS .ply; ``--path`` the dataset directory
+(sparse/0/*.bin + images/) whose cameras are used.  alpha_min 0.5, a truncation of 4 voxels and min_weight 1 are
+defaults nobody has tuned.  The mesh is not cleaned: small components are the caller's to remove.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gs", required=True, help="the saved scene (.npy record array or 3DGS .ply)")
+    ap.add_argument("--path", required=True, help="dataset directory (sparse/0/*.bin + images/): the cameras")
+    ap.add_argument("--out", default="mesh.ply")
+    ap.add_argument("--resize", type=float, default=1.0)
+    ap.add_argument("--voxel", type=float, default=None, help="voxel size in world units (default: longest side / 256)")
+    ap.add_argument("--trunc", type=float, default=None, help="truncation distance (default: 4 voxels; untuned)")
+    ap.add_argument("--alpha-min", type=float, default=0.5, help="opacity a pixel needs to count (untuned)")
+    ap.add_argument("--min-weight", type=float, default=1.0, help="weight every corner of a meshed cell needs (untuned)")
+    ap.add_argument("--depth-max", type=float, default=None, help="ignore surface farther than this from a camera")
+    ap.add_argument("--no-color", action="store_true", help="a mesh without vertex colours")
+    a = ap.parse_args()
+
+    from easygaussiansplatting_amd import scene as S
+    from easygaussiansplatting_amd.dataset import GSplatDataset
+    from easygaussiansplatting_amd.gau_io import load_gs
+    from easygaussiansplatting_amd.mesh import save_mesh_ply
+    from easygaussiansplatting_amd.trainer import Trainer
+
+    gs = load_gs(a.gs)
+    ds = GSplatDataset(a.path, resize_rate=a.resize)
+    sc = S.Scene(gs["pw"].copy(), gs["rot"].copy(), gs["scale"].copy(), gs["alpha"].copy(),
+                 gs["sh"].reshape(gs["sh"].shape[0], -1).copy(), None)
+    tr = Trainer(sc, ds.cameras, ds.images, max_steps=1, scene_size=ds.sence_size)
+    vertices, faces, colors = tr.extract_mesh(voxel_size=a.voxel, trunc=a.trunc, min_weight=a.min_weight,
+                                              color=not a.no_color, alpha_min=a.alpha_min, depth_max=a.depth_max)
+    save_mesh_ply(a.out, vertices, faces, colors)
+    print("wrote %s: %d vertices, %d faces from %d views" % (a.out, vertices.shape[0], faces.shape[0], len(ds)))
+
+
+if __name__ == "__main__":
+    main()

@@ -80,6 +80,12 @@ def main():
                     help="the statistic pruned on: largest weight (RadSplat), summed weight (Mini-Splatting), pixels hit")
     ap.add_argument("--prune-threshold", type=float, default=None, help="keep Gaussians whose score is at least this")
     ap.add_argument("--prune-fraction", type=float, default=None, help="drop this share of the Gaussians, lowest score first")
+    ap.add_argument("--mesh", default=None, metavar="OUT.ply",
+                    help="after training, fuse the depth maps of all training views into a TSDF volume and write its "
+                         "zero level set as a triangle mesh (Trainer.extract_mesh, DESIGN §3.19; alpha_min 0.5, "
+                         "truncation 4 voxels, min_weight 1: untuned defaults)")
+    ap.add_argument("--mesh-voxel", type=float, default=None, metavar="S",
+                    help="--mesh: the voxel size in world units (default: the longest side of the scene's box / 256)")
     a = ap.parse_args()
     if a.strategy == "mcmc" and a.cap_max is None:
         ap.error("--strategy mcmc needs --cap-max")
@@ -141,6 +147,11 @@ def main():
         if a.bilagrid:
             tr.save_grids(os.path.join(a.out, "grids.npz"))
         print("Training is finished.")
+        if a.mesh:
+            from easygaussiansplatting_amd.mesh import save_mesh_ply
+            vertices, faces, colors = tr.extract_mesh(voxel_size=a.mesh_voxel)
+            save_mesh_ply(a.mesh, vertices, faces, colors)
+            print("mesh: %d vertices, %d faces -> %s" % (vertices.shape[0], faces.shape[0], a.mesh))
     if world > 1:
         dist.destroy_process_group()
 
