@@ -14,15 +14,26 @@ nothing back, extraction reads one number (the triangle count).
 ``Trainer.extract_mesh`` does the loop over a trainer's cameras.  ``alpha_min`` = 0.5, ``trunc`` = 4 voxels and
 ``min_weight`` = 1 are defaults NOBODY HAS TUNED.  The expected depth sum w z / sum w bleeds at silhouettes (a pixel that
 sees two surfaces reports a depth between them); ``alpha_min`` is the only guard against it here.
+
+A TSDF of splat depth maps carries floaters.  The mesh is cleaned where it already lives, on the GPU (DESIGN §3.20,
+csrc/egs_meshops.hip, libegs_meshops.so; include/egs_meshops.h has every rule): ``connected_components`` (a lock-free
+union-find over vertex connectivity), ``remove_small_components`` (by face count and/or the k largest, with compaction),
+``vertex_normals`` (area weighted, outward), ``smooth_taubin`` and ``clean_mesh``, which chains them.  All of it is
+deterministic bit for bit.  ``lam`` = 0.5, ``mu`` = -0.53 and 10 iterations of the smoothing are Taubin's and Open3D's
+defaults, which nobody has tuned here either.
+
+    V, F, C, N = clean_mesh(*vol.extract(), min_faces=200, normals=True)
+    save_mesh_ply_with_normals("mesh.ply", V, F, C, N)
 """
 from __future__ import annotations
 
+import collections
 import math
 
 import numpy as np
 import torch
 
-from . import _tsdflib
+from . import _meshopslib, _tsdflib
 from ._host import _lib_on, _ptr, _stream
 from .depthloss import _plane
 from .normalloss import _intrinsics, _planes3
@@ -207,6 +218,188 @@ class TSDFVolume:
         return V, faces, C
 
 
+# -------------------------------------------------------------------------------------------------------- mesh cleaning
+TAUBIN_LAMBDA = 0.5       # Taubin's pair, Open3D's defaults; untuned here
+TAUBIN_MU = -0.53
+TAUBIN_ITERATIONS = 10
+
+Components = collections.namedtuple("Components", ["label", "comp_faces", "comp_verts"])
+
+
+def _count(value, name, minimum=0):
+    try:
+        ok = int(value) == value and int(value) >= minimum
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok or int(value) > _meshopslib.MAX_COUNT:
+        raise ValueError("%s must be an integer in [%d, 2^31), got %r" % (name, minimum, value))
+    return int(value)
+
+
+def _faces(faces, n_vertices, check):
+    """``faces`` as a contiguous [F,3] int64 tensor on the GPU; with ``check`` one ``aminmax`` (a readback) makes sure every
+    index lies in [0, n_vertices)"""
+    if not isinstance(faces, torch.Tensor):
+        raise TypeError("faces must be a torch.Tensor, got %s" % type(faces).__name__)
+    if faces.dtype != torch.int64:
+        raise ValueError("faces must be torch.int64, got %s" % (faces.dtype,))
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces must have shape [F, 3], got %s" % (list(faces.shape),))
+    if faces.shape[0] > _meshopslib.MAX_COUNT:
+        raise ValueError("a mesh takes fewer than 2^31 faces, got %d" % faces.shape[0])
+    if not faces.is_cuda:
+        raise ValueError("faces must live on the GPU (got device %s)" % (faces.device,))
+    f = faces.detach().contiguous()
+    if check and f.shape[0] > 0:
+        lo, hi = torch.stack(torch.aminmax(f)).tolist()
+        if lo < 0 or hi >= n_vertices:
+            raise ValueError("faces index %d vertices, found an index outside (min %d, max %d)" % (n_vertices, lo, hi))
+    return f
+
+
+def _rows3(t, name, like=None):
+    """``t`` as a contiguous [V,3] float32 tensor, with the shape and device of ``like`` if given"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != torch.float32:
+        raise ValueError("%s must be torch.float32, got %s" % (name, t.dtype))
+    if t.dim() != 2 or t.shape[1] != 3 or (like is not None and t.shape[0] != like.shape[0]):
+        raise ValueError("%s must have shape [%s, 3], got %s" % (name, "V" if like is None else like.shape[0],
+                                                                 list(t.shape)))
+    if t.shape[0] > _meshopslib.MAX_COUNT:
+        raise ValueError("a mesh takes fewer than 2^31 vertices, got %d" % t.shape[0])
+    if like is not None and t.device != like.device:
+        raise ValueError("%s lives on %s, vertices on %s" % (name, t.device, like.device))
+    return t.detach().contiguous()
+
+
+def _mesh_args(vertices, faces, check):
+    v = _rows3(vertices, "vertices")
+    f = _faces(faces, v.shape[0], check)
+    if f.device != v.device:
+        raise ValueError("faces live on %s, vertices on %s" % (f.device, v.device))
+    _lib_on(v)
+    return v, f
+
+
+def _incidence(f, n_vertices):
+    """the vertex-to-face incidence in CSR form (include/egs_meshops.h): -> (row_start [V+1] int64, rows [3F] int64), the
+    entries 3 f + k of a vertex in ascending order: a stable sort of the flattened faces"""
+    flat = f.reshape(-1)
+    keys, rows = torch.sort(flat, stable=True)
+    row_start = torch.searchsorted(keys, torch.arange(n_vertices + 1, dtype=torch.int64, device=f.device))
+    return row_start.contiguous(), rows.contiguous()
+
+
+def connected_components(faces, n_vertices, check=True):
+    """-> Components(label, comp_faces, comp_verts), three [n_vertices] int32 tensors on the device.  Two vertices are
+    connected when a face holds both (vertex connectivity).  ``label[v]`` is the smallest vertex index of v's component;
+    ``comp_faces[r]`` and ``comp_verts[r]`` are the numbers of faces and vertices of the component whose representative
+    (``label[r] == r``) is r, and 0 at every other index.  A face belongs to the component of its first vertex; a vertex
+    no face names is a component without a face.  A lock-free union-find and integer sums: the same bits on every run.
+    ``check`` = False skips the index-range test (one ``aminmax`` readback); the kernels skip a face with an index
+    outside [0, n_vertices) either way."""
+    n = _count(n_vertices, "n_vertices")
+    f = _faces(faces, n, check)
+    _lib_on(f)
+    lib = _meshopslib.load()
+    out = [torch.empty(n, dtype=torch.int32, device=f.device) for _ in range(3)]
+    _meshopslib.check(lib.egs_meshops_components(n, f.shape[0], _ptr(f), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), 0,
+                                                 _stream()))
+    return Components(*out)
+
+
+def remove_small_components(vertices, faces, colors=None, min_faces=None, keep_largest=None, normals=None, check=True):
+    """-> (vertices', faces', colors' or None, normals' or None) without the small components.  A component is kept when it
+    has at least ``min_faces`` faces (if given) and is among the ``keep_largest`` components with the most faces (if
+    given; ties go to the smaller label, i.e. the smaller first vertex index); at least one of the two must be given.
+    Components without a face are always dropped, which removes unreferenced vertices.  Kept vertices and faces keep
+    their relative order, face indices are rewritten, colours and normals travel with their vertices bit for bit,
+    degenerate faces are left as they are.  One readback: the two kept counts, in a single copy (and the ``aminmax`` of
+    ``check``)."""
+    if min_faces is None and keep_largest is None:
+        raise ValueError("give min_faces, keep_largest or both")
+    min_faces = 0 if min_faces is None else _count(min_faces, "min_faces")
+    k = None if keep_largest is None else _count(keep_largest, "keep_largest", 1)
+    v, f = _mesh_args(vertices, faces, check)
+    c = None if colors is None else _rows3(colors, "colors", v)
+    nrm = None if normals is None else _rows3(normals, "normals", v)
+    lib = _meshopslib.load()
+    dev = v.device
+    V, F = v.shape[0], f.shape[0]
+    comp = connected_components(f, V, check=False)
+    rank = None
+    if k is not None:
+        order = torch.sort(comp.comp_faces, descending=True, stable=True).indices      # more faces first, then label
+        rank = torch.empty(V, dtype=torch.int32, device=dev)
+        rank[order] = torch.arange(V, dtype=torch.int32, device=dev)
+    vkeep = torch.empty(V, dtype=torch.int32, device=dev)
+    fkeep = torch.empty(F, dtype=torch.int32, device=dev)
+    _meshopslib.check(lib.egs_meshops_keep_flags(V, F, _ptr(f), _ptr(comp.label), _ptr(comp.comp_faces), _ptr(rank),
+                                                 min_faces, 0 if k is None else k, _ptr(vkeep), _ptr(fkeep), 0, _stream()))
+    vscan = torch.cumsum(vkeep, 0, dtype=torch.int64)
+    fscan = torch.cumsum(fkeep, 0, dtype=torch.int64)
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    Vk, Fk = torch.cat([vscan[-1:] if V else zero, fscan[-1:] if F else zero]).tolist()      # the one readback
+    ov = torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+    of = torch.empty((Fk, 3), dtype=torch.int64, device=dev)
+    oc = None if c is None else torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+    on = None if nrm is None else torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+    _meshopslib.check(lib.egs_meshops_compact(V, F, _ptr(v), _ptr(c), _ptr(nrm), _ptr(f), _ptr(vkeep), _ptr(fkeep),
+                                              _ptr(vscan), _ptr(fscan), Vk, Fk, _ptr(ov), _ptr(oc), _ptr(on), _ptr(of), 0,
+                                              _stream()))
+    return ov, of, oc, on
+
+
+def vertex_normals(vertices, faces, check=True):
+    """-> [V,3] float32: the area-weighted vertex normals, S / |S| with S the sum of (b - a) x (c - a) over a vertex's
+    faces -- outward for a mesh of ``TSDFVolume.extract``.  Summed in double in (face, corner) order by one thread per
+    vertex and rounded once: bitwise reproducible.  (0, 0, 0) where |S| is 0 or not finite or the vertex has no face."""
+    v, f = _mesh_args(vertices, faces, check)
+    lib = _meshopslib.load()
+    row_start, rows = _incidence(f, v.shape[0])
+    out = torch.empty_like(v)
+    _meshopslib.check(lib.egs_meshops_vertex_normals(v.shape[0], f.shape[0], _ptr(v), _ptr(f), _ptr(row_start), _ptr(rows),
+                                                     _ptr(out), 0, _stream()))
+    return out
+
+
+def smooth_taubin(vertices, faces, iterations=TAUBIN_ITERATIONS, lam=TAUBIN_LAMBDA, mu=TAUBIN_MU, check=True):
+    """-> the smoothed vertices [V,3] float32; the input is not modified.  Each iteration is a ``lam`` step and a ``mu``
+    step of p' = p + s (m - p), m being the face umbrella of p: the mean of q + r over the other two vertices of every
+    incident face, halved (the uniform umbrella on a closed manifold; at a boundary interior neighbours weigh double).
+    Double sums in (face, corner) order, one rounding per step; a vertex without a face does not move.  ``lam`` = 0.5,
+    ``mu`` = -0.53 and 10 iterations are Taubin's and Open3D's defaults, which nobody has tuned here."""
+    iterations = _count(iterations, "iterations")
+    lam, mu = float(lam), float(mu)
+    if not (math.isfinite(lam) and math.isfinite(mu)):
+        raise ValueError("lam and mu must be finite, got %r, %r" % (lam, mu))
+    v, f = _mesh_args(vertices, faces, check)
+    lib = _meshopslib.load()
+    row_start, rows = _incidence(f, v.shape[0])
+    out = torch.empty_like(v)
+    tmp = torch.empty_like(v) if iterations > 0 else None
+    _meshopslib.check(lib.egs_meshops_taubin(v.shape[0], f.shape[0], _ptr(v), _ptr(f), _ptr(row_start), _ptr(rows),
+                                             iterations, lam, mu, _ptr(out), _ptr(tmp), 0, _stream()))
+    return out
+
+
+def clean_mesh(vertices, faces, colors=None, min_faces=None, keep_largest=None, smooth_iterations=0, normals=False,
+               lam=TAUBIN_LAMBDA, mu=TAUBIN_MU, check=True):
+    """-> (vertices, faces, colors or None, normals or None): ``remove_small_components`` (if ``min_faces`` or
+    ``keep_largest`` is given), then ``smooth_taubin`` (if ``smooth_iterations`` > 0), then -- with ``normals`` -- the
+    ``vertex_normals`` of the result."""
+    smooth_iterations = _count(smooth_iterations, "smooth_iterations")
+    v, f = _mesh_args(vertices, faces, check)
+    c = None if colors is None else _rows3(colors, "colors", v)
+    if min_faces is not None or keep_largest is not None:
+        v, f, c, _ = remove_small_components(v, f, c, min_faces=min_faces, keep_largest=keep_largest, check=False)
+    if smooth_iterations > 0:
+        v = smooth_taubin(v, f, smooth_iterations, lam, mu, check=False)
+    n = vertex_normals(v, f, check=False) if normals else None
+    return v, f, c, n
+
+
 # ------------------------------------------------------------------------------------------------------------ PLY files
 def _np(t, dtype):
     return np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype)
@@ -214,7 +407,14 @@ def _np(t, dtype):
 
 def save_mesh_ply(path, vertices, faces, colors=None):
     """Binary little-endian PLY of an indexed triangle mesh: vertices [V,3] float32, faces [F,3] integers, optional
-    colors [V,3] in [0, 1] written as uchar red green blue.  numpy alone, no ``plyfile``."""
+    colors [V,3] in [0, 1] written as uchar red green blue.  numpy alone, no ``plyfile``.
+    ``save_mesh_ply_with_normals`` writes vertex normals as well."""
+    save_mesh_ply_with_normals(path, vertices, faces, colors, None)
+
+
+def save_mesh_ply_with_normals(path, vertices, faces, colors=None, normals=None):
+    """``save_mesh_ply`` with optional normals [V,3] float32, written as float nx ny nz after x y z (the order MeshLab and
+    Open3D write); without ``normals`` the file is ``save_mesh_ply``'s byte for byte."""
     v, f = _np(vertices, np.float32), _np(faces, np.int64)
     if v.ndim != 2 or v.shape[1] != 3:
         raise ValueError("vertices must have shape [V, 3], got %s" % (list(v.shape),))
@@ -227,6 +427,12 @@ def save_mesh_ply(path, vertices, faces, colors=None):
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v), "property float x",
             "property float y", "property float z"]
+    if normals is not None:
+        n = _np(normals, np.float32)
+        if n.shape != v.shape:
+            raise ValueError("normals must have shape %s, got %s" % (list(v.shape), list(n.shape)))
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        head += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         c = _np(colors, np.float32)
         if c.shape != v.shape:
@@ -236,6 +442,8 @@ def save_mesh_ply(path, vertices, faces, colors=None):
     head += ["element face %d" % len(f), "property list uchar int vertex_indices", "end_header"]
     vrec = np.empty(len(v), dtype=fields)
     vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vrec["nx"], vrec["ny"], vrec["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if colors is not None:
         c8 = np.clip(np.rint(np.nan_to_num(c) * 255.0), 0, 255).astype(np.uint8)
         vrec["red"], vrec["green"], vrec["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
@@ -248,10 +456,11 @@ def save_mesh_ply(path, vertices, faces, colors=None):
         fh.write(frec.tobytes())
 
 
-def load_mesh_ply(path):
+def load_mesh_ply(path, with_normals=False):
     """-> (vertices [V,3] float32, faces [F,3] int64, colors [V,3] float32 in [0, 1] or None) numpy arrays of a file
-    ``save_mesh_ply`` wrote (binary little-endian, float x y z, optional uchar red green blue, triangles as
-    ``uchar int`` lists)."""
+    ``save_mesh_ply`` or ``save_mesh_ply_with_normals`` wrote (binary little-endian, float x y z, optional float nx ny
+    nz, optional uchar red green blue, triangles as ``uchar int`` lists).  With ``with_normals`` a fourth value: the
+    normals [V,3] float32, or None if the file has none."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header\n")
@@ -274,11 +483,13 @@ def load_mesh_ply(path):
         elif p[:1] == ["property"] and element in props:
             props[element].append(p[1:])
     names = [p[-1] for p in props["vertex"]]
-    has_color = names == ["x", "y", "z", "red", "green", "blue"]
-    if nv is None or nf is None or not (names == ["x", "y", "z"] or has_color) or \
+    xyz, nrm, rgb = ["x", "y", "z"], ["nx", "ny", "nz"], ["red", "green", "blue"]
+    has_normals = names[3:6] == nrm
+    has_color = names[-3:] == rgb
+    if nv is None or nf is None or names != xyz + (nrm if has_normals else []) + (rgb if has_color else []) or \
             props["face"] != [["list", "uchar", "int", "vertex_indices"]]:
         raise ValueError("%s: not the layout save_mesh_ply writes" % path)
-    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if has_color else [])
+    fields = [(k, "<f4") for k in xyz + (nrm if has_normals else [])] + ([(k, "u1") for k in rgb] if has_color else [])
     body = end + len(b"end_header\n")
     vrec = np.frombuffer(data, dtype=fields, count=nv, offset=body)
     frec = np.frombuffer(data, dtype=[("n", "u1"), ("i", "<i4", (3,))], count=nf, offset=body + vrec.nbytes)
@@ -286,4 +497,7 @@ def load_mesh_ply(path):
         raise ValueError("%s: a face that is not a triangle" % path)
     v = np.stack([vrec["x"], vrec["y"], vrec["z"]], 1).astype(np.float32)
     c = np.stack([vrec["red"], vrec["green"], vrec["blue"]], 1).astype(np.float32) / np.float32(255) if has_color else None
-    return v, frec["i"].astype(np.int64), c
+    if not with_normals:
+        return v, frec["i"].astype(np.int64), c
+    n = np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], 1).astype(np.float32) if has_normals else None
+    return v, frec["i"].astype(np.int64), c, n

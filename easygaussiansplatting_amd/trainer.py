@@ -740,7 +740,8 @@ class Trainer:
             return _features.render(feats, *args, cam, high_shs=high, antialiased=self.antialiased)
 
     def extract_mesh(self, view_ids: Sequence[int] = None, voxel_size: float = None, bounds=None, trunc: float = None,
-                     min_weight: float = None, color: bool = True, **integrate_kwargs):
+                     min_weight: float = None, color: bool = True, min_component_faces: int = None,
+                     keep_largest: int = None, smooth_iterations: int = 0, **integrate_kwargs):
         """-> (vertices [V,3] float32, faces [F,3] int64, colors [V,3] float32 or None): the scene's surface as a triangle
         mesh (``mesh.TSDFVolume``).  Every view of ``view_ids`` (default: all cameras) is rendered with its
         depth and opacity maps, forward only, with this trainer's ``antialiased`` and -- with ``pose_opt`` -- the current
@@ -749,7 +750,12 @@ class Trainer:
         the truncation distance, ``voxel_size`` to the longest side of that box / 256, ``trunc`` to 4 voxels,
         ``min_weight`` to 1; ``integrate_kwargs`` (``alpha_min`` = 0.5, ``near``, ``depth_max``, ``clip_to_frustum``) go to
         ``TSDFVolume.integrate``.  These defaults are values NOBODY HAS TUNED.  Parameters, gradients and optimizer state
-        are left as they are; every rank that calls this fuses all the views itself."""
+        are left as they are; every rank that calls this fuses all the views itself.
+
+        Cleaning (``mesh.clean_mesh``), all off by default -- a default call returns what it always did,
+        bit for bit: ``min_component_faces`` drops the connected components with fewer faces (the floaters a TSDF of
+        splat depth maps carries), ``keep_largest`` = k keeps only the k components with the most faces,
+        ``smooth_iterations`` > 0 then runs that many Taubin iterations (lambda 0.5, mu -0.53: untuned too)."""
         from . import mesh as _mesh
         view_ids = list(range(len(self.cams))) if view_ids is None else [int(v) for v in view_ids]
         p = self.params
@@ -791,7 +797,12 @@ class Trainer:
                                  poses[1][v].detach(), self.device, id=cam.id, path=cam.path)
                 out = fn.apply(*args, us, cam, opts)
                 vol.integrate(out[2], out[3], cam, image=out[0].contiguous() if color else None, **integrate_kwargs)
-            return vol.extract(_mesh.MIN_WEIGHT if min_weight is None else min_weight)
+            V, F, C = vol.extract(_mesh.MIN_WEIGHT if min_weight is None else min_weight)
+            if min_component_faces is not None or keep_largest is not None or smooth_iterations:
+                # (extract guarantees the index range: no aminmax readback)
+                V, F, C, _ = _mesh.clean_mesh(V, F, C, min_faces=min_component_faces, keep_largest=keep_largest,
+                                              smooth_iterations=smooth_iterations, check=False)
+            return V, F, C
 
     def prune_by_importance(self, score: str = "max", threshold=None, fraction=None, view_ids: Sequence[int] = None,
                             verbose: bool = False):

@@ -4,10 +4,14 @@ into a TSDF volume, write the zero level set.
 
     python examples/extract_mesh.py --gs data/final.npy --path /data/tandt/train [--out mesh.ply] [--voxel S]
                                     [--alpha-min 0.5] [--trunc T] [--min-weight 1] [--depth-max D] [--no-color]
+                                    [--min-component-faces N] [--keep-largest K] [--smooth N] [--normals]
 
 ``--gs`` is a checkpoint of ``examples/train.py`` (.npy record array) or a 3DGS .ply; ``--path`` the dataset directory
 (sparse/0/*.bin + images/) whose cameras are used.  alpha_min 0.5, a truncation of 4 voxels and min_weight 1 are
-defaults nobody has tuned.  The mesh is not cleaned: small components are the caller's to remove.
+defaults nobody has tuned.  The mesh is cleaned on the GPU when asked: ``--min-component-faces`` and
+``--keep-largest`` drop the floaters (connected components by face count), ``--smooth`` runs Taubin iterations (lambda 0.5,
+mu -0.53: untuned as well), ``--normals`` writes area-weighted vertex normals.  Without these flags the mesh is written as
+extracted.
 """
 import argparse
 import os
@@ -28,12 +32,17 @@ def main():
     ap.add_argument("--min-weight", type=float, default=1.0, help="weight every corner of a meshed cell needs (untuned)")
     ap.add_argument("--depth-max", type=float, default=None, help="ignore surface farther than this from a camera")
     ap.add_argument("--no-color", action="store_true", help="a mesh without vertex colours")
+    ap.add_argument("--min-component-faces", type=int, default=None, metavar="N",
+                    help="drop the connected components with fewer than N faces")
+    ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K components with the most faces")
+    ap.add_argument("--smooth", type=int, default=0, metavar="N", help="Taubin smoothing iterations (untuned)")
+    ap.add_argument("--normals", action="store_true", help="write vertex normals (nx ny nz)")
     a = ap.parse_args()
 
     from easygaussiansplatting_amd import scene as S
     from easygaussiansplatting_amd.dataset import GSplatDataset
     from easygaussiansplatting_amd.gau_io import load_gs
-    from easygaussiansplatting_amd.mesh import save_mesh_ply
+    from easygaussiansplatting_amd.mesh import save_mesh_ply_with_normals, vertex_normals
     from easygaussiansplatting_amd.trainer import Trainer
 
     gs = load_gs(a.gs)
@@ -42,8 +51,11 @@ def main():
                  gs["sh"].reshape(gs["sh"].shape[0], -1).copy(), None)
     tr = Trainer(sc, ds.cameras, ds.images, max_steps=1, scene_size=ds.sence_size)
     vertices, faces, colors = tr.extract_mesh(voxel_size=a.voxel, trunc=a.trunc, min_weight=a.min_weight,
-                                              color=not a.no_color, alpha_min=a.alpha_min, depth_max=a.depth_max)
-    save_mesh_ply(a.out, vertices, faces, colors)
+                                              color=not a.no_color, min_component_faces=a.min_component_faces,
+                                              keep_largest=a.keep_largest, smooth_iterations=a.smooth,
+                                              alpha_min=a.alpha_min, depth_max=a.depth_max)
+    normals = vertex_normals(vertices, faces, check=False) if a.normals else None
+    save_mesh_ply_with_normals(a.out, vertices, faces, colors, normals)
     print("wrote %s: %d vertices, %d faces from %d views" % (a.out, vertices.shape[0], faces.shape[0], len(ds)))
 
 

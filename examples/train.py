@@ -86,6 +86,8 @@ def main():
                          "truncation 4 voxels, min_weight 1: untuned defaults)")
     ap.add_argument("--mesh-voxel", type=float, default=None, metavar="S",
                     help="--mesh: the voxel size in world units (default: the longest side of the scene's box / 256)")
+    ap.add_argument("--mesh-min-faces", type=int, default=None, metavar="N",
+                    help="--mesh: drop the connected components (floaters) with fewer than N faces (DESIGN §3.20)")
     a = ap.parse_args()
     if a.strategy == "mcmc" and a.cap_max is None:
         ap.error("--strategy mcmc needs --cap-max")
@@ -149,7 +151,7 @@ def main():
         print("Training is finished.")
         if a.mesh:
             from easygaussiansplatting_amd.mesh import save_mesh_ply
-            vertices, faces, colors = tr.extract_mesh(voxel_size=a.mesh_voxel)
+            vertices, faces, colors = tr.extract_mesh(voxel_size=a.mesh_voxel, min_component_faces=a.mesh_min_faces)
             save_mesh_ply(a.mesh, vertices, faces, colors)
             print("mesh: %d vertices, %d faces -> %s" % (vertices.shape[0], faces.shape[0], a.mesh))
     if world > 1:
