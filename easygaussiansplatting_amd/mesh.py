@@ -24,6 +24,15 @@ defaults, which nobody has tuned here either.
 
     V, F, C, N = clean_mesh(*vol.extract(), min_faces=200, normals=True)
     save_mesh_ply_with_normals("mesh.ply", V, F, C, N)
+
+Marching tetrahedra on a 256^3 lattice leave about 0.9 M triangles for one object.  ``simplify_vertex_clustering`` (DESIGN
+§3.21, csrc/egs_simplify.hip, libegs_simplify.so; include/egs_simplify.h has every rule) decimates the mesh on the GPU:
+every cell of a uniform grid becomes one vertex, placed where it minimises the squared distance to the planes of the faces
+that touched the cell (Lindstrom's scheme, Open3D's ``simplify_vertex_clustering`` with ``Quadric`` contraction); collapsed
+and duplicate faces are dropped.  Deterministic bit for bit like the rest.  The regulariser of the placement, 1e-3, is
+untuned: nobody has tuned it here.  Vertex clustering does NOT preserve topology: a closed manifold may come out with a few
+opposite face pairs and another Euler characteristic.  ``clean_mesh(..., simplify_cell=...)`` runs it between the smoothing
+and the normals.
 """
 from __future__ import annotations
 
@@ -33,7 +42,7 @@ import math
 import numpy as np
 import torch
 
-from . import _meshopslib, _tsdflib
+from . import _meshopslib, _simplifylib, _tsdflib
 from ._host import _lib_on, _ptr, _stream
 from .depthloss import _plane
 from .normalloss import _intrinsics, _planes3
@@ -384,18 +393,154 @@ def smooth_taubin(vertices, faces, iterations=TAUBIN_ITERATIONS, lam=TAUBIN_LAMB
     return out
 
 
+PLACEMENTS = {"quadric": _simplifylib.PLACE_QUADRIC, "mean": _simplifylib.PLACE_MEAN}
+
+
+def _cell_size(value, name="cell_size"):
+    try:
+        cell = float(value)
+    except (TypeError, ValueError):
+        cell = float("nan")
+    if not (math.isfinite(cell) and cell > 0):
+        raise ValueError("%s must be a finite number > 0, got %r" % (name, value))
+    return cell
+
+
+def _placement(value, name="placement"):
+    if value not in PLACEMENTS:
+        raise ValueError("%s must be 'quadric' or 'mean', got %r" % (name, value))
+    return PLACEMENTS[value]
+
+
+def _origin(value):
+    try:
+        origin = tuple(float(x) for x in value)
+    except (TypeError, ValueError):
+        origin = ()
+    if len(origin) != 3 or not all(math.isfinite(x) for x in origin):
+        raise ValueError("origin must be three finite numbers or None, got %r" % (value,))
+    return origin
+
+
+def simplify_vertex_clustering(vertices, faces, colors=None, cell_size=None, origin=None, placement="quadric", check=True,
+                               return_info=False):
+    """-> (vertices', faces', colors' or None): vertex-clustering simplification (include/egs_simplify.h has every rule).
+    The vertices that fall into one cell of the uniform grid (``origin`` + ``cell_size`` x integers; ``origin`` = None: the
+    bounding box minimum) become one vertex.  ``placement`` = "quadric" puts it where it minimises the summed squared
+    distance to the planes of the faces that touched the cell (area weighted, regularised towards the cell mean with the
+    weight 1e-3 of the quadric's trace -- a value nobody has tuned here -- and clamped to the cell); "mean" takes the mean
+    of the cell's vertices.  The colour is the mean.  A face two of whose corners fall into one cell is dropped; of faces on
+    the same three cells in the same orientation the first stays (opposite orientations are different faces: both stay);
+    cells no kept face names are dropped.  Kept faces keep their order, vertices come in ascending cell key (x fastest).
+    Topology is NOT preserved.  Sums in double in a fixed order, no float atomic: the same bits on every run.
+
+    ``check`` makes sure every face index lies in [0, V) (the kernels skip such a face either way).  Vertices must be
+    finite, ``origin`` <= the bounding box minimum and the extent below 2^21 cells per axis: ValueError otherwise.
+    At most three readbacks: the bounding box (with it the finite check, the 2^21 check and the index check, in one copy),
+    the cluster count (``torch.unique``) and the two kept counts in one copy.  ``return_info`` adds a dict -- ``clusters``,
+    ``placed_mean``, ``placed_solved``, ``placed_clamped``, ``placed_no_face``, ``faces_degenerate``, ``faces_duplicate`` -- at
+    the cost of one more readback."""
+    if cell_size is None:
+        raise ValueError("cell_size must be a finite number > 0, got None")
+    cell = _cell_size(cell_size)
+    place = _placement(placement)
+    org = None if origin is None else _origin(origin)
+    v, f = _mesh_args(vertices, faces, False)
+    c = None if colors is None else _rows3(colors, "colors", v)
+    dev = v.device
+    V, F = v.shape[0], f.shape[0]
+    empty = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev),
+             None if c is None else torch.empty((0, 3), dtype=torch.float32, device=dev))
+    info = dict(clusters=0, placed_mean=0, placed_solved=0, placed_clamped=0, placed_no_face=0, faces_degenerate=F,
+                faces_duplicate=0)
+    if V == 0:
+        return empty + (info,) if return_info else empty
+    # readback 1: the bounding box, and with check the range of the face indices (exact in double: |index| < 2^53 or refused)
+    lo, hi = torch.aminmax(v.double(), dim=0)
+    parts = [lo, hi]
+    if check and F > 0:
+        parts.append(torch.stack(torch.aminmax(f)).clamp(-(1 << 52), 1 << 52).double())
+    box = torch.cat(parts).tolist()
+    if not all(math.isfinite(x) for x in box[:6]):
+        raise ValueError("vertices must be finite (bounding box %r .. %r)" % (box[:3], box[3:6]))
+    if len(box) > 6 and (box[6] < 0 or box[7] >= V):
+        raise ValueError("faces index %d vertices, found an index outside (min %d, max %d)" % (V, box[6], box[7]))
+    if org is None:
+        org = tuple(box[:3])
+    if any(o > m for o, m in zip(org, box[:3])):
+        raise ValueError("origin %r must not exceed the bounding box minimum %r" % (org, tuple(box[:3])))
+    if any(math.floor((m - o) / cell) >= (1 << _simplifylib.KEY_BITS) for o, m in zip(org, box[3:6])):
+        raise ValueError("cell_size %r: the mesh spans 2^%d cells or more from the origin" % (cell_size, _simplifylib.KEY_BITS))
+    lib = _simplifylib.load()
+    S = _stream()
+    keys = torch.empty(V, dtype=torch.int64, device=dev)
+    _simplifylib.check(lib.egs_simplify_keys(V, _ptr(v), *org, cell, _ptr(keys), 0, S))
+    uniq, cluster = torch.unique(keys, return_inverse=True)          # readback 2 (torch's): the cluster count
+    cluster = cluster.contiguous()
+    Vc = uniq.shape[0]
+    srt, members = torch.sort(cluster, stable=True)                    # members in ascending vertex index
+    member_start = torch.searchsorted(srt, torch.arange(Vc + 1, dtype=torch.int64, device=dev)).contiguous()
+    members = members.contiguous()
+    quadrics = None
+    if place == _simplifylib.PLACE_QUADRIC:                            # the two-pass form: per-vertex partials first
+        row_start, rows = _incidence(f, V) if F > 0 else (None, None)
+        quadrics = torch.empty((V, 9), dtype=torch.float64, device=dev)
+        _simplifylib.check(lib.egs_simplify_vertex_quadrics(V, F, _ptr(v), _ptr(f), _ptr(row_start), _ptr(rows), _ptr(keys),
+                                                            *org, cell, _ptr(quadrics), 0, S))
+    pos = torch.empty((Vc, 3), dtype=torch.float32, device=dev)
+    col = None if c is None else torch.empty((Vc, 3), dtype=torch.float32, device=dev)
+    placed = torch.empty(Vc, dtype=torch.int32, device=dev)
+    _simplifylib.check(lib.egs_simplify_clusters(V, F, Vc, _ptr(v), _ptr(c), _ptr(keys), _ptr(member_start), _ptr(members),
+                                                 _ptr(quadrics), None, None, None, *org, cell, place, _ptr(pos), _ptr(col),
+                                                 _ptr(placed), 0, S))
+    rot = torch.empty((F, 3), dtype=torch.int64, device=dev)
+    valid = torch.empty(F, dtype=torch.int32, device=dev)
+    key_hi = torch.empty(F, dtype=torch.int64, device=dev)
+    key_lo = torch.empty(F, dtype=torch.int64, device=dev)
+    _simplifylib.check(lib.egs_simplify_remap_faces(V, F, Vc, _ptr(f), _ptr(cluster), _ptr(rot), _ptr(valid), _ptr(key_hi),
+                                                    _ptr(key_lo), 0, S))
+    order = torch.sort(key_lo, stable=True).indices                    # (key_hi, key_lo) ascending, ties by face index
+    order = order[torch.sort(key_hi[order], stable=True).indices].contiguous()
+    fkeep = torch.empty(F, dtype=torch.int32, device=dev)
+    ckeep = torch.empty(Vc, dtype=torch.int32, device=dev)
+    _simplifylib.check(lib.egs_simplify_keep_flags(F, Vc, _ptr(order), _ptr(rot), _ptr(valid), _ptr(key_hi), _ptr(key_lo),
+                                                   _ptr(fkeep), _ptr(ckeep), 0, S))
+    vscan = torch.cumsum(ckeep, 0, dtype=torch.int64)
+    fscan = torch.cumsum(fkeep, 0, dtype=torch.int64)
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    Vk, Fk = torch.cat([vscan[-1:], fscan[-1:] if F else zero]).tolist()      # readback 3: the two kept counts
+    ov = torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+    of = torch.empty((Fk, 3), dtype=torch.int64, device=dev)
+    oc = None if c is None else torch.empty((Vk, 3), dtype=torch.float32, device=dev)
+    _meshopslib.check(_meshopslib.load().egs_meshops_compact(Vc, F, _ptr(pos), _ptr(col), None, _ptr(rot), _ptr(ckeep),
+                                                             _ptr(fkeep), _ptr(vscan), _ptr(fscan), Vk, Fk, _ptr(ov),
+                                                             _ptr(oc), None, _ptr(of), 0, S))
+    if not return_info:
+        return ov, of, oc
+    counts = torch.cat([torch.bincount(placed.clamp(0, 3), minlength=4), valid.sum(dtype=torch.int64).reshape(1)]).tolist()
+    info = dict(clusters=Vc, placed_mean=counts[0], placed_solved=counts[1], placed_clamped=counts[2],
+                placed_no_face=counts[3], faces_degenerate=F - counts[4], faces_duplicate=counts[4] - Fk)
+    return ov, of, oc, info
+
+
 def clean_mesh(vertices, faces, colors=None, min_faces=None, keep_largest=None, smooth_iterations=0, normals=False,
-               lam=TAUBIN_LAMBDA, mu=TAUBIN_MU, check=True):
+               lam=TAUBIN_LAMBDA, mu=TAUBIN_MU, check=True, simplify_cell=None, simplify_placement="quadric"):
     """-> (vertices, faces, colors or None, normals or None): ``remove_small_components`` (if ``min_faces`` or
-    ``keep_largest`` is given), then ``smooth_taubin`` (if ``smooth_iterations`` > 0), then -- with ``normals`` -- the
-    ``vertex_normals`` of the result."""
+    ``keep_largest`` is given), then ``smooth_taubin`` (if ``smooth_iterations`` > 0), then
+    ``simplify_vertex_clustering`` with cells of ``simplify_cell`` from the bounding box minimum (if given), then -- with
+    ``normals`` -- the ``vertex_normals`` of the result."""
     smooth_iterations = _count(smooth_iterations, "smooth_iterations")
+    if simplify_cell is not None:
+        _cell_size(simplify_cell, "simplify_cell")
+        _placement(simplify_placement, "simplify_placement")
     v, f = _mesh_args(vertices, faces, check)
     c = None if colors is None else _rows3(colors, "colors", v)
     if min_faces is not None or keep_largest is not None:
         v, f, c, _ = remove_small_components(v, f, c, min_faces=min_faces, keep_largest=keep_largest, check=False)
     if smooth_iterations > 0:
         v = smooth_taubin(v, f, smooth_iterations, lam, mu, check=False)
+    if simplify_cell is not None:
+        v, f, c = simplify_vertex_clustering(v, f, c, cell_size=simplify_cell, placement=simplify_placement, check=False)
     n = vertex_normals(v, f, check=False) if normals else None
     return v, f, c, n
 

@@ -741,7 +741,8 @@ class Trainer:
 
     def extract_mesh(self, view_ids: Sequence[int] = None, voxel_size: float = None, bounds=None, trunc: float = None,
                      min_weight: float = None, color: bool = True, min_component_faces: int = None,
-                     keep_largest: int = None, smooth_iterations: int = 0, **integrate_kwargs):
+                     keep_largest: int = None, smooth_iterations: int = 0, simplify_voxels: float = None,
+                     simplify_placement: str = "quadric", **integrate_kwargs):
         """-> (vertices [V,3] float32, faces [F,3] int64, colors [V,3] float32 or None): the scene's surface as a triangle
         mesh (``mesh.TSDFVolume``).  Every view of ``view_ids`` (default: all cameras) is rendered with its
         depth and opacity maps, forward only, with this trainer's ``antialiased`` and -- with ``pose_opt`` -- the current
@@ -755,8 +756,17 @@ class Trainer:
         Cleaning (``mesh.clean_mesh``), all off by default -- a default call returns what it always did,
         bit for bit: ``min_component_faces`` drops the connected components with fewer faces (the floaters a TSDF of
         splat depth maps carries), ``keep_largest`` = k keeps only the k components with the most faces,
-        ``smooth_iterations`` > 0 then runs that many Taubin iterations (lambda 0.5, mu -0.53: untuned too)."""
+        ``smooth_iterations`` > 0 then runs that many Taubin iterations (lambda 0.5, mu -0.53: untuned too).
+
+        Simplification (``mesh.simplify_vertex_clustering``), off by default and run after the cleaning:
+        ``simplify_voxels`` = k merges the vertices of every cell of k x ``voxel_size`` on the grid that starts at the
+        volume's origin into one vertex, placed by ``simplify_placement`` ("quadric", whose regulariser 1e-3 is untuned, or
+        "mean"), and drops the faces that collapse.  Topology is not preserved.  (The grid's origin must not exceed the
+        mesh's bounding box: smoothing that pushes a surface at the volume's wall below the origin ends in a ValueError.)"""
         from . import mesh as _mesh
+        if simplify_voxels is not None:
+            _mesh._cell_size(simplify_voxels, "simplify_voxels")
+            _mesh._placement(simplify_placement, "simplify_placement")
         view_ids = list(range(len(self.cams))) if view_ids is None else [int(v) for v in view_ids]
         p = self.params
         with torch.no_grad():
@@ -802,6 +812,9 @@ class Trainer:
                 # (extract guarantees the index range: no aminmax readback)
                 V, F, C, _ = _mesh.clean_mesh(V, F, C, min_faces=min_component_faces, keep_largest=keep_largest,
                                               smooth_iterations=smooth_iterations, check=False)
+            if simplify_voxels is not None:
+                V, F, C = _mesh.simplify_vertex_clustering(V, F, C, cell_size=float(simplify_voxels) * voxel,
+                                                           origin=vol.origin, placement=simplify_placement, check=False)
             return V, F, C
 
     def prune_by_importance(self, score: str = "max", threshold=None, fraction=None, view_ids: Sequence[int] = None,

@@ -5,13 +5,15 @@ into a TSDF volume, write the zero level set.
     python examples/extract_mesh.py --gs data/final.npy --path /data/tandt/train [--out mesh.ply] [--voxel S]
                                     [--alpha-min 0.5] [--trunc T] [--min-weight 1] [--depth-max D] [--no-color]
                                     [--min-component-faces N] [--keep-largest K] [--smooth N] [--normals]
+                                    [--simplify K] [--simplify-placement quadric|mean]
 
 ``--gs`` is a checkpoint of ``examples/train.py`` (.npy record array) or a 3DGS .ply; ``--path`` the dataset directory
 (sparse/0/*.bin + images/) whose cameras are used.  alpha_min 0.5, a truncation of 4 voxels and min_weight 1 are
 defaults nobody has tuned.  The mesh is cleaned on the GPU when asked: ``--min-component-faces`` and
 ``--keep-largest`` drop the floaters (connected components by face count), ``--smooth`` runs Taubin iterations (lambda 0.5,
-mu -0.53: untuned as well), ``--normals`` writes area-weighted vertex normals.  Without these flags the mesh is written as
-extracted.
+mu -0.53: untuned as well), ``--normals`` writes area-weighted vertex normals.  ``--simplify K`` then decimates the mesh by vertex
+clustering on cells of K voxels (quadric placement with an untuned regulariser of 1e-3; topology is not
+preserved).  Without these flags the mesh is written as extracted.
 """
 import argparse
 import os
@@ -37,6 +39,10 @@ def main():
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K components with the most faces")
     ap.add_argument("--smooth", type=int, default=0, metavar="N", help="Taubin smoothing iterations (untuned)")
     ap.add_argument("--normals", action="store_true", help="write vertex normals (nx ny nz)")
+    ap.add_argument("--simplify", type=float, default=None, metavar="K",
+                    help="decimate by vertex clustering: one vertex per cell of K voxels (topology is not preserved)")
+    ap.add_argument("--simplify-placement", choices=("quadric", "mean"), default="quadric",
+                    help="--simplify: where a cell's vertex goes: the quadric optimum (regulariser 1e-3, untuned) or the mean")
     a = ap.parse_args()
 
     from easygaussiansplatting_amd import scene as S
@@ -53,6 +59,7 @@ def main():
     vertices, faces, colors = tr.extract_mesh(voxel_size=a.voxel, trunc=a.trunc, min_weight=a.min_weight,
                                               color=not a.no_color, min_component_faces=a.min_component_faces,
                                               keep_largest=a.keep_largest, smooth_iterations=a.smooth,
+                                              simplify_voxels=a.simplify, simplify_placement=a.simplify_placement,
                                               alpha_min=a.alpha_min, depth_max=a.depth_max)
     normals = vertex_normals(vertices, faces, check=False) if a.normals else None
     save_mesh_ply_with_normals(a.out, vertices, faces, colors, normals)

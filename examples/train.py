@@ -88,6 +88,9 @@ def main():
                     help="--mesh: the voxel size in world units (default: the longest side of the scene's box / 256)")
     ap.add_argument("--mesh-min-faces", type=int, default=None, metavar="N",
                     help="--mesh: drop the connected components (floaters) with fewer than N faces (DESIGN §3.20)")
+    ap.add_argument("--mesh-simplify", type=float, default=None, metavar="K",
+                    help="--mesh: decimate by vertex clustering, one vertex per cell of K voxels (DESIGN §3.21; quadric "
+                         "placement, regulariser untuned; topology is not preserved)")
     a = ap.parse_args()
     if a.strategy == "mcmc" and a.cap_max is None:
         ap.error("--strategy mcmc needs --cap-max")
@@ -151,7 +154,8 @@ def main():
         print("Training is finished.")
         if a.mesh:
             from easygaussiansplatting_amd.mesh import save_mesh_ply
-            vertices, faces, colors = tr.extract_mesh(voxel_size=a.mesh_voxel, min_component_faces=a.mesh_min_faces)
+            vertices, faces, colors = tr.extract_mesh(voxel_size=a.mesh_voxel, min_component_faces=a.mesh_min_faces,
+                                                      simplify_voxels=a.mesh_simplify)
             save_mesh_ply(a.mesh, vertices, faces, colors)
             print("mesh: %d vertices, %d faces -> %s" % (vertices.shape[0], faces.shape[0], a.mesh))
     if world > 1:
