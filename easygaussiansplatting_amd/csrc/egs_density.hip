@@ -335,6 +335,7 @@ extern "C" int egs_adam_step(int n_groups, const EgsAdamGroup* groups, double be
     EGS_CHECK_ARG(g.count >= 0 && g.step >= 1);
     if (g.count == 0) continue;
     EGS_CHECK_ARG(g.param && g.grad && g.exp_avg && g.exp_avg_sq);
+    EGS_CHECK_ARG(adam_aligned16(g.param, g.grad, g.exp_avg, g.exp_avg_sq));      // k_adam loads and stores float4
     blocks += adam_fill_group(A.g[A.n_groups++], g.param, g.grad, g.exp_avg, g.exp_avg_sq, g.count, g.lr, g.step, beta1,
                               beta2, blocks);
   }

@@ -586,7 +586,12 @@ int egs_reset_alpha(int n, float raw_val, float* alphas_raw, float* exp_avg, flo
 
 /* torch.optim.Adam.step as the reference configures it (train.py:32; no weight decay / amsgrad):
  * all parameter groups in one launch.  step = the 1-based step count of the group AFTER this update.
- * betas/eps are doubles because torch derives 1 - beta and the bias corrections in double. */
+ * betas/eps are doubles because torch derives 1 - beta and the bias corrections in double; lr is a float, and the
+ * bias-corrected step size is derived in double from that float.
+ * At most 8 groups.  param, grad, exp_avg and exp_avg_sq of a group with count > 0 must be 16-byte aligned (the kernel
+ * moves float4s; a tensor as the torch allocator returns it is, a view that starts inside one need not be): a null or
+ * misaligned pointer, count < 0 or step < 1 returns EGS_ERR_BAD_ARG before any launch.  A group with count == 0 is
+ * skipped, whatever its pointers. */
 typedef struct EgsAdamGroup {
   float* param;
   const float* grad;
@@ -601,7 +606,7 @@ int egs_adam_step(int n_groups, const EgsAdamGroup* groups, double beta1, double
  * egs_sh_grad_views(n, sh_dim, views, pws, rows, row_stride, scale, grad..) followed by egs_adam_step on that gradient,
  * without the gradient rows ever reaching HBM.  low: the [n][3] tensor of the raw layout (gsmodel.py:117: low_shs) --
  * or, with high == NULL, the whole [n][sh_dim] tensor; high: the [n][sh_dim - 3] tensor (high_shs).  `grad` of the
- * groups is ignored, `count` must be n times the width. */
+ * groups is ignored, `count` must be n times the width, and the other three pointers 16-byte aligned as above. */
 int egs_adam_sh_factored(int n, int sh_dim, int views, const float* pws, const float* rows, int64_t row_stride,
                          float scale, const EgsAdamGroup* low, const EgsAdamGroup* high /*nullable*/, double beta1,
                          double beta2, double eps, void* stream);

@@ -1,7 +1,8 @@
 """Visibility-masked Adam, host side (no GPU): the float32 reference's own checks (tests/sparse_adam_ref.py), the C
 surface of libegs_adam.so against include/egs_adam.h and ``_adamlib.SIGNATURES``, its refusals before any HIP call, the
-untouched surface of libegs_hip.so, and the refusals of ``FusedAdam.step(visible=...)`` and ``Trainer(sparse_adam=True)``
-that need no device."""
+untouched surface of libegs_hip.so, the dense ``egs_adam_step``'s refusal of misaligned pointers (with ``FusedAdam.step``
+rolling its counters back), and the refusals of ``FusedAdam.step(visible=...)`` and ``Trainer(sparse_adam=True)`` that
+need no device."""
 import ctypes as C
 import os
 import re
@@ -188,6 +189,73 @@ def test_sparse_adam_sh_factored_refuses_bad_arguments_before_the_device(lib):
     # nothing to do is no error -- but sizes are still checked
     assert call(n=0, pws=None, rows=None, visible=None) == 0
     assert refused(call(n=0, K=7)) and refused(call(n=0, low=None))
+
+
+def test_dense_adam_step_refuses_misaligned_pointers_before_the_device(lib):
+    """``egs_adam_step`` (libegs_hip.so) moves float4s like the masked step and refuses what the masked step refuses: each
+    of the four pointers null or off a 16-byte boundary, before any HIP call.  A zero-count group is skipped, whatever it
+    points to."""
+    from easygaussiansplatting_amd import _lib
+    main = _lib.load()
+    err = main.egs_last_error_string
+
+    def grp(param=_FAKE, grad=_FAKE, m=_FAKE, v=_FAKE, count=300, step=1):
+        return _lib.EgsAdamGroup(param, grad, m, v, count, 1e-3, step)
+
+    def call(groups):
+        return main.egs_adam_step(len(groups), (_lib.EgsAdamGroup * max(len(groups), 1))(*groups), 0.9, 0.999, 1e-15, None)
+
+    def refused(rc):
+        return rc == BAD_ARG and b"bad argument" in err() and b"egs_density" in err()
+    for field in ("param", "grad", "m", "v"):
+        for off in (4, 8, 12):
+            assert refused(call([grp(**{field: _FAKE + off})])) and b"adam_aligned16" in err(), (field, off)
+            assert refused(call([grp(count=0), grp(**{field: _FAKE + off})])), (field, off)       # behind a skipped group
+        assert refused(call([grp(), grp(**{field: None})])), field
+    assert refused(call([grp(step=0)])) and refused(call([grp(count=-1)])) and refused(call([grp()] * 9))
+    assert call([]) == 0 and call([grp(count=0)]) == 0
+    assert call([grp(_FAKE + 4, _FAKE + 8, None, _FAKE + 12, count=0)]) == 0
+
+
+class _DeviceLike(torch.Tensor):
+    """a host tensor that calls itself a device tensor: ``FusedAdam.step`` takes it as far as the C entry point, which
+    must refuse it before anything is launched"""
+    is_cuda = property(lambda self: True)
+
+
+@pytest.mark.parametrize("which", ["param", "grad", "exp_avg", "exp_avg_sq"])
+def test_fused_adam_step_with_a_misaligned_tensor_raises_and_rolls_every_counter_back(lib, monkeypatch, which):
+    """``x[1:]`` of an [n, 3] tensor is contiguous float32 and starts 12 bytes into its storage: the dense step refuses it
+    (RuntimeError from the library's argument check), no tensor moves, every step counter is where it was."""
+    from easygaussiansplatting_amd.optim import FusedAdam
+
+    class _Stream:
+        cuda_stream = 0
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _Stream())
+    n = 8
+    like = lambda t: torch.Tensor._make_subclass(_DeviceLike, t)
+    sliced = lambda value=0.5: torch.full((n + 1, 3), value)[1:]
+    ps = [like(torch.full((n, 3), 0.5)).requires_grad_() for _ in range(3)]
+    if which == "param":
+        ps[1] = like(sliced()).requires_grad_()
+    assert all(p.is_contiguous() and p.is_cuda for p in ps)
+    for p in ps:
+        p.grad = torch.ones(n, 3)
+    if which == "grad":
+        ps[1].grad = sliced()
+    opt = FusedAdam([{"params": [p], "lr": 1e-3} for p in ps])
+    for k, p in enumerate(ps):
+        opt.state[p] = {"step": 3 + k, "exp_avg": torch.zeros(n, 3), "exp_avg_sq": torch.zeros(n, 3)}
+    if which in ("exp_avg", "exp_avg_sq"):
+        opt.state[ps[1]][which] = sliced(0.0)
+    ptrs = dict(param=ps[1], grad=ps[1].grad, exp_avg=opt.state[ps[1]]["exp_avg"], exp_avg_sq=opt.state[ps[1]]["exp_avg_sq"])
+    assert ptrs[which].data_ptr() % 16 == 12 and all(t.data_ptr() % 16 == 0 for k, t in ptrs.items() if k != which)
+    with pytest.raises(RuntimeError, match="bad argument.*adam_aligned16"):
+        opt.step()
+    for k, p in enumerate(ps):
+        st = opt.state[p]
+        assert st["step"] == 3 + k and not st["exp_avg"].any() and not st["exp_avg_sq"].any(), k
+        assert bool((p.detach() == 0.5).all())
 
 
 def test_missing_library_raises(monkeypatch, tmp_path):
