@@ -213,7 +213,8 @@ __global__ __launch_bounds__(TSDF_THREADS) void k_mesh_emit(Lattice L, int64_t c
   Cell c;
   if (!load_cell(L.nx, L.ny, L.nz, cell, tsdf, weight, min_weight, c)) return;
   MeshOut out = {verts, keys, colors, offsets[cell], total, 0};
-  egs_tsdf::emit_cell(L, c, color, out);
+  const egs_tsdf::DenseAddr addr = {L.nx, (int64_t)L.nx * L.ny, (int64_t)L.nx * L.ny * L.nz};
+  egs_tsdf::emit_cell(L, c, color, addr, out);
 }
 
 }  // namespace egs

@@ -121,9 +121,18 @@ EGS_HD int cell_triangles(int inside8) {
   return n;
 }
 
+// Where the corners of a cell live: key(c, p) is the linear sample index of corner p in the lattice, which names it in a
+// vertex key; at(c, p) is its index in a colour plane, and `plane` the distance between two colour planes.  A dense volume
+// stores a sample at its lattice index: the identity.  (A block-allocated volume, egs_sparsetsdf.hip, has its own.)
+struct DenseAddr {
+  int64_t sy, sz, plane;      // nx, nx ny, nx ny nz
+  EGS_HD int64_t key(const Cell& c, int p) const { return c.base + (p & 1) + ((p >> 1) & 1) * sy + ((p >> 2) & 1) * sz; }
+  EGS_HD int64_t at(const Cell& c, int p) const { return key(c, p); }
+};
+
 // the vertex on the edge between corners p and q of the cell (p a subset of q's bits): coordinates, key, colour
-template <typename Out>
-EGS_HD void edge_vertex(const Lattice& L, const Cell& c, int p, int q, const float* __restrict__ color, int64_t total_n,
+template <typename Addr, typename Out>
+EGS_HD void edge_vertex(const Lattice& L, const Cell& c, int p, int q, const float* __restrict__ color, const Addr& A,
                         Out& out, int slot) {
   const int d = p ^ q;
   const float flo = c.f[p], fhi = c.f[q];
@@ -133,14 +142,12 @@ EGS_HD void edge_vertex(const Lattice& L, const Cell& c, int p, int q, const flo
   const float x = (L.ox + L.voxel * (float)lx) + ((d & 1) ? tv : 0.f);
   const float y = (L.oy + L.voxel * (float)ly) + ((d & 2) ? tv : 0.f);
   const float z = (L.oz + L.voxel * (float)lz) + ((d & 4) ? tv : 0.f);
-  const int64_t sx = 1, sy = L.nx, sz = (int64_t)L.nx * L.ny;
-  const int64_t lo = c.base + (p & 1) * sx + ((p >> 1) & 1) * sy + ((p >> 2) & 1) * sz;
-  const int64_t hi = c.base + (q & 1) * sx + ((q >> 1) & 1) * sy + ((q >> 2) & 1) * sz;
-  out.vertex(slot, x, y, z, 7 * lo + edge_type(d));
+  out.vertex(slot, x, y, z, 7 * A.key(c, p) + edge_type(d));
   if (color) {
+    const int64_t lo = A.at(c, p), hi = A.at(c, q);
     float rgb[3];
     for (int k = 0; k < 3; ++k) {
-      const float a = color[k * total_n + lo], b = color[k * total_n + hi];
+      const float a = color[k * A.plane + lo], b = color[k * A.plane + hi];
       rgb[k] = a + t * (b - a);
     }
     out.colour(slot, rgb[0], rgb[1], rgb[2]);
@@ -149,9 +156,8 @@ EGS_HD void edge_vertex(const Lattice& L, const Cell& c, int p, int q, const flo
 
 // Emit the triangles of a cell whose corners are all valid, in order, through `out`: out.begin(k) opens the cell's k-th
 // triangle (false: it has no room, the cell stops), out.vertex / out.colour fill its slots 0..2.  -> triangles emitted
-template <typename Out>
-EGS_HD int emit_cell(const Lattice& L, const Cell& c, const float* __restrict__ color, Out& out) {
-  const int64_t total_n = (int64_t)L.nx * L.ny * L.nz;
+template <typename Addr, typename Out>
+EGS_HD int emit_cell(const Lattice& L, const Cell& c, const float* __restrict__ color, const Addr& A, Out& out) {
   int inside8 = 0;
   for (int k = 0; k < 8; ++k) inside8 |= (c.f[k] < 0.f ? 1 : 0) << k;
   int n = 0;
@@ -174,7 +180,7 @@ EGS_HD int emit_cell(const Lattice& L, const Cell& c, const float* __restrict__ 
       const int e[3] = {j, flip ? l : k, flip ? k : l};
       for (int s = 0; s < 3; ++s) {
         const int a = i < e[s] ? i : e[s], b = i < e[s] ? e[s] : i;
-        edge_vertex(L, c, v[a], v[b], color, total_n, out, s);
+        edge_vertex(L, c, v[a], v[b], color, A, out, s);
       }
       ++n;
     } else {
@@ -192,7 +198,7 @@ EGS_HD int emit_cell(const Lattice& L, const Cell& c, const float* __restrict__ 
         const int corner[3] = {0, positive ? c1 : c2, positive ? c2 : c1};
         for (int s = 0; s < 3; ++s) {
           const int p = qa[corner[s]], q = qb[corner[s]];
-          edge_vertex(L, c, v[p < q ? p : q], v[p < q ? q : p], color, total_n, out, s);
+          edge_vertex(L, c, v[p < q ? p : q], v[p < q ? q : p], color, A, out, s);
         }
         ++n;
       }

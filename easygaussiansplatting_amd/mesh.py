@@ -33,6 +33,14 @@ and duplicate faces are dropped.  Deterministic bit for bit like the rest.  The 
 untuned: nobody has tuned it here.  Vertex clustering does NOT preserve topology: a closed manifold may come out with a few
 opposite face pairs and another Euler characteristic.  ``clean_mesh(..., simplify_cell=...)`` runs it between the smoothing
 and the normals.
+
+A dense volume costs what its bounding box costs.  ``SparseTSDFVolume`` (csrc/egs_sparsetsdf.hip,
+libegs_sparsetsdf.so; include/egs_sparse_tsdf.h has every rule) stores and updates only the 8^3-sample blocks within the
+truncation band of an observed surface: the same arithmetic on the same lattice (both volumes call csrc/egs_tsdf_device.h),
+the same vertex keys, so everything after ``extract()`` is unchanged.  A block is updated only from the view that allocates
+it onwards, and a cell is meshed only when all eight corners are allocated.
+
+    vol = SparseTSDFVolume(origin=(-1, -1, -1), voxel_size=2 / 1023, dims=(1024, 1024, 1024))
 """
 from __future__ import annotations
 
@@ -42,7 +50,7 @@ import math
 import numpy as np
 import torch
 
-from . import _meshopslib, _simplifylib, _tsdflib
+from . import _meshopslib, _simplifylib, _sparsetsdflib, _tsdflib
 from ._host import _lib_on, _ptr, _stream
 from .depthloss import _plane
 from .normalloss import _intrinsics, _planes3
@@ -98,6 +106,52 @@ def frustum_box(origin, voxel, dims, K, hw, Rcw, tcw, near, far):
     return (int(lo[0]), int(hi[0]), int(lo[1]), int(hi[1]), int(lo[2]), int(hi[2]))
 
 
+def _weld(verts, keys, colors):
+    """a triangle soup with vertex keys -> (vertices [V,3], faces [F,3] int64, colors [V,3] or None), welded by key"""
+    uniq, inverse = torch.unique(keys.reshape(-1), return_inverse=True)
+    faces = inverse.reshape(-1, 3)
+    V = torch.empty((uniq.shape[0], 3), dtype=torch.float32, device=verts.device)
+    V[inverse] = verts.reshape(-1, 3)          # (duplicates hold the same bits: whichever lands is right)
+    C = None
+    if colors is not None:
+        C = torch.empty((uniq.shape[0], 3), dtype=torch.float32, device=verts.device)
+        C[inverse] = colors.reshape(-1, 3)
+    return V, faces, C
+
+
+def _view_args(has_color, device, depth, alpha, cam, image, weight, alpha_min, near, depth_max):
+    """The checks ``TSDFVolume.integrate`` and ``SparseTSDFVolume.integrate`` share -> (d, a, w, img, K, alpha_min, near,
+    Rcw, tcw): the maps as planes, the intrinsics, the pose as device tensors"""
+    d = _plane(depth, "depth")
+    H, W = int(d.shape[0]), int(d.shape[1])
+    a = None if alpha is None else _plane(alpha, "alpha", (H, W), d)
+    w = None if weight is None else _plane(weight, "weight", (H, W), d)
+    if (image is None) != (not has_color):
+        raise ValueError("image must be given iff the volume has a colour plane (color=%s)" % (has_color))
+    img = None if image is None else _planes3(image, "image", (H, W), d)
+    K = _intrinsics(cam)
+    alpha_min, near = float(alpha_min), float(near)
+    if not 0.0 <= alpha_min < float("inf"):
+        raise ValueError("alpha_min must be finite and >= 0, got %r" % (alpha_min,))
+    if not 0.0 <= near < float("inf"):
+        raise ValueError("near must be finite and >= 0, got %r" % (near,))
+    if depth_max is not None and not float(depth_max) > 0:
+        raise ValueError("depth_max must be > 0 or None, got %r" % (depth_max,))
+    if not (hasattr(cam, "Rcw") and hasattr(cam, "tcw")):
+        raise ValueError("cam must carry its pose Rcw, tcw, got %r" % (cam,))
+    if d.device != device:
+        raise ValueError("depth lives on %s, the volume on %s" % (d.device, device))
+    if not d.is_cuda:
+        raise ValueError("depth must live on the GPU (got device %s)" % (d.device,))
+    _lib_on(d)
+    as_dev = lambda p: (p if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p, np.float32))) \
+        .detach().to(device=d.device, dtype=torch.float32).contiguous()
+    Rcw, tcw = as_dev(cam.Rcw).reshape(-1), as_dev(cam.tcw).reshape(-1)
+    if Rcw.numel() != 9 or tcw.numel() != 3:
+        raise ValueError("cam.Rcw must have 9 entries and cam.tcw 3")
+    return d, a, w, img, K, alpha_min, near, Rcw, tcw
+
+
 class TSDFVolume:
     """A dense truncated signed distance volume on the GPU: ``dims`` = (nx, ny, nz) samples at ``origin`` +
     ``voxel_size`` (ix, iy, iz) in the world frame.  ``tsdf`` [nz,ny,nx] (1), ``weight`` [nz,ny,nx] (0) and, with
@@ -136,34 +190,10 @@ class TSDFVolume:
         plane; ``weight`` [H,W] >= 0 or None.  ``clip_to_frustum``: launch on the lattice sub-box the view can reach
         (``frustum_box``; the same bits as the full launch).  Shapes, dtypes and devices are checked (ValueError), values
         are not.  Nothing is read back."""
-        d = _plane(depth, "depth")
+        d, a, w, img, K, alpha_min, near, Rcw, tcw = _view_args(self.color is not None, self.tsdf.device, depth, alpha, cam,
+                                                                image, weight, alpha_min, near, depth_max)
         H, W = int(d.shape[0]), int(d.shape[1])
-        a = None if alpha is None else _plane(alpha, "alpha", (H, W), d)
-        w = None if weight is None else _plane(weight, "weight", (H, W), d)
-        if (image is None) != (self.color is None):
-            raise ValueError("image must be given iff the volume has a colour plane (color=%s)" % (self.color is not None))
-        img = None if image is None else _planes3(image, "image", (H, W), d)
-        K = _intrinsics(cam)
-        alpha_min, near = float(alpha_min), float(near)
-        if not 0.0 <= alpha_min < float("inf"):
-            raise ValueError("alpha_min must be finite and >= 0, got %r" % (alpha_min,))
-        if not 0.0 <= near < float("inf"):
-            raise ValueError("near must be finite and >= 0, got %r" % (near,))
-        if depth_max is not None and not float(depth_max) > 0:
-            raise ValueError("depth_max must be > 0 or None, got %r" % (depth_max,))
-        if not (hasattr(cam, "Rcw") and hasattr(cam, "tcw")):
-            raise ValueError("cam must carry its pose Rcw, tcw, got %r" % (cam,))
-        if d.device != self.tsdf.device:
-            raise ValueError("depth lives on %s, the volume on %s" % (d.device, self.tsdf.device))
-        if not d.is_cuda:
-            raise ValueError("depth must live on the GPU (got device %s)" % (d.device,))
-        _lib_on(d)
         lib = _tsdflib.load()
-        as_dev = lambda p: (p if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p, np.float32))) \
-            .detach().to(device=d.device, dtype=torch.float32).contiguous()
-        Rcw, tcw = as_dev(cam.Rcw).reshape(-1), as_dev(cam.tcw).reshape(-1)
-        if Rcw.numel() != 9 or tcw.numel() != 3:
-            raise ValueError("cam.Rcw must have 9 entries and cam.tcw 3")
         nx, ny, nz = self.dims
         box = (0, nx, 0, ny, 0, nz)
         if clip_to_frustum:
@@ -215,16 +245,223 @@ class TSDFVolume:
         mesh.  A cell is meshed when all its corners have weight >= ``min_weight`` (1 by default, untuned).  Vertices on
         the same lattice edge are welded by their key; their coordinates are identical, any occurrence gives them.
         Outward orientation: a face's normal points from negative to positive tsdf, towards the cameras."""
-        verts, keys, colors = self.extract_triangles(min_weight)
-        uniq, inverse = torch.unique(keys.reshape(-1), return_inverse=True)
-        faces = inverse.reshape(-1, 3)
-        V = torch.empty((uniq.shape[0], 3), dtype=torch.float32, device=verts.device)
-        V[inverse] = verts.reshape(-1, 3)          # (duplicates hold the same bits: whichever lands is right)
-        C = None
-        if colors is not None:
-            C = torch.empty((uniq.shape[0], 3), dtype=torch.float32, device=verts.device)
-            C[inverse] = colors.reshape(-1, 3)
-        return V, faces, C
+        return _weld(*self.extract_triangles(min_weight))
+
+
+# ------------------------------------------------------------------------------------------------------ the sparse volume
+SPARSE_FIRST_CAPACITY = 1024      # pool slots before the first doubling
+
+
+class SparseTSDFVolume:
+    """A block-allocated truncated signed distance volume on the GPU (csrc/egs_sparsetsdf.hip,
+    libegs_sparsetsdf.so; include/egs_sparse_tsdf.h has every rule): the lattice of ``TSDFVolume`` -- ``dims`` = (nx, ny,
+    nz) samples at ``origin`` + ``voxel_size`` (ix, iy, iz) -- of which only the 8 x 8 x 8-sample blocks within the
+    truncation band of an observed surface are stored, so the cost follows the surface and not the bounding box, and the
+    lattice may have 2^31 samples and more (at most 2^27 blocks; at most 2^22 of them allocated).
+
+    ``directory`` [nbz,nby,nbx] int32 holds -1 or a block's pool slot, ``block_coords`` [capacity] int32 the linear block
+    index of each slot, ``tsdf`` and ``weight`` [capacity,512] and ``color`` [3,capacity,512] the pools (x fastest within
+    a block); slots 0 .. ``n_blocks`` - 1 are in use.  The pool grows by doubling; ``max_blocks`` caps it.
+
+    SEMANTICS.  Every sample of an allocated block takes the bits ``TSDFVolume`` gives it from the same previous bits
+    (both call the functions of csrc/egs_tsdf_device.h), but a block is updated only FROM THE VIEW THAT ALLOCATES IT
+    onwards: free-space observations (t = 1) that earlier views made of its samples are not recorded.  A cell is meshed
+    only when all eight of its corners lie in allocated blocks (and have weight >= ``min_weight``); its triangles, vertex
+    keys and colours are then the dense volume's."""
+
+    def __init__(self, origin, voxel_size, dims, trunc=None, color=True, max_blocks=None, device="cuda"):
+        try:
+            self.origin = tuple(float(v) for v in origin)
+            self.dims = tuple(int(v) for v in dims)
+            self.voxel_size = float(voxel_size)
+        except (TypeError, ValueError):
+            raise ValueError("origin, voxel_size, dims must be three numbers, a number and three integers") from None
+        if len(self.origin) != 3 or not all(math.isfinite(v) for v in self.origin):
+            raise ValueError("origin must be three finite numbers, got %r" % (origin,))
+        if not (math.isfinite(self.voxel_size) and self.voxel_size > 0):
+            raise ValueError("voxel_size must be finite and > 0, got %r" % (voxel_size,))
+        if len(self.dims) != 3 or min(self.dims) < 1 or max(self.dims) > _tsdflib.MAX_SAMPLES:
+            raise ValueError("dims must be three positive integers (nx, ny, nz), got %r" % (dims,))
+        B = _sparsetsdflib.BLOCK
+        self.block_dims = tuple((n + B - 1) // B for n in self.dims)
+        total = self.block_dims[0] * self.block_dims[1] * self.block_dims[2]
+        if total > _sparsetsdflib.MAX_DIRECTORY:
+            raise ValueError("dims %r: %d blocks, the directory takes at most 2^27" % (self.dims, total))
+        self.trunc = TRUNC_VOXELS * self.voxel_size if trunc is None else float(trunc)
+        if not (math.isfinite(self.trunc) and self.trunc > 0):
+            raise ValueError("trunc must be finite and > 0, got %r" % (trunc,))
+        if 2.0 * self.trunc > _sparsetsdflib.MAX_MARCH * self.voxel_size:
+            raise ValueError("trunc must not exceed %d voxels, got %r" % (_sparsetsdflib.MAX_MARCH // 2, trunc))
+        self.limit = min(total, _sparsetsdflib.MAX_SLOTS)
+        if max_blocks is not None:
+            if int(max_blocks) != max_blocks or int(max_blocks) < 1:
+                raise ValueError("max_blocks must be a positive integer or None, got %r" % (max_blocks,))
+            self.limit = min(self.limit, int(max_blocks))
+        self.max_blocks = None if max_blocks is None else int(max_blocks)
+        self.device = torch.device(device)
+        self.has_color = bool(color)
+        nbx, nby, nbz = self.block_dims
+        self.directory = torch.full((nbz, nby, nbx), -1, dtype=torch.int32, device=self.device)
+        self.n_blocks = 0
+        self._allocate_pool(min(self.limit, SPARSE_FIRST_CAPACITY))
+
+    # ---- the pool
+    def _allocate_pool(self, capacity):
+        """new pools of ``capacity`` slots holding 1 / 0 / 0, the slots in use copied over"""
+        S, dev, n = _sparsetsdflib.BLOCK_SAMPLES, self.device, self.n_blocks
+        coords = torch.full((capacity,), -1, dtype=torch.int32, device=dev)
+        tsdf = torch.ones((capacity, S), dtype=torch.float32, device=dev)
+        weight = torch.zeros((capacity, S), dtype=torch.float32, device=dev)
+        color = torch.zeros((3, capacity, S), dtype=torch.float32, device=dev) if self.has_color else None
+        if n > 0:
+            coords[:n] = self.block_coords[:n]
+            tsdf[:n] = self.tsdf[:n]
+            weight[:n] = self.weight[:n]
+            if color is not None:
+                color[:, :n] = self.color[:, :n]
+        self.block_coords, self.tsdf, self.weight, self.color, self.capacity = coords, tsdf, weight, color, capacity
+
+    def _geometry(self):
+        return (*self.dims, *self.origin, self.voxel_size)
+
+    def integrate(self, depth, alpha, cam, image=None, weight=None, alpha_min=ALPHA_MIN, near=0.01, depth_max=None,
+                  clip_to_frustum=True, grid_cap=0):
+        """Fuse one view: the arguments of ``TSDFVolume.integrate`` (``clip_to_frustum`` is accepted and has nothing to
+        do: only allocated blocks are walked).  First the blocks the view's truncation band meets, dilated by one block,
+        are allocated -- ONE integer, the number of new blocks, is read back -- then the view is fused into every
+        allocated block.  ``max_blocks`` exceeded: ValueError, and the volume is left as it was.  ``grid_cap``: a cap on
+        the workgroups of the fusion (the ABI's ``max_blocks``; the same bits)."""
+        d, a, w, img, K, alpha_min, near, Rcw, tcw = _view_args(self.has_color, self.tsdf.device, depth, alpha, cam, image,
+                                                                weight, alpha_min, near, depth_max)
+        H, W = int(d.shape[0]), int(d.shape[1])
+        lib = _sparsetsdflib.load()
+        chk = _sparsetsdflib.check
+        d, a, w, img = (None if t is None else t.contiguous() for t in (d, a, w, img))
+        dmax = float("inf") if depth_max is None else float(depth_max)
+        nx, ny, nz = self.dims
+        dev = self.tsdf.device
+        flags = torch.zeros(self.directory.shape, dtype=torch.int32, device=dev)
+        chk(lib.egs_sparsetsdf_touch(*self._geometry(), H, W, _ptr(d), _ptr(a), _ptr(w), *K, _ptr(Rcw), _ptr(tcw),
+                                     self.trunc, alpha_min, near, dmax, _ptr(flags), _stream()))
+        fresh = torch.empty(self.directory.shape, dtype=torch.int32, device=dev)
+        chk(lib.egs_sparsetsdf_mark(nx, ny, nz, _ptr(flags), _ptr(self.directory), _ptr(fresh), _stream()))
+        fresh = fresh.reshape(-1)
+        ends = torch.cumsum(fresh, 0, dtype=torch.int64)
+        new = int(ends[-1])                # the one readback of a view
+        if self.n_blocks + new > self.limit:
+            raise ValueError("the view needs %d new blocks beside the %d allocated: more than %s"
+                             % (new, self.n_blocks, "max_blocks = %d" % self.max_blocks if self.limit == self.max_blocks
+                                else "the volume's limit of %d" % self.limit))
+        if new > 0:
+            if self.n_blocks + new > self.capacity:
+                self._allocate_pool(min(self.limit, max(2 * self.capacity, self.n_blocks + new)))
+            offsets = (ends - fresh).contiguous()
+            chk(lib.egs_sparsetsdf_assign(nx, ny, nz, _ptr(fresh), _ptr(offsets), self.n_blocks, self.capacity,
+                                          _ptr(self.directory), _ptr(self.block_coords), _stream()))
+            self.n_blocks += new
+        chk(lib.egs_sparsetsdf_integrate(*self._geometry(), self.n_blocks, self.capacity, _ptr(self.block_coords),
+                                         _ptr(self.tsdf), _ptr(self.weight), _ptr(self.color), H, W, _ptr(d), _ptr(a),
+                                         _ptr(img), _ptr(w), *K, _ptr(Rcw), _ptr(tcw), self.trunc, alpha_min, near, dmax,
+                                         int(grid_cap), _stream()))
+        return self
+
+    def extract_triangles(self, min_weight=MIN_WEIGHT):
+        """-> (verts [T,3,3] float32, keys [T,3] int64, colors [T,3,3] float32 or None): the triangle soup of the zero
+        level set by slot, then by the cell within the block; the keys are the dense volume's"""
+        min_weight = float(min_weight)
+        if not (math.isfinite(min_weight) and min_weight > 0):
+            raise ValueError("min_weight must be finite and > 0, got %r" % (min_weight,))
+        dev = self.tsdf.device
+        if not self.tsdf.is_cuda:
+            raise ValueError("the volume must live on the GPU (got device %s)" % (dev,))
+        _lib_on(self.tsdf)
+        lib = _sparsetsdflib.load()
+        nx, ny, nz = self.dims
+        n, total = self.n_blocks, 0
+        if n > 0:
+            counts = torch.empty(n * _sparsetsdflib.BLOCK_SAMPLES, dtype=torch.int32, device=dev)
+            _sparsetsdflib.check(lib.egs_sparsetsdf_mesh_count(nx, ny, nz, n, self.capacity, _ptr(self.directory),
+                                                               _ptr(self.block_coords), _ptr(self.tsdf),
+                                                               _ptr(self.weight), min_weight, _ptr(counts), _stream()))
+            ends = torch.cumsum(counts, 0, dtype=torch.int64)
+            offsets = (ends - counts).contiguous()
+            total = int(ends[-1])          # the one readback of an extraction
+            if total > _tsdflib.MAX_SAMPLES:
+                raise ValueError("the mesh has %d triangles, more than 2^31 - 1" % total)
+        verts = torch.empty((total, 3, 3), dtype=torch.float32, device=dev)
+        keys = torch.empty((total, 3), dtype=torch.int64, device=dev)
+        colors = torch.empty((total, 3, 3), dtype=torch.float32, device=dev) if self.color is not None else None
+        if total > 0:
+            _sparsetsdflib.check(lib.egs_sparsetsdf_mesh_emit(*self._geometry(), n, self.capacity, _ptr(self.directory),
+                                                              _ptr(self.block_coords), _ptr(self.tsdf), _ptr(self.weight),
+                                                              _ptr(self.color), min_weight, _ptr(offsets), total, total,
+                                                              _ptr(verts), _ptr(keys), _ptr(colors), _stream()))
+        return verts, keys, colors
+
+    def extract(self, min_weight=MIN_WEIGHT):
+        """-> (vertices [V,3] float32, faces [F,3] int64, colors [V,3] float32 or None), welded by key as
+        ``TSDFVolume.extract`` does.  A cell is meshed when all eight corners lie in allocated blocks with weight >=
+        ``min_weight``: the surface ends where the allocation ends."""
+        return _weld(*self.extract_triangles(min_weight))
+
+    # ---- to and from a dense volume (plain indexing)
+    def to_dense(self):
+        """-> a ``TSDFVolume`` with the allocated blocks' samples and 1 / 0 / 0 elsewhere; it takes fewer than 2^31
+        samples like every dense volume"""
+        vol = TSDFVolume(self.origin, self.voxel_size, self.dims, trunc=self.trunc, color=self.has_color,
+                         device=self.device)
+        B = _sparsetsdflib.BLOCK
+        nx, ny, nz = self.dims
+        nbx, nby, nbz = self.block_dims
+        n = self.n_blocks
+        b = self.block_coords[:n].long()
+
+        def scatter(pool, fill):
+            blocks = torch.full((nbz * nby * nbx, B, B, B), fill, dtype=torch.float32, device=self.device)
+            blocks[b] = pool[:n].reshape(n, B, B, B)
+            full = blocks.reshape(nbz, nby, nbx, B, B, B).permute(0, 3, 1, 4, 2, 5).reshape(nbz * B, nby * B, nbx * B)
+            return full[:nz, :ny, :nx].contiguous()
+
+        vol.tsdf, vol.weight = scatter(self.tsdf, 1.0), scatter(self.weight, 0.0)
+        if self.has_color:
+            vol.color = torch.stack([scatter(self.color[c], 0.0) for c in range(3)])
+        return vol
+
+    @classmethod
+    def from_dense(cls, volume, block_mask):
+        """A sparse volume holding the blocks of the dense ``volume`` that ``block_mask`` [nbz,nby,nbx] (bool) selects,
+        slots in ascending block index"""
+        B = _sparsetsdflib.BLOCK
+        self = cls(volume.origin, volume.voxel_size, volume.dims, trunc=volume.trunc, color=volume.color is not None,
+                   device=volume.tsdf.device)
+        nbx, nby, nbz = self.block_dims
+        mask = torch.as_tensor(block_mask, device=self.device)
+        if mask.dtype != torch.bool or tuple(mask.shape) != (nbz, nby, nbx):
+            raise ValueError("block_mask must be a bool tensor of shape %s, got %s %s"
+                             % ([nbz, nby, nbx], mask.dtype, list(mask.shape)))
+        b = torch.nonzero(mask.reshape(-1)).reshape(-1)
+        n = int(b.shape[0])
+        if n > self.limit:
+            raise ValueError("block_mask selects %d blocks, the volume's limit is %d" % (n, self.limit))
+        nx, ny, nz = self.dims
+
+        def gather(plane, fill):
+            full = torch.full((nbz * B, nby * B, nbx * B), fill, dtype=torch.float32, device=self.device)
+            full[:nz, :ny, :nx] = plane
+            blocks = full.reshape(nbz, B, nby, B, nbx, B).permute(0, 2, 4, 1, 3, 5).reshape(nbz * nby * nbx, B * B * B)
+            return blocks[b]
+
+        self.n_blocks = 0
+        self._allocate_pool(max(n, 1))
+        self.n_blocks = n
+        if n > 0:
+            self.block_coords[:n] = b.to(torch.int32)
+            self.directory.reshape(-1)[b] = torch.arange(n, dtype=torch.int32, device=self.device)
+            self.tsdf[:n], self.weight[:n] = gather(volume.tsdf, 1.0), gather(volume.weight, 0.0)
+            if self.has_color:
+                for c in range(3):
+                    self.color[c, :n] = gather(volume.color[c], 0.0)
+        return self
 
 
 # -------------------------------------------------------------------------------------------------------- mesh cleaning

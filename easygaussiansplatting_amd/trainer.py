@@ -742,7 +742,7 @@ class Trainer:
     def extract_mesh(self, view_ids: Sequence[int] = None, voxel_size: float = None, bounds=None, trunc: float = None,
                      min_weight: float = None, color: bool = True, min_component_faces: int = None,
                      keep_largest: int = None, smooth_iterations: int = 0, simplify_voxels: float = None,
-                     simplify_placement: str = "quadric", **integrate_kwargs):
+                     simplify_placement: str = "quadric", sparse: bool = False, **integrate_kwargs):
         """-> (vertices [V,3] float32, faces [F,3] int64, colors [V,3] float32 or None): the scene's surface as a triangle
         mesh (``mesh.TSDFVolume``).  Every view of ``view_ids`` (default: all cameras) is rendered with its
         depth and opacity maps, forward only, with this trainer's ``antialiased`` and -- with ``pose_opt`` -- the current
@@ -762,7 +762,12 @@ class Trainer:
         ``simplify_voxels`` = k merges the vertices of every cell of k x ``voxel_size`` on the grid that starts at the
         volume's origin into one vertex, placed by ``simplify_placement`` ("quadric", whose regulariser 1e-3 is untuned, or
         "mean"), and drops the faces that collapse.  Topology is not preserved.  (The grid's origin must not exceed the
-        mesh's bounding box: smoothing that pushes a surface at the volume's wall below the origin ends in a ValueError.)"""
+        mesh's bounding box: smoothing that pushes a surface at the volume's wall below the origin ends in a ValueError.)
+
+        ``sparse`` = True fuses into a ``mesh.SparseTSDFVolume``, which stores only the 8^3 blocks near the
+        observed surfaces: the defaults stay what they are, but ``voxel_size`` may then be far finer than a dense
+        volume could hold.  A block is updated only from the view that allocates it onwards, and the surface ends where
+        the allocation ends.  ``sparse`` = False, the default, returns what it always did, bit for bit."""
         from . import mesh as _mesh
         if simplify_voxels is not None:
             _mesh._cell_size(simplify_voxels, "simplify_voxels")
@@ -791,7 +796,8 @@ class Trainer:
             pad = trunc if pad is None else pad
             lo, hi = lo - pad, hi + pad
             dims = tuple(int(math.ceil((h - l) / voxel - 1e-9)) + 1 for l, h in zip(lo, hi))
-            vol = _mesh.TSDFVolume(tuple(lo), voxel, dims, trunc=trunc, color=color, device=self.device)
+            vol = (_mesh.SparseTSDFVolume if sparse else _mesh.TSDFVolume)(tuple(lo), voxel, dims, trunc=trunc,
+                                                                           color=color, device=self.device)
             if self.fused_activations:
                 args, fn = (p["pws"], p["low_shs"], p["high_shs"], p["alphas_raw"], p["scales_raw"], p["rots_raw"]), \
                     GSRawFunction

@@ -5,7 +5,7 @@ into a TSDF volume, write the zero level set.
     python examples/extract_mesh.py --gs data/final.npy --path /data/tandt/train [--out mesh.ply] [--voxel S]
                                     [--alpha-min 0.5] [--trunc T] [--min-weight 1] [--depth-max D] [--no-color]
                                     [--min-component-faces N] [--keep-largest K] [--smooth N] [--normals]
-                                    [--simplify K] [--simplify-placement quadric|mean]
+                                    [--simplify K] [--simplify-placement quadric|mean] [--sparse]
 
 ``--gs`` is a checkpoint of ``examples/train.py`` (.npy record array) or a 3DGS .ply; ``--path`` the dataset directory
 (sparse/0/*.bin + images/) whose cameras are used.  alpha_min 0.5, a truncation of 4 voxels and min_weight 1 are
@@ -13,7 +13,9 @@ defaults nobody has tuned.  The mesh is cleaned on the GPU when asked (DESIGN §
 ``--keep-largest`` drop the floaters (connected components by face count), ``--smooth`` runs Taubin iterations (lambda 0.5,
 mu -0.53: untuned as well), ``--normals`` writes area-weighted vertex normals.  ``--simplify K`` then decimates the mesh by vertex
 clustering on cells of K voxels (quadric placement with an untuned regulariser of 1e-3; topology is not
-preserved).  Without these flags the mesh is written as extracted.
+preserved).  Without these flags the mesh is written as extracted.  ``--sparse`` fuses into a block-allocated volume
+ that stores only the 8^3 blocks near the surfaces: ``--voxel`` may then be far finer than a dense volume could
+hold; the default voxel size stays what it is.
 """
 import argparse
 import os
@@ -43,6 +45,8 @@ def main():
                     help="decimate by vertex clustering: one vertex per cell of K voxels (topology is not preserved)")
     ap.add_argument("--simplify-placement", choices=("quadric", "mean"), default="quadric",
                     help="--simplify: where a cell's vertex goes: the quadric optimum (regulariser 1e-3, untuned) or the mean")
+    ap.add_argument("--sparse", action="store_true",
+                    help="fuse into a block-allocated volume: only the 8^3 blocks near the surfaces are stored")
     a = ap.parse_args()
 
     from easygaussiansplatting_amd import scene as S
@@ -60,7 +64,7 @@ def main():
                                               color=not a.no_color, min_component_faces=a.min_component_faces,
                                               keep_largest=a.keep_largest, smooth_iterations=a.smooth,
                                               simplify_voxels=a.simplify, simplify_placement=a.simplify_placement,
-                                              alpha_min=a.alpha_min, depth_max=a.depth_max)
+                                              sparse=a.sparse, alpha_min=a.alpha_min, depth_max=a.depth_max)
     normals = vertex_normals(vertices, faces, check=False) if a.normals else None
     save_mesh_ply_with_normals(a.out, vertices, faces, colors, normals)
     print("wrote %s: %d vertices, %d faces from %d views" % (a.out, vertices.shape[0], faces.shape[0], len(ds)))

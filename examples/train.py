@@ -91,6 +91,9 @@ def main():
     ap.add_argument("--mesh-simplify", type=float, default=None, metavar="K",
                     help="--mesh: decimate by vertex clustering, one vertex per cell of K voxels (DESIGN §3.21; quadric "
                          "placement, regulariser untuned; topology is not preserved)")
+    ap.add_argument("--mesh-sparse", action="store_true",
+                    help="--mesh: fuse into a block-allocated volume (DESIGN §3.22) that stores only the 8^3 blocks near "
+                         "the surfaces, so that --mesh-voxel may be far finer than a dense volume could hold")
     a = ap.parse_args()
     if a.strategy == "mcmc" and a.cap_max is None:
         ap.error("--strategy mcmc needs --cap-max")
@@ -155,7 +158,7 @@ def main():
         if a.mesh:
             from easygaussiansplatting_amd.mesh import save_mesh_ply
             vertices, faces, colors = tr.extract_mesh(voxel_size=a.mesh_voxel, min_component_faces=a.mesh_min_faces,
-                                                      simplify_voxels=a.mesh_simplify)
+                                                      simplify_voxels=a.mesh_simplify, sparse=a.mesh_sparse)
             save_mesh_ply(a.mesh, vertices, faces, colors)
             print("mesh: %d vertices, %d faces -> %s" % (vertices.shape[0], faces.shape[0], a.mesh))
     if world > 1:
