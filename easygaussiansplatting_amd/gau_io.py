@@ -199,6 +199,9 @@ def load_gs(fn) -> np.ndarray:
         return load_ply(fn)
     if fn.endswith(".npy"):
         return np.load(fn)
+    if fn.endswith(".gsz"):              # a compressed scene (``compress``); not in the reference
+        from .compress import load_compressed
+        return load_compressed(fn)
     raise ValueError("%s is not a supported file." % fn)
 
 

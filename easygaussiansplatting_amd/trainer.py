@@ -880,8 +880,32 @@ class Trainer:
 
     def save(self, fn: str) -> np.ndarray:
         """Checkpoint of ACTIVATED parameters, dtype == gau_io.py:7-12 (gau_io.py:141-156)."""
-        with torch.no_grad():
-            pws, shs, alphas, scales, rots = (x.detach().cpu().numpy() for x in activate(self.params))
-        gs = np.rec.fromarrays([pws, rots, scales, alphas.reshape(-1), shs], dtype=gsdata_type(shs.shape[1]))
+        gs = self._records()
         np.save(fn, gs)
         return gs
+
+    def _records(self) -> np.ndarray:
+        """the ACTIVATED parameters as a record array (``gsdata_type``)"""
+        with torch.no_grad():
+            pws, shs, alphas, scales, rots = (x.detach().cpu().numpy() for x in activate(self.params))
+        return np.rec.fromarrays([pws, rots, scales, alphas.reshape(-1), shs], dtype=gsdata_type(shs.shape[1]))
+
+    def save_compressed(self, fn: str, clusters: int = None, iters: int = 10, weight_by: str = None):
+        """The Gaussians ``save`` writes, as a compressed scene (``compress.save_compressed``): the SH rest
+        against a k-means codebook of ``clusters`` centroids (default min(65536, N // 4): gsplat's figure, untuned here),
+        the other attributes at 8 or 16 bits.  ``weight_by`` = "sum" or "max" weights the codebook by that blending-weight
+        statistic of ``importance()`` over all cameras (LightGaussian's weighting).  -> the dict of arrays written.
+
+        With ``weight_by`` set and several ranks this is a COLLECTIVE, unlike ``save``: ``importance()`` renders each
+        rank's share of the views and all-reduces, so every rank must enter the call; rank 0 then clusters and writes the
+        file and the other ranks return None.  Without ``weight_by`` nothing is exchanged: call it on the rank that writes."""
+        from . import compress
+        if weight_by not in (None, "sum", "max"):
+            raise ValueError("weight_by must be None, 'sum' or 'max', got %r" % (weight_by,))
+        weights = None
+        if weight_by is not None:
+            st = self.importance()
+            if self.world > 1 and self.rank != 0:
+                return None
+            weights = (st.sum if weight_by == "sum" else st.max).contiguous()
+        return compress.save_compressed(fn, self._records(), clusters=clusters, iters=iters, weights=weights)

@@ -94,6 +94,9 @@ def main():
     ap.add_argument("--mesh-sparse", action="store_true",
                     help="--mesh: fuse into a block-allocated volume (DESIGN §3.22) that stores only the 8^3 blocks near "
                          "the surfaces, so that --mesh-voxel may be far finer than a dense volume could hold")
+    ap.add_argument("--save-compressed", default=None, metavar="OUT.gsz",
+                    help="after training, also write the scene compressed (DESIGN §3.23): SH rest against a k-means "
+                         "codebook, other attributes at 8 or 16 bits (the number of centroids is gsplat's default, untuned)")
     a = ap.parse_args()
     if a.strategy == "mcmc" and a.cap_max is None:
         ap.error("--strategy mcmc needs --cap-max")
@@ -154,6 +157,9 @@ def main():
             tr.save_poses(os.path.join(a.out, "poses.npz"))
         if a.bilagrid:
             tr.save_grids(os.path.join(a.out, "grids.npz"))
+        if a.save_compressed:
+            tr.save_compressed(a.save_compressed)
+            print("compressed scene: %d B -> %s" % (os.path.getsize(a.save_compressed), a.save_compressed))
         print("Training is finished.")
         if a.mesh:
             from easygaussiansplatting_amd.mesh import save_mesh_ply
